@@ -8,17 +8,23 @@ unknown — that is `value`.  One process per GPU; for N > 1 the driver launches
 torch.distributed.run and every rank fits its own 1M-case shard (independent local problems: no
 data-path collective, "weak" scaling).
 
-The default single-GPU run also measures every other BASELINE config with the same --steps / --warmup and
-reports them under "configs" (each with ms_per_step, kernel_ms, roofline fraction, traffic and parity against the
-reference-generated golden of that config): C1 at its specified 10k points and at a working set beyond the
-Infinity Cache, C3, C4 (ExpertSolver, 256 stacked right-hand sides), C5 at 1M and at the full 16M points of
-configs[4] on one GPU, and the literal form of configs[4] (`--config C5 --sharded`: ONE Morton-ordered cloud
-partitioned over the ranks, own-points-only neighbour search against a halo band, index-based fit, halo values
-exchanged per step on a side stream under the interior fits; wlsqm/sharded.py HaloCloudSolver).
-`--config Cx` measures one config as `value` instead.
+A plain run sets up, warms up, times exactly --steps steps and prints the headline JSON as its only stdout line; its
+roofline block comes from HIP events over the timed region itself.  Everything else is measured with `--full` only: the
+parity checks against the reference-generated goldens and the CPU oracle, the CPU baseline, dedicated per-kernel timings,
+the strict / accurate numerics modes, and every other BASELINE config with the same --steps / --warmup, reported under
+"configs" (each with ms_per_step, kernel_ms, roofline fraction, traffic and parity against the reference-generated golden
+of that config): C1 at its specified 10k points and at a working set beyond the Infinity Cache, C3, C4 (ExpertSolver,
+256 stacked right-hand sides), C5 at 1M and at the full 16M points of configs[4] on one GPU, and the literal form of
+configs[4] (`--config C5 --sharded`: ONE Morton-ordered cloud partitioned over the ranks, own-points-only neighbour
+search against a halo band, index-based fit, halo values exchanged per step on a side stream under the interior fits;
+wlsqm/sharded.py HaloCloudSolver).  `--config Cx` measures one config as `value` instead.
 
-Rank 0 prints the full record on a line prefixed "# full: " and then, as the LAST line of stdout, the compact headline
-JSON (< 1.5 KB: the contract's fields + roofline + cpu_baseline + a parity digest + one [ms, frac] pair per side config).
+`--dump-outputs DIR` writes what the timed path returned in its last timed step as DIR/<name>.npy (float64, at most
+64 MB in all: a fixed, seeded sample of the rows of a larger output).  The inputs are synthetic and seeded, so two builds
+run with the same arguments can be compared output for output.
+
+With `--full`, rank 0 prints the full record on a line prefixed "# full: " and then, as the LAST line of stdout, the compact
+headline JSON (< 1.5 KB: the contract's fields + roofline + cpu_baseline + a parity digest + one [ms, frac] pair per side config).
 """
 import argparse
 import json
@@ -48,6 +54,26 @@ NDOF = {1: [1, 2, 3, 4, 5], 2: [1, 3, 6, 10, 15], 3: [1, 4, 10, 20, 35]}
 HBM_PEAK_GBPS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 FP64_PEAK_TFLOPS = 78.6    # vector fp64 peak; measured: a lone wave per SIMD issues 62, four waves 74 (tools/ubench/fp64_issue.hip)
 GOLDEN_OF = {"C2": "C2_1M", "C3": "C3_1M", "C5": "C5_1M"}      # reference outputs at the density the metric is quoted on
+DUMP_LIMIT = 64 * 2 ** 20  # bytes: --dump-outputs writes at most this much in all
+
+
+def dump_sample(t, axis=0, limit=DUMP_LIMIT):
+    """The device tensor t as a float64 host array; when it is larger than `limit`, a fixed, seeded sample of its entries
+    along `axis` (sorted indices, the same for every run with the same shape)."""
+    import torch
+    n = t.shape[axis]
+    row = t.numel() // max(1, n) * 8
+    if n * row > limit:
+        idx = np.sort(np.random.default_rng(0).choice(n, max(1, limit // row), replace=False))
+        t = t.index_select(axis, torch.from_numpy(idx).to(t.device))
+    return t.to(torch.float64).cpu().numpy()
+
+
+def dump_outputs(d, outputs):
+    """--dump-outputs: one DIR/<name>.npy per array the timed path returned in its last step."""
+    os.makedirs(d, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def bytes_per_fit(dim, order, nk, knowns):
@@ -265,10 +291,12 @@ def golden_parity(name, dev):
     return acc
 
 
-def measure_fit(name, cfg, n, dev, timer, steps, warmup, rank, parity=True, keep=False, extras=None, unsorted=False):
+def measure_fit(name, cfg, n, dev, timer, steps, warmup, rank, parity=True, keep=False, extras=None, unsorted=False, full=True, dump=False):
     """One BASELINE config through the device-resident dense API: build, time, roofline, parity.
     extras: None (basic fit), "sens" (do_sens: + 8 nk no bytes written per fit) or "iter" (iterative refinement, max_iter 10).
-    unsorted: every case's neighbours in random order (what a ball query or any caller that does not sort by distance hands over)."""
+    unsorted: every case's neighbours in random order (what a ball query or any caller that does not sort by distance hands over).
+    full: also time the launch in a dedicated run (otherwise kernel_ms is the event span of the timed region).
+    dump: res["_outputs"] holds what the last timed step returned (fi)."""
     import torch
     import wlsqm.hip as whip
     dim, order, nk = cfg["dim"], cfg["order"], cfg["nk"]
@@ -360,12 +388,13 @@ def measure_fit(name, cfg, n, dev, timer, steps, warmup, rank, parity=True, keep
     hint.__enter__()
     dt = timer.run(lambda: whip.fit_many_device(*args), steps, warmup)
     kernel = whip.last_kernel()
-    # dominant kernel: HIP events over the timed region itself (Timer.run), on the stream it is launched on; a dedicated run of the same
-    # launch (events inside the library, no Python between the launches) is kept beside it in the full record
+    outputs = {"fi": dump_sample(fi_d)} if dump else None
+    # dominant kernel: HIP events over the timed region itself (Timer.run), on the stream it is launched on; with `full`, a dedicated run of
+    # the same launch (events inside the library, no Python between the launches) is kept beside it in the full record
     ms_region = getattr(timer, "last_event_ms_per_step", None)
-    ms_dedicated = whip.time_fit_device(*args, reps=min(max(steps, 20), 500))
+    ms_dedicated = whip.time_fit_device(*args, reps=min(max(steps, 20), 500)) if full else None
     hint.__exit__()
-    launch_bound = (not ms_region) or ms_region > 1.5 * ms_dedicated          # tiny launches: the span measures Python's launch rate, not the kernel
+    launch_bound = full and ((not ms_region) or ms_region > 1.5 * ms_dedicated)          # tiny launches: the span measures Python's launch rate, not the kernel
     ms_kernel = ms_dedicated if launch_bound else ms_region
     B_fit = bytes_per_fit(dim, order, nk, cfg["knowns"])
     achieved = B_fit * n / (ms_kernel * 1e-3) / 1e9
@@ -416,10 +445,12 @@ def measure_fit(name, cfg, n, dev, timer, steps, warmup, rank, parity=True, keep
         res["parity"] = {"vs_reference_golden": golden_parity_c1(dev)}
     if keep:
         res["_tensors"] = dict(xk=xk_d, fk=fk_d, xi=xi_d, fi=fi_d, F=F)
+    if outputs:
+        res["_outputs"] = outputs
     return res, dt
 
 
-def measure_c4(cfg, n, R, dev, timer, steps, warmup, rank, parity=True):
+def measure_c4(cfg, n, R, dev, timer, steps, warmup, rank, parity=True, full=True, dump=False):
     """BASELINE configs[3]: ExpertSolver on the C2 geometry, prepare once, then right-hand sides F_t = sin(pi x + 0.01 t)
     cos(pi y).  A step = ONE solve_many_device call over R stacked fields; a fit = one (case, field)
     pair.  Algorithmic bytes per fit: fk 8 nk + fi 8 no + the case's [nr x nk] solution operator shared by
@@ -454,21 +485,25 @@ def measure_c4(cfg, n, R, dev, timer, steps, warmup, rank, parity=True):
     t_operator = time.perf_counter() - t0
     dt = timer.run(lambda: solver.solve_many_device(fk, fi), steps, warmup)
     kernel = whip.last_kernel()
-    # the kernel alone, events on the stream it is launched on (torch's current stream is passed to the launch)
-    reps = min(max(steps, 5), 50)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        solver.solve_many_device(fk, fi)
-    e1.record(); torch.cuda.synchronize()
-    ms_kernel = e0.elapsed_time(e1) / reps
-    # time stepping: one fused launch per field
-    fi_seq = torch.zeros_like(fi[0])
-    e0.record()
-    for r in range(min(R, 64)):
-        solver.solve_device(fk[r], fi_seq)
-    e1.record(); torch.cuda.synchronize()
-    ms_step_field = e0.elapsed_time(e1) / min(R, 64)
+    outputs = {"fi": dump_sample(fi, axis=1)} if dump else None
+    ms_kernel = getattr(timer, "last_event_ms_per_step", None)
+    ms_step_field = None
+    if full:
+        # the kernel alone, events on the stream it is launched on (torch's current stream is passed to the launch)
+        reps = min(max(steps, 5), 50)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            solver.solve_many_device(fk, fi)
+        e1.record(); torch.cuda.synchronize()
+        ms_kernel = e0.elapsed_time(e1) / reps
+        # time stepping: one fused launch per field
+        fi_seq = torch.zeros_like(fi[0])
+        e0.record()
+        for r in range(min(R, 64)):
+            solver.solve_device(fk[r], fi_seq)
+        e1.record(); torch.cuda.synchronize()
+        ms_step_field = e0.elapsed_time(e1) / min(R, 64)
     nr = no - bin(cfg["knowns"]).count("1")
     B_fit = 8 * nk + 8 * no + 8 * nr * nk / R       # fk + fi + the case's [nr x nk] operator shared by the R fields
     achieved = B_fit * n * R / (ms_kernel * 1e-3) / 1e9
@@ -481,9 +516,12 @@ def measure_c4(cfg, n, R, dev, timer, steps, warmup, rank, parity=True):
            "value_including_prepare": n * R / (dt / steps + t_operator + t_prepare),
            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                         "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": tsrc, "kernel_ms": ms_kernel,
-                        "kernel": kernel, "algorithmic_bytes_per_launch": B_fit * n * R},
-           "time_stepping": {"ms_per_field": ms_step_field, "fits_per_s": n / (ms_step_field * 1e-3),
-                             "bytes_per_fit": bytes_per_fit(dim, order, nk, cfg["knowns"])}}
+                        "kernel": kernel, "algorithmic_bytes_per_launch": B_fit * n * R}}
+    if full:
+        res["time_stepping"] = {"ms_per_field": ms_step_field, "fits_per_s": n / (ms_step_field * 1e-3),
+                                "bytes_per_fit": bytes_per_fit(dim, order, nk, cfg["knowns"])}
+    else:
+        res["roofline"]["note"] = "kernel_ms: HIP events over the timed region / steps"
     if parity and rank == 0:
         # the last field of the stack against the oracle and the 80-bit solution (the reference has no stacked solve: its
         # ExpertSolver.solve is called once per field, expert.pyx:537-571; the golden of this geometry is C2's)
@@ -505,6 +543,8 @@ def measure_c4(cfg, n, R, dev, timer, steps, warmup, rank, parity=True):
         acc["max_rel_diff_to_sequential_solve_device"] = float(((fi[r] - fi_seq2).abs().amax(0) / fi_seq2.abs().amax(0)).max())
         res["parity"] = {"vs_oracle": acc}
     del fk, fi
+    if outputs:
+        res["_outputs"] = outputs
     return res, dt
 
 
@@ -537,7 +577,7 @@ def morton_order_device(S, bits=16):
     return torch.argsort(key, stable=True)
 
 
-def run_sharded(a, dev, dist, rank, world, timer, parity=True):
+def run_sharded(a, dev, dist, rank, world, timer, parity=True, dump=False):
     """BASELINE configs[4] in its literal form: ONE 3D cloud of world x --ncases Morton-ordered Halton points, partitioned over
     the ranks in contiguous blocks; every rank searches only its own points (against a verified halo band), fits them with the
     index-based kernel from its local tables and, per step, receives only the halo values it names (all_to_all_single on a side
@@ -566,11 +606,15 @@ def run_sharded(a, dev, dist, rank, world, timer, parity=True):
     torch.cuda.synchronize()
     t_setup = time.perf_counter() - t0
 
+    last = [None]
+
     def step():
-        fi = solver.step()
+        fi = last[0] = solver.step()
         solver.values[: solver.n_own] = fi[:, 0] + 1e-7 * (fi[:, 4] + fi[:, 6] + fi[:, 8])      # i3_X2, i3_Y2, i3_Z2
     dt = timer.run(step, a.steps, a.warmup, collective=True)
     kernel = whip.last_kernel()
+    outputs = ({"fi": dump_sample(last[0], limit=DUMP_LIMIT * 3 // 4), "values": dump_sample(solver.values[: solver.n_own], limit=DUMP_LIMIT // 4)}
+               if dump else None)
     # the two parts alone (events on the launch stream): fits without the exchange, exchange without the fits
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
     reps = max(3, min(a.steps, 20))
@@ -636,6 +680,8 @@ def run_sharded(a, dev, dist, rank, world, timer, parity=True):
         acc = _parity.accounting(fi_d.cpu().numpy(), fi_o, truth=truth)
         acc["reference"] = "CPU oracle on the first %d local cases, current field" % ns
         out["parity"] = {"vs_oracle": acc}
+    if outputs:
+        out["_outputs"] = outputs
     return out
 
 
@@ -990,11 +1036,16 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS),
-                    help="measure this config as `value` (default: C2 as `value` plus every other config under `configs`)")
+                    help="measure this config as `value` (default: C2 as `value`, with --full plus every other config under `configs`)")
     ap.add_argument("--ncases", type=int, default=None, help="local fits per GPU per step (default 1M; --sharded: 2M points per rank)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the parity checks (profiling passes)")
-    ap.add_argument("--no-side-configs", action="store_true", help="default run: C2 only")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: parity, CPU baseline, dedicated kernel timings, the "
+                         "numerics modes, the side configs (single GPU) or the sharded configs[4] block (N > 1), and the full record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64, <= 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="(--full) skip the parity checks (profiling passes)")
+    ap.add_argument("--no-side-configs", action="store_true", help="(--full) C2 only")
     ap.add_argument("--nrhs", type=int, default=None, help="C4: right-hand sides stacked per step (default 256 = BASELINE configs[3])")
     ap.add_argument("--sharded", action="store_true",
                     help="C5 in the literal form of BASELINE configs[4]: one Morton-ordered cloud of --ncases points PER RANK, "
@@ -1026,27 +1077,31 @@ def main():
     timer = Timer(dist, dev)
     headline = a.config or "C2"
     cfg = CONFIGS[headline]
-    parity = not a.no_parity
+    parity = a.full and not a.no_parity
+    dump = a.dump_outputs is not None and rank == 0
 
     if a.sharded:
-        out = run_sharded(a, dev, dist, rank, world, timer, parity)
+        out = run_sharded(a, dev, dist, rank, world, timer, parity, dump=dump)
+        outputs = out.pop("_outputs", None)
     elif headline == "C4":
         R = a.nrhs or 256
-        res, dt = measure_c4(cfg, a.ncases, R, dev, timer, a.steps, a.warmup, rank, parity)
+        res, dt = measure_c4(cfg, a.ncases, R, dev, timer, a.steps, a.warmup, rank, parity, full=a.full, dump=dump)
+        outputs = res.pop("_outputs", None)
         out = headline_line(res, world, a, dt, a.ncases * R)
     else:
-        res, dt = measure_fit(headline, cfg, a.ncases, dev, timer, a.steps, a.warmup, rank, parity, keep=True)
+        res, dt = measure_fit(headline, cfg, a.ncases, dev, timer, a.steps, a.warmup, rank, parity, keep=True, full=a.full, dump=dump)
+        outputs = res.pop("_outputs", None)
         tensors = res.pop("_tensors")
         out = headline_line(res, world, a, dt, a.ncases)
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
             from oracle import oracle
             out["cpu_baseline"] = cpu_baseline(oracle, cfg, tensors["xk"], tensors["fk"], tensors["xi"], tensors["F"], a.ncases,
                                                NDOF[cfg["dim"]][cfg["order"]])
         del tensors
         torch.cuda.empty_cache()
-        if a.config is None and world == 1 and not a.no_side_configs:
+        if a.full and a.config is None and world == 1 and not a.no_side_configs:
             out["configs"] = side_configs(a, dev, timer, rank, parity)
-        if a.config is None and world > 1 and not a.no_side_configs:
+        if a.full and a.config is None and world > 1 and not a.no_side_configs:
             # BASELINE configs[4] in its literal form, in the driver's own scaling run: ONE 16M-point 3D cloud partitioned over the
             # N ranks, halo values exchanged over RCCL every step (wlsqm/sharded.py).  Reported beside the C2 weak-scaling value.
             import copy
@@ -1065,8 +1120,13 @@ def main():
                 out["sharded_parity"] = line["parity"]
     if rehearsal:
         out["rehearsal"] = "all ranks on GPU 0, gloo: control-flow check only, not a measurement"
+    if outputs:
+        dump_outputs(a.dump_outputs, outputs)
     if rank == 0:
-        emit(out)
+        if a.full:
+            emit(out)
+        else:
+            print(json.dumps(compact_line(out), separators=(",", ":")), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

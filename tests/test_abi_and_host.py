@@ -251,6 +251,23 @@ def test_bench_headline_is_compact_and_parseable(capsys, tmp_path, monkeypatch):
     assert len(json.dumps(bench.compact_line(full), separators=(",", ":"))) <= bench.COMPACT_LIMIT
 
 
+def test_bench_dump_outputs_are_seeded_and_bounded(tmp_path):
+    """bench.py --dump-outputs: an output under the limit is written whole; a larger one as a sample of its rows that is the same
+    every time and stays within the limit; the files are float64 .npy."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    t = torch.arange(6000, dtype=torch.float64).reshape(1000, 6)
+    assert np.array_equal(bench.dump_sample(t), t.numpy())
+    a = bench.dump_sample(t, limit=4800)
+    assert a.shape == (100, 6) and a.nbytes <= 4800 and np.array_equal(a, bench.dump_sample(t, limit=4800))
+    assert np.all(np.diff(a[:, 0]) > 0) and np.all(a[:, 0] % 6 == 0)          # whole rows of t, in their order
+    assert bench.dump_sample(t.reshape(10, 100, 6), axis=1, limit=4800).shape == (10, 10, 6)
+    bench.dump_outputs(str(tmp_path / "out"), {"fi": a})
+    got = np.load(tmp_path / "out" / "fi.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, a)
+
+
 def test_strict_mode_flag_is_per_thread_and_restored(binding, monkeypatch):
     """wlsqm_hip_set_strict / get_strict (no GPU needed): the context manager restores the previous mode, another thread starts
     from the environment's default, and WLSQM_HIP_STRICT is read by a thread's first use."""

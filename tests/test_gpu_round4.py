@@ -147,7 +147,7 @@ def test_bench_n2_flow_runs_end_to_end_as_a_rehearsal(tmp_path):
     env = dict(os.environ, WLSQM_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--ncases", "200000", "--no-cpu-baseline"]
+           "--ncases", "200000", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

@@ -4,7 +4,7 @@
 set -euo pipefail
 UNIT="$1"; KEY="$2"; shift 2
 PKG=python-wlsqm_amd
-run() { for i in 1 2 3; do WLSQM_BENCH_SIDE="$KEY" python3 bench.py --steps 10 --warmup 3 --no-parity --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1', d['configs_summary'])"; done; }
+run() { for i in 1 2 3; do WLSQM_BENCH_SIDE="$KEY" python3 bench.py --full --steps 10 --warmup 3 --no-parity --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1', d['configs_summary'])"; done; }
 ORIG="$(mktemp /tmp/lib_orig_XXXXXX.so)"; VAR="$(mktemp /tmp/unit_var_XXXXXX.o)"
 cp $PKG/wlsqm/_lib/libwlsqm_hip.so "$ORIG"
 trap 'cp "$ORIG" $PKG/wlsqm/_lib/libwlsqm_hip.so; rm -f "$ORIG" "$VAR"' EXIT

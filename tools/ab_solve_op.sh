@@ -3,7 +3,7 @@
 # times the library as built, then rebuilds solve_op.o with each flag set given, relinks and times again (C4 kernel ms, frac).
 set -euo pipefail
 PKG=python-wlsqm_amd
-run() { python3 bench.py --config C4 --steps 10 --warmup 3 --no-parity 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1', d['roofline']['kernel_ms'], d['roofline']['frac'])"; }
+run() { python3 bench.py --full --config C4 --steps 10 --warmup 3 --no-parity 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1', d['roofline']['kernel_ms'], d['roofline']['frac'])"; }
 ORIG="$(mktemp /tmp/lib_orig_XXXXXX.so)"; VAR="$(mktemp /tmp/unit_var_XXXXXX.o)"
 cp $PKG/wlsqm/_lib/libwlsqm_hip.so "$ORIG"
 # whatever happens below (a failing compile, link or timing command under set -e): the library as built comes back

@@ -62,7 +62,7 @@ for name in ("fetch", "write", "sq1", "sq2", "sq3"):
                                           scratch=int(x.get("Scratch_Size", 0) or 0), workgroup=int(x.get("Workgroup_Size", 0) or 0),
                                           grid=int(x.get("Grid_Size", 0) or 0))
 out = dict(tag=tag, config=cfg,
-           command="tools/profile_config.sh %s %s: rocprofv3 --kernel-trace --pmc <one group> -- python3 bench.py --config %s "
+           command="tools/profile_config.sh %s %s: rocprofv3 --kernel-trace --pmc <one group> -- python3 bench.py --full --config %s "
                    "--steps 5 --warmup 1 (separate passes: FETCH_SIZE, WRITE_SIZE, three SQ groups)" % (tag, cfg, cfg),
            kernels={})
 for k, cs in kern.items():

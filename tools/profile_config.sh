@@ -13,7 +13,7 @@ TAG="$1"; CFG="$2"; CASES="$3"; ALG="$4"; shift 4
 OUT="gpurun_out/prof/${TAG}_${CFG}"
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-COMMON=(--config "$CFG" --no-cpu-baseline --no-parity "$@")
+COMMON=(--full --config "$CFG" --no-cpu-baseline --no-parity "$@")
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o stats -- python3 bench.py "${COMMON[@]}" --steps 50 --warmup 5 > "$OUT/stats.log" 2>&1
 echo "[profile_config] $CFG stats pass done"
 pass() {  # pass NAME counters...
