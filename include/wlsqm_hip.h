@@ -281,6 +281,42 @@ int wlsqm_hip_expert_destroy(wlsqm_expert* h);
 int wlsqm_hip_interpolate_fit_host(int dimension, int order, const double* xi, const double* fi,
                                    const double* x, int64_t x_stride, int64_t nx, int diff, double* out, int device);
 
+/* ---- batched dense solves: wlsqm.utils.lapackdrivers (lapackdrivers.pyx, the m* / *factor* families) ----
+ * `count` independent problems in the reference's layout, Fortran order throughout: A is (n, n, nlhs) with element
+ * (i, j, k) at A[i + n*j + n*n*k]; b is (n, count), ipiv (n, nlhs) int32 with LAPACK's 1-based entries, info one
+ * int32 per factored matrix (LAPACK's INFO: j > 0 if the j-th pivot is exactly zero; the factorization completes).
+ *   getrf / gesv: dgetf2 semantics (partial pivoting, first largest |entry| of the column).
+ *   sytrf / sysv: dsytf2 semantics with uplo = 'U' (Bunch-Kaufman, 1x1 and 2x2 pivots, dsytrf's ipiv encoding); the
+ *                 strict lower triangle of A is neither read nor written.
+ *   getrs / sytrs: right-hand side k is solved with the factor A[:, :, k*lhs_stride] and its pivots; lhs_stride is 1
+ *                 (one factor per right-hand side) or 0 (one factor for every right-hand side, nlhs = 1).
+ *   gesv / sysv:  factor + solve in one launch, one right-hand side per matrix (A, ipiv, info and b all written).
+ * n >= 1, count >= 0 (0: nothing happens), null pointers -> WLSQM_EVALUE.  `info` may be null (not written).
+ * The kernel that runs is a function of n alone, so a matrix gives the same bits at any position of any batch.
+ * The *_device entries enqueue on `stream` without synchronising; the *_host entries take host pointers, stream them
+ * through pinned staging buffers in chunks and return when the results are in the caller's arrays. */
+int wlsqm_hip_getrf_batched_device(int n, int64_t count, double* A, int32_t* ipiv, int32_t* info, int device, void* stream);
+int wlsqm_hip_getrs_batched_device(int n, int64_t count, int lhs_stride, const double* A, const int32_t* ipiv, double* b,
+                                   int device, void* stream);
+int wlsqm_hip_gesv_batched_device(int n, int64_t count, double* A, int32_t* ipiv, int32_t* info, double* b, int device,
+                                  void* stream);
+int wlsqm_hip_sytrf_batched_device(int n, int64_t count, double* A, int32_t* ipiv, int32_t* info, int device, void* stream);
+int wlsqm_hip_sytrs_batched_device(int n, int64_t count, int lhs_stride, const double* A, const int32_t* ipiv, double* b,
+                                   int device, void* stream);
+int wlsqm_hip_sysv_batched_device(int n, int64_t count, double* A, int32_t* ipiv, int32_t* info, double* b, int device,
+                                  void* stream);
+/* A <- (A + A^T) / 2 for every matrix (the reference's msymmetrize) */
+int wlsqm_hip_symmetrize_batched_device(int n, int64_t count, double* A, int device, void* stream);
+int wlsqm_hip_getrf_batched_host(int n, int64_t count, double* A, int32_t* ipiv, int32_t* info, int device);
+int wlsqm_hip_getrs_batched_host(int n, int64_t count, int lhs_stride, const double* A, const int32_t* ipiv, double* b,
+                                 int device);
+int wlsqm_hip_gesv_batched_host(int n, int64_t count, double* A, int32_t* ipiv, int32_t* info, double* b, int device);
+int wlsqm_hip_sytrf_batched_host(int n, int64_t count, double* A, int32_t* ipiv, int32_t* info, int device);
+int wlsqm_hip_sytrs_batched_host(int n, int64_t count, int lhs_stride, const double* A, const int32_t* ipiv, double* b,
+                                 int device);
+int wlsqm_hip_sysv_batched_host(int n, int64_t count, double* A, int32_t* ipiv, int32_t* info, double* b, int device);
+int wlsqm_hip_symmetrize_batched_host(int n, int64_t count, double* A, int device);
+
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ---- */
 /* Runs `reps` back-to-back launches of the fit kernel for batch `b` (device-resident, uniform
  * order) on `stream`, bracketed by HIP events on that stream; returns the mean kernel time in

@@ -125,6 +125,20 @@ def lib():
                                                C.c_void_p, C.c_double, C.c_int, C.c_void_p]
     L.wlsqm_hip_interpolate_fit_host.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                                  C.c_int64, C.c_int, C.c_void_p, C.c_int]
+    # batched dense solves (wlsqm.utils.lapackdrivers, wlsqm.hip.*_batched)
+    for op in ("getrf", "gesv", "sytrf", "sysv"):
+        solve = op in ("gesv", "sysv")
+        rest = [C.c_void_p] * (4 if solve else 3)
+        getattr(L, "wlsqm_hip_%s_batched_device" % op).argtypes = [C.c_int, C.c_int64] + rest + [C.c_int, C.c_void_p]
+        getattr(L, "wlsqm_hip_%s_batched_host" % op).argtypes = [C.c_int, C.c_int64] + rest + [C.c_int]
+    for op in ("getrs", "sytrs"):
+        getattr(L, "wlsqm_hip_%s_batched_device" % op).argtypes = [C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
+        getattr(L, "wlsqm_hip_%s_batched_host" % op).argtypes = [C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 3 + [C.c_int]
+    L.wlsqm_hip_symmetrize_batched_device.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+    L.wlsqm_hip_symmetrize_batched_host.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_int]
+    for op in ("getrf", "getrs", "gesv", "sytrf", "sytrs", "sysv", "symmetrize"):
+        getattr(L, "wlsqm_hip_%s_batched_device" % op).restype = C.c_int
+        getattr(L, "wlsqm_hip_%s_batched_host" % op).restype = C.c_int
     for name in ("wlsqm_hip_fit_many_host", "wlsqm_hip_fit_many_device", "wlsqm_hip_time_fit_device",
                  "wlsqm_hip_expert_create", "wlsqm_hip_expert_create_guest", "wlsqm_hip_expert_prepare", "wlsqm_hip_expert_prepare_device", "wlsqm_hip_expert_solve",
                  "wlsqm_hip_expert_solve_device", "wlsqm_hip_expert_prepare_operator", "wlsqm_hip_expert_solve_many_device", "wlsqm_hip_expert_solve_many",

@@ -13,7 +13,8 @@ from . import _binding as B
 import contextlib
 
 __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_cloud_device", "device_count", "knn", "ball", "nearest",
-           "last_kernel", "set_strict", "get_strict", "strict", "accurate", "strict_intermediates"]
+           "last_kernel", "set_strict", "get_strict", "strict", "accurate", "strict_intermediates",
+           "getrf_batched", "getrs_batched", "gesv_batched", "sytrf_batched", "sytrs_batched", "sysv_batched", "symmetrize_batched"]
 
 
 def _mode_code(mode):
@@ -385,3 +386,123 @@ def nearest(S, X, stream=None):
     s, dev = _stream_and_device(S, stream)
     B.check(B.lib().wlsqm_hip_nearest_device(dim, int(S.shape[0]), _ptr(S), int(X.shape[0]), _ptr(X), dim, _ptr(out), dev, s))
     return out
+
+
+# ---- batched dense solves (the kernels behind wlsqm.utils.lapackdrivers), device-resident ----
+
+def _fortran3(A, name="A"):
+    """A device float64 tensor (n, n, count) with the reference's Fortran layout: strides (1, n, n*n)."""
+    _check(A, name, "float64", 3)
+    n = int(A.shape[0])
+    if int(A.shape[1]) != n or n < 1:
+        raise ValueError("%s must have shape (n, n, count) with n >= 1, got %s" % (name, tuple(A.shape)))
+    if A.shape[2] > 1 and A.stride() != (1, n, n * n) or A.shape[2] <= 1 and A.stride()[:2] != (1, n):
+        raise ValueError("%s must be Fortran-ordered: strides (1, n, n*n), got %s" % (name, A.stride()))
+    return n, int(A.shape[2])
+
+
+def _fortran2(t, n, count, name, dtype_name):
+    _check(t, name, dtype_name, 2)
+    if tuple(t.shape) != (n, count):
+        raise ValueError("%s must have shape (%d, %d), got %s" % (name, n, count, tuple(t.shape)))
+    if count > 1 and t.stride() != (1, n) or count <= 1 and t.stride()[0] != 1:
+        raise ValueError("%s must be Fortran-ordered: strides (1, %d), got %s" % (name, n, t.stride()))
+
+
+def _same_device(ref, *ts):
+    for t in ts:
+        if t is not None and t.device != ref.device:
+            raise ValueError("all tensors must be on the same device")
+
+
+def _pivots_and_info(A, n, count, ipiv, info):
+    import torch
+    if ipiv is None:
+        ipiv = torch.empty((count, n), dtype=torch.int32, device=A.device).t()
+    _fortran2(ipiv, n, count, "ipiv", "int32")
+    if info is None:
+        info = torch.empty((count,), dtype=torch.int32, device=A.device)
+    _check(info, "info", "int32", 1)
+    if int(info.shape[0]) != count or (count > 1 and info.stride()[0] != 1):
+        raise ValueError("info must be a contiguous (count,) int32 tensor")
+    _same_device(A, ipiv, info)
+    return ipiv, info
+
+
+def _factor_batched(op, A, ipiv, info, stream):
+    n, count = _fortran3(A)
+    ipiv, info = _pivots_and_info(A, n, count, ipiv, info)
+    s, dev = _stream_and_device(A, stream)
+    B.check(getattr(B.lib(), "wlsqm_hip_%s_batched_device" % op)(n, count, _ptr(A), _ptr(ipiv), _ptr(info), dev, s))
+    return ipiv, info
+
+
+def _factor_solve_batched(op, A, b, ipiv, info, stream):
+    n, count = _fortran3(A)
+    _fortran2(b, n, count, "b", "float64")
+    ipiv, info = _pivots_and_info(A, n, count, ipiv, info)
+    _same_device(A, b)
+    s, dev = _stream_and_device(A, stream)
+    B.check(getattr(B.lib(), "wlsqm_hip_%s_batched_device" % op)(n, count, _ptr(A), _ptr(ipiv), _ptr(info), _ptr(b), dev, s))
+    return ipiv, info
+
+
+def _solve_batched(op, A, ipiv, b, stream):
+    n, nlhs = _fortran3(A)
+    _check(b, "b", "float64", 2)
+    count = int(b.shape[1])
+    if nlhs not in (1, count):
+        raise ValueError("A holds %d factors: 1 (one factor for every right-hand side) or one per column of b (%d)" % (nlhs, count))
+    _fortran2(b, n, count, "b", "float64")
+    _fortran2(ipiv, n, nlhs, "ipiv", "int32")
+    _same_device(A, ipiv, b)
+    lhs_stride = 1 if nlhs == count and count > 1 else 0
+    s, dev = _stream_and_device(A, stream)
+    B.check(getattr(B.lib(), "wlsqm_hip_%s_batched_device" % op)(n, count, lhs_stride, _ptr(A), _ptr(ipiv), _ptr(b), dev, s))
+    return b
+
+
+def getrf_batched(A, ipiv=None, info=None, stream=None):
+    """LU factorization with partial pivoting (dgetf2 semantics) of every matrix of the device tensor A (n, n, count),
+    float64 with Fortran strides (1, n, n*n), in place on `stream` (default: the current stream).  Returns (ipiv, info):
+    int32 (n, count) Fortran-ordered 1-based pivots and (count,) LAPACK INFO (j > 0: U(j, j) is exactly zero); both are
+    allocated when not passed in."""
+    return _factor_batched("getrf", A, ipiv, info, stream)
+
+
+def getrs_batched(A, ipiv, b, stream=None):
+    """Solve with the factors of getrf_batched: b (n, count) float64, Fortran-ordered, is overwritten by the solutions.
+    A (n, n, count) / ipiv (n, count) give one factor per right-hand side; A (n, n, 1) / ipiv (n, 1) one factor for all
+    of them.  Returns b."""
+    return _solve_batched("getrs", A, ipiv, b, stream)
+
+
+def gesv_batched(A, b, ipiv=None, info=None, stream=None):
+    """getrf_batched + getrs_batched in one launch, one right-hand side per matrix: A gets the LU factors, b (n, count)
+    the solutions.  Returns (ipiv, info)."""
+    return _factor_solve_batched("gesv", A, b, ipiv, info, stream)
+
+
+def sytrf_batched(A, ipiv=None, info=None, stream=None):
+    """Bunch-Kaufman U*D*U^T factorization (dsytf2 semantics, uplo='U') of the upper triangle of every matrix of A
+    (n, n, count), in place; the strict lower triangle is neither read nor written.  Returns (ipiv, info) with dsytrf's
+    pivot encoding."""
+    return _factor_batched("sytrf", A, ipiv, info, stream)
+
+
+def sytrs_batched(A, ipiv, b, stream=None):
+    """Solve with the factors of sytrf_batched (one factor per right-hand side, or A (n, n, 1) for all).  Returns b."""
+    return _solve_batched("sytrs", A, ipiv, b, stream)
+
+
+def sysv_batched(A, b, ipiv=None, info=None, stream=None):
+    """sytrf_batched + sytrs_batched in one launch, one right-hand side per matrix.  Returns (ipiv, info)."""
+    return _factor_solve_batched("sysv", A, b, ipiv, info, stream)
+
+
+def symmetrize_batched(A, stream=None):
+    """A[:, :, k] <- (A[:, :, k] + A[:, :, k]^T) / 2 for every k, in place.  Returns A."""
+    n, count = _fortran3(A)
+    s, dev = _stream_and_device(A, stream)
+    B.check(B.lib().wlsqm_hip_symmetrize_batched_device(n, count, _ptr(A), dev, s))
+    return A
