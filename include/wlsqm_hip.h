@@ -290,7 +290,9 @@ int wlsqm_hip_interpolate_fit_host(int dimension, int order, const double* xi, c
  *                 strict lower triangle of A is neither read nor written.
  *   getrs / sytrs: right-hand side k is solved with the factor A[:, :, k*lhs_stride] and its pivots; lhs_stride is 1
  *                 (one factor per right-hand side) or 0 (one factor for every right-hand side, nlhs = 1).
- *   gesv / sysv:  factor + solve in one launch, one right-hand side per matrix (A, ipiv, info and b all written).
+ *   gesv / sysv:  factor + solve in one launch, one right-hand side per matrix.  A, ipiv and info are written; b gets
+ *                 the solution when the matrix's INFO is 0 and is left bit-unchanged otherwise (dgesv / dsysv solve only
+ *                 when INFO == 0), whether or not `info` is null.
  * n >= 1, count >= 0 (0: nothing happens), null pointers -> WLSQM_EVALUE.  `info` may be null (not written).
  * The kernel that runs is a function of n alone, so a matrix gives the same bits at any position of any batch.
  * The *_device entries enqueue on `stream` without synchronising; the *_host entries take host pointers, stream them

@@ -247,11 +247,12 @@ __global__ __launch_bounds__(64) void lane_kernel(BParams p) {
             else seq_sytrs<1, LP>(sA, sP, sX + lane, n);
         } else {
             double* a = sA + lane; int* pv = sP + lane;
+            int info = 0;
             if (FACT) {
-                const int info = KIND == 0 ? seq_getf2<LP>(a, pv, n) : seq_sytf2<LP>(a, pv, n);
+                info = KIND == 0 ? seq_getf2<LP>(a, pv, n) : seq_sytf2<LP>(a, pv, n);
                 if (p.info) p.info[s0 + lane] = info;
             }
-            if (SOLVE) {
+            if (SOLVE && info == 0) {                             // dgesv / dsysv: a singular system keeps its b as it came
                 if (KIND == 0) seq_getrs<LP, LP>(a, pv, sX + lane, n);
                 else seq_sytrs<LP, LP>(a, pv, sX + lane, n);
             }
@@ -313,9 +314,14 @@ __device__ int grp_getf2(double* a, int* pv, int n, double* rv, int* ri) {
     int info = 0;
     for (int j = 0; j < n; ++j) {
         double v = -1.0; int p = INT_MAX;
-        for (int i = j + tid; i < n; i += NT) { const double t = fabs(a[i + (size_t)n * j]); if (t > v) { v = t; p = i; } }
+        // idamax: nothing beats a NaN head (the key +inf, and the smallest index wins ties); a NaN further down never wins
+        for (int i = j + tid; i < n; i += NT) {
+            double t = fabs(a[i + (size_t)n * j]);
+            if (i == j && isnan(t)) t = INFINITY;
+            if (t > v) { v = t; p = i; }
+        }
         blk_argmax<NT>(v, p, rv, ri);
-        if (p == INT_MAX) p = j;                                  // (a column of NaNs)
+        if (p == INT_MAX) p = j;
         if (tid == 0) pv[j] = p + 1;
         const double d = a[p + (size_t)n * j];
         if (NT > 64) __syncthreads();                             // every wave has read d before the rows move
@@ -373,7 +379,11 @@ __device__ int grp_sytf2(double* a, int* pv, int n, double* rv, int* ri) {
         int kstep = 1, kp = k;
         const double absakk = fabs(U_(k, k));
         double colmax = -1.0; int imax = INT_MAX;
-        for (int i = 1 + tid; i <= k - 1; i += NT) { const double t = fabs(U_(i, k)); if (t > colmax) { colmax = t; imax = i; } }
+        for (int i = 1 + tid; i <= k - 1; i += NT) {              // idamax, NaN head as in grp_getf2
+            double t = fabs(U_(i, k));
+            if (i == 1 && isnan(t)) t = INFINITY;
+            if (t > colmax) { colmax = t; imax = i; }
+        }
         blk_argmax<NT>(colmax, imax, rv, ri);
         if (k == 1) colmax = 0.0;
         else { if (imax == INT_MAX) imax = 1; colmax = fabs(U_(imax, k)); }
@@ -538,12 +548,13 @@ __global__ __launch_bounds__(NT) void group_kernel(BParams p) {
     if (SOLVE)
         for (int i = tid; i < n; i += NT) xs[i] = p.b[(size_t)s * n + i];
     __syncthreads();
+    int info = 0;                                                 // uniform over the workgroup
     if (FACT) {
-        const int info = KIND == 0 ? grp_getf2<NT>(a, gP, n, rv, ri) : grp_sytf2<NT>(a, gP, n, rv, ri);
+        info = KIND == 0 ? grp_getf2<NT>(a, gP, n, rv, ri) : grp_sytf2<NT>(a, gP, n, rv, ri);
         if (tid == 0 && p.info) p.info[s] = info;
         __syncthreads();
     }
-    if (SOLVE) {
+    if (SOLVE && info == 0) {                                     // dgesv / dsysv: a singular system keeps its b as it came
         if (KIND == 0) grp_getrs<NT>(a, gP, xs, ys, n);
         else grp_sytrs<NT>(a, gP, xs, ys, n, rv);
         for (int i = tid; i < n; i += NT) p.b[(size_t)s * n + i] = ys[i];
@@ -598,8 +609,10 @@ static int launch_form(const BParams& p, hipStream_t s) {
 }
 
 static int launch_op(int op, BParams p, hipStream_t s) {
-    // launches of at most 2^24 problems: the grids stay far inside their limits whatever the form
-    const long long CH = 1LL << 24;
+    // launches of at most CH problems, so that blocks x threads stays below 2^31 work-items in every form: lane 2^24 / 64
+    // per block x 64 threads, group of 64 2^24 x 64 = 2^30, group of 256 2^22 x 256 = 2^30 (2^24 x 256 would be 2^32,
+    // past the 32-bit grid size of a dispatch)
+    const long long CH = p.n > 32 ? 1LL << 22 : 1LL << 24;
     const long long count = p.count;
     for (long long c0 = 0; c0 < count; c0 += CH) {
         BParams q = p;

@@ -479,7 +479,8 @@ def getrs_batched(A, ipiv, b, stream=None):
 
 def gesv_batched(A, b, ipiv=None, info=None, stream=None):
     """getrf_batched + getrs_batched in one launch, one right-hand side per matrix: A gets the LU factors, b (n, count)
-    the solutions.  Returns (ipiv, info)."""
+    the solutions.  As dgesv, a system whose info is > 0 (singular) is not solved: its column of b is left bit-unchanged,
+    while its factor, pivots and info are written.  Returns (ipiv, info)."""
     return _factor_solve_batched("gesv", A, b, ipiv, info, stream)
 
 
@@ -496,7 +497,8 @@ def sytrs_batched(A, ipiv, b, stream=None):
 
 
 def sysv_batched(A, b, ipiv=None, info=None, stream=None):
-    """sytrf_batched + sytrs_batched in one launch, one right-hand side per matrix.  Returns (ipiv, info)."""
+    """sytrf_batched + sytrs_batched in one launch, one right-hand side per matrix.  As dsysv, a system whose info is
+    > 0 (singular D) is not solved: its column of b is left bit-unchanged.  Returns (ipiv, info)."""
     return _factor_solve_batched("sysv", A, b, ipiv, info, stream)
 
 

@@ -12,7 +12,8 @@ place exactly as the reference's LAPACK calls do, and return when the results ar
 
 Matrices are Fortran-ordered float64: A (n, n) or (n, n, nlhs), b (n,), (n, nrhs) or (n, nlhs); pivot arrays are
 Fortran-ordered np.intc with LAPACK's 1-based entries.  ``ntasks`` (OpenMP threads in the reference) is accepted and
-ignored.  Like the reference, the solvers do not report singular matrices (the results are then inf / nan); the
+ignored.  Like the reference, the solvers do not report singular matrices: as dgesv / dsysv, a system whose matrix has
+an exactly zero pivot is not solved, and its right-hand side is left as it came (the factor and pivots are written); the
 device-resident entry points wlsqm.hip.getrf_batched & co. return LAPACK's INFO per matrix.
 
 The helpers that have no batch (scaling, the 2x2 and tridiagonal solvers, svd, copies, symmetrization) run on the host
@@ -91,10 +92,10 @@ def _run(fn, *args):
 
 # ---- the GPU families: one factorization (getrf / sytrf) and one solve (getrs / sytrs) each ----
 
-def _factor(kind, A, ipiv, count):
+def _factor(kind, A, ipiv, count, info=None):
     n = A.shape[0]
     fn = B.lib().wlsqm_hip_getrf_batched_host if kind == "ge" else B.lib().wlsqm_hip_sytrf_batched_host
-    _run(fn, n, count, _p(A), _p(ipiv), None)
+    _run(fn, n, count, _p(A), _p(ipiv), _p(info))
 
 
 def _solve(kind, A, ipiv, b, count, lhs_stride):
@@ -122,8 +123,10 @@ def _many_rhs(kind, A, b, keep_A):
     n = _square(A); _rhs(b, n, None)
     F = np.array(A, order="F") if keep_A else A
     ipiv = np.empty(n, dtype=np.intc)
-    _factor(kind, F, ipiv, 1)
-    _solve(kind, F, ipiv, b, b.shape[1], 0)
+    info = np.zeros(1, dtype=np.intc)
+    _factor(kind, F, ipiv, 1, info)
+    if info[0] == 0:                    # dgesv / dsysv: a singular A leaves b as it came
+        _solve(kind, F, ipiv, b, b.shape[1], 0)
     return 0
 
 
