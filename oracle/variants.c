@@ -11,7 +11,8 @@
  *             (lapackdrivers.pyx:553-623, 1628-1665)
  *   V_SYM     upper triangle only, mirrored (the reference sums (w c_m) c_j and (w c_j) c_m separately)
  * With no switch set the routine IS the oracle's arithmetic (checked bit-for-bit against it by the tool).
- * 2D and 3D, any order, knowns mask, WEIGHT_CENTER / UNIFORM. */
+ * 1D, 2D and 3D, any order, knowns mask, WEIGHT_CENTER / UNIFORM.  (The V_SYM bits are pinned against the accurate mode for the 2D / 3D systems up to 10
+ * unknowns: 2D orders 0-3, 3D orders 0-2; 1D and 3D orders 3-4 build their monomials as prod d^p / p! and serve the fast-arithmetic emulation only.) */
 #include <math.h>
 #include <string.h>
 
@@ -22,6 +23,7 @@ static const int P2[15][3] = {{0,0,0},{1,0,0},{0,1,0},{2,0,0},{1,1,0},{0,2,0},{3
 static const int P3[35][3] = {{0,0,0},{1,0,0},{0,1,0},{0,0,1},{2,0,0},{1,1,0},{0,2,0},{0,1,1},{0,0,2},{1,0,1},
     {3,0,0},{2,1,0},{1,2,0},{0,3,0},{0,2,1},{0,1,2},{0,0,3},{1,0,2},{2,0,1},{1,1,1},
     {4,0,0},{3,1,0},{2,2,0},{1,3,0},{0,4,0},{0,3,1},{0,2,2},{0,1,3},{0,0,4},{1,0,3},{2,0,2},{3,0,1},{2,1,1},{1,2,1},{1,1,2}};
+static const int P1[5][3] = {{0,0,0},{1,0,0},{2,0,0},{3,0,0},{4,0,0}};
 static const double FACT[9] = {1, 1, 2, 6, 24, 120, 720, 5040, 40320};
 
 static double mac(double a, double b, double c, int flags) { return (flags & V_FMA) ? fma(b, c, a) : a + b * c; }
@@ -41,7 +43,14 @@ static void monomials(int dim, int order, int no, const double* d, double* c) {
     double dx = d[0], dy = d[1], dz = dim == 3 ? d[2] : 0., dx2 = dx * dx, dy2 = dy * dy, dz2 = dz * dz;
     const double s6 = 1. / 6., s24 = 1. / 24.;
     c[0] = 1.;
-    if (dim == 2) {
+    if (dim == 1 || (dim == 3 && order >= 3)) {
+        const int (*P)[3] = dim == 1 ? P1 : P3;
+        for (int a = 1; a < no; a++) {
+            double v = 1.;
+            for (int m = 0; m < dim; m++) for (int e = 0; e < P[a][m]; e++) v *= d[m];
+            c[a] = v / (FACT[P[a][0]] * FACT[P[a][1]] * FACT[P[a][2]]);
+        }
+    } else if (dim == 2) {
         if (order >= 1) { c[1] = dx; c[2] = dy; }
         if (order >= 2) { c[3] = 0.5 * dx2; c[4] = dx * dy; c[5] = 0.5 * dy2; }
         if (order == 3) { c[6] = s6 * dx2 * dx; c[7] = 0.5 * dx2 * dy; c[8] = 0.5 * dx * dy2; c[9] = s6 * dy * dy2; }
@@ -51,15 +60,13 @@ static void monomials(int dim, int order, int no, const double* d, double* c) {
     } else {
         if (order >= 1) { c[1] = dx; c[2] = dy; c[3] = dz; }
         if (order >= 2) { c[4] = 0.5 * dx2; c[5] = dx * dy; c[6] = 0.5 * dy2; c[7] = dy * dz; c[8] = 0.5 * dz2; c[9] = dx * dz; }
-        /* orders 3-4 in 3D are not part of the study */
     }
-    (void)no;
 }
 
 /* one case; returns 0.  xk [nk, dim], fi in/out [no] */
 static void fit_case(int dim, int order, int no, int nk, const double* xk, const double* fk, const double* xi, double* fi,
                      long long knowns, int wm, int flags, int nsplit) {
-    const int (*P)[3] = dim == 2 ? P2 : P3;
+    const int (*P)[3] = dim == 1 ? P1 : dim == 2 ? P2 : P3;
     double c[128][35], w[128], t[128], M[35][35], g[35];
     double max_d2 = 0.;
     for (int k = 0; k < nk; k++) {
@@ -80,7 +87,7 @@ static void fit_case(int dim, int order, int no, int nk, const double* xk, const
         /* distinct moments mu(p,q,r) = sum w dx^p dy^q dz^r, then M[a][b] = mu(Pa+Pb) / (Pa! Pb!) */
         double mu[9][9][9];
         int D = 2 * order;
-        for (int p = 0; p <= D; p++) for (int q = 0; p + q <= D; q++) for (int r = 0; p + q + r <= (dim == 3 ? D : p + q); r++) {
+        for (int p = 0; p <= D; p++) for (int q = 0; p + q <= (dim == 1 ? p : D); q++) for (int r = 0; p + q + r <= (dim == 3 ? D : p + q); r++) {
             for (int k = 0; k < nk; k++) {
                 double d[3] = {0, 0, 0};
                 for (int m = 0; m < dim; m++) d[m] = xk[k * dim + m] - xi[m];
@@ -176,7 +183,7 @@ static void fit_case(int dim, int order, int no, int nk, const double* xk, const
 
 int wlsqm_variant_fit_many(int dim, int order, int no, long ncases, int nk, const double* xk, const double* fk, const double* xi,
                            double* fi, long long knowns, int wm, int flags, int nsplit) {
-    if (nk > 128 || no > 35 || (dim != 2 && dim != 3)) return -1;
+    if (nk > 128 || no > 35 || dim < 1 || dim > 3) return -1;
 #pragma omp parallel for schedule(static)
     for (long j = 0; j < ncases; j++)
         fit_case(dim, order, no, nk, xk + j * nk * dim, fk + j * nk, xi + j * dim, fi + j * no, knowns, wm, flags, nsplit);
@@ -188,7 +195,7 @@ int wlsqm_variant_fit_many(int dim, int order, int no, long ncases, int nk, cons
 int wlsqm_variant_fit_many_ragged(int dim, int order, int no, long ncases, int max_nk, const double* xk, const double* fk,
                                   const int* nk, const double* xi, double* fi, long fi_stride, const long long* knowns,
                                   const int* wm, int flags, int nsplit) {
-    if (max_nk > 128 || no > 35 || (dim != 2 && dim != 3)) return -1;
+    if (max_nk > 128 || no > 35 || dim < 1 || dim > 3) return -1;
 #pragma omp parallel for schedule(static)
     for (long j = 0; j < ncases; j++) {
         int n = nk[j] < max_nk ? nk[j] : max_nk;
