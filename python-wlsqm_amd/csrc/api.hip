@@ -1,6 +1,6 @@
 // api.hip — C ABI of libwlsqm_hip.so (see include/wlsqm_hip.h for the contract and the
-// reference file:line each entry point replaces).  Host logic only; kernels live in
-// fit_lane.hip / fit_tile.hip / fit_wave.hip.
+// reference file:line each entry point replaces).  Host logic only: the entry points and launch_fit, which offers a batch to the
+// kernel families (one fit_*.hip each, declared in wlsqm_dispatch.hpp) in a fixed order.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -11,7 +11,7 @@
 #include <string>
 #include <vector>
 
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "hostio.hpp"
 
 namespace wlsqm {
@@ -28,22 +28,6 @@ int hip_fail(hipError_t e, const char* what) {
 const char* last_kernel_name() { return g_kernel; }
 void note_kernel(const char* name) { g_kernel = name; }
 
-int launch_fit_lane(int dimension, int order, const KParams& p, hipStream_t stream);
-int launch_fit_tile(int dimension, int order, const KParams& p, long long max_nk, hipStream_t stream, bool* handled);
-int launch_fit_wave(int dimension, int order, const KParams& p, hipStream_t stream);
-int launch_fit_moment(int dimension, int order, const KParams& p, long long max_nk, hipStream_t stream, bool* handled);
-int launch_fit_ring(int dimension, int order, const KParams& p, long long max_nk, hipStream_t stream, bool* handled);
-int launch_fit_ring_gather(int dimension, int order, const KParams& p, long long max_nk, hipStream_t stream, bool* handled);
-int launch_fit_tilek(int dimension, int order, const KParams& p, long long max_nk, hipStream_t stream, bool* handled);
-long long preferred_slots(int dimension, int order, long long max_nk);
-int launch_fit_rows(int dimension, int order, const KParams& p, hipStream_t stream, bool* handled);
-int launch_fit_chunk(int dimension, int order, const KParams& p, long long K, hipStream_t stream, bool* handled);
-int launch_fit_chunk_refine(int dimension, int order, const KParams& p, long long K, hipStream_t stream, bool* handled);
-int launch_fit_sens(int dimension, int order, const KParams& p, long long K, hipStream_t stream, bool* handled);
-int launch_fit_strict(int dimension, int order, const KParams& p, const StrictDebug* dbg, hipStream_t stream);
-int launch_fit_stage(int dimension, int order, const KParams& p, long long K, hipStream_t stream, bool* handled);
-int launch_fit_stage_refine(int dimension, int order, const KParams& p, long long K, hipStream_t stream, bool* handled);
-
 // Numerics mode of the calling thread: 0 = the fast kernels, 1 = reference-order arithmetic (fit_strict.hip), 2 = accurate
 // (fit_accurate.hip: reference-order arithmetic with the normal matrix assembled from its upper triangle).  The first use on a
 // thread takes WLSQM_HIP_STRICT from the environment (unset / 0, 1, 2 or "accurate"); wlsqm_hip_set_strict() overrides it.
@@ -59,8 +43,8 @@ bool accurate_mode() { return strict_mode_value() == 2; }
 bool strict_mode() { return strict_mode_value() >= 1; }
 static int strict_mode_value() {
     if (g_strict < 0) {
-        const char* e = getenv("WLSQM_HIP_STRICT");
-        g_strict = (!e || !e[0] || e[0] == '0') ? 0 : ((e[0] == '2' || e[0] == 'a' || e[0] == 'A') ? 2 : 1);
+        const char c = env_first("WLSQM_HIP_STRICT");
+        g_strict = (!c || c == '0') ? 0 : ((c == '2' || c == 'a' || c == 'A') ? 2 : 1);
     }
     return g_strict;
 }
@@ -105,8 +89,8 @@ __global__ void gather_rows_kernel(const KParams p, int dim, long long K, long l
 // (WLSQM_HIP_REPACK_MB, default 512), so a 16M-case odd-K or index-based call needs O(slice) extra memory, not a second copy
 // of the batch.  The slices run back to back on the stream and reuse the same block.
 static size_t repack_slice_bytes() {
-    const char* e = getenv("WLSQM_HIP_REPACK_MB");
-    const long long mb = e ? atoll(e) : 512;
+    long long mb = 512;
+    env_int("WLSQM_HIP_REPACK_MB", &mb);
     return (size_t)(mb > 0 ? mb : 512) << 20;
 }
 
@@ -162,9 +146,10 @@ static int fit_through_dense_scratch(int dimension, int order, const KParams& p,
     return rc != WLSQM_OK ? rc : rc2;
 }
 
+// What the repack hands on, and so what need not be repacked: dense rows with an even neighbour count.
 static bool dense_layout_ok(int dim, const KParams& p, long long K) {
-    if (p.sxk_k != dim || p.sxk_j != K * dim || p.sfk_k != 1 || p.sfk_j != K || (K % 2) != 0) return false;
-    return ((reinterpret_cast<uintptr_t>(p.xk) | reinterpret_cast<uintptr_t>(p.fk)) & 15u) == 0;
+    if ((K % 2) != 0) return false;
+    return dense_rows(dim, p, K);
 }
 
 int launch_fit(int dimension, int order, const KParams& p_in, long long max_nk, hipStream_t stream) {
@@ -180,56 +165,31 @@ int launch_fit(int dimension, int order, const KParams& p_in, long long max_nk, 
         }
     }
     if (strict_mode()) return launch_fit_strict(dimension, order, p, nullptr, stream);   // any layout, any shape, all extras
-    {
-        const char* off = getenv("WLSQM_HIP_DISABLE_TILE");
-        const char* norp = getenv("WLSQM_HIP_DISABLE_REPACK");
-        const bool tiles_on = !(off && off[0] == '1') && !(norp && norp[0] == '1');
-        if (tiles_on && !p.hoods && !p.case_index && p.xk && p.fk && no <= 15 && max_nk >= 2 && p.ncases >= 256 &&
-            !dense_layout_ok(dimension, p, max_nk)) {
-            bool done = false;
-            const int rc = fit_through_dense_scratch(dimension, order, p, max_nk, stream, /*gather=*/false, &done);
-            if (rc != WLSQM_OK || done) return rc;
-        }
-    }
+    // The families in the order they are asked.  A step is over — launch_fit returns rc — when it failed or took the batch.
     bool handled = false;
-    int rc = launch_fit_stage(dimension, order, p, max_nk, stream, &handled);     // one lane per case, rows staged through LDS (round 4)
-    if (rc != WLSQM_OK || handled) return rc;
-    rc = launch_fit_stage_refine(dimension, order, p, max_nk, stream, &handled);  // the same mapping with the refinement sweeps (fit_stage_iter.hip)
-    if (rc != WLSQM_OK || handled) return rc;
-    rc = launch_fit_ring(dimension, order, p, max_nk, stream, &handled);          // one-kernel fit of the 15-unknown systems
-    if (rc != WLSQM_OK || handled) return rc;
-    rc = launch_fit_ring_gather(dimension, order, p, max_nk, stream, &handled);   // the same on index-based input (2D order 4)
-    if (rc != WLSQM_OK || handled) return rc;
-    rc = launch_fit_moment(dimension, order, p, max_nk, stream, &handled);
-    if (rc != WLSQM_OK || handled) return rc;
-    rc = launch_fit_tile(dimension, order, p, max_nk, stream, &handled);
-    if (rc != WLSQM_OK || handled) return rc;
-    rc = launch_fit_tilek(dimension, order, p, max_nk, stream, &handled);
-    if (rc != WLSQM_OK || handled) return rc;
-    rc = launch_fit_sens(dimension, order, p, max_nk, stream, &handled);     // sensitivities of the shapes without a tile kernel
-    if (rc != WLSQM_OK || handled) return rc;
-    if (no <= 15) {
-        rc = launch_fit_chunk_refine(dimension, order, p, max_nk, stream, &handled);   // refinement of the 10- / 15-unknown systems
-        if (rc != WLSQM_OK || handled) return rc;
-    }
-    {
-        // index-based input no tiled kernel took: gather it into dense rows and dispatch again (the dense tables are complete)
-        const char* off = getenv("WLSQM_HIP_DISABLE_TILE");
-        const char* norp = getenv("WLSQM_HIP_DISABLE_REPACK");
-        const bool tiles_on = !(off && off[0] == '1') && !(norp && norp[0] == '1');
-        if (tiles_on && p.hoods && !p.case_index && no <= 15 && max_nk >= 2 && p.ncases >= 256) {
-            bool done = false;
-            rc = fit_through_dense_scratch(dimension, order, p, max_nk, stream, /*gather=*/true, &done);
-            if (rc != WLSQM_OK || done) return rc;
-        }
-    }
-    if (no <= 15) {
-        rc = launch_fit_chunk(dimension, order, p, max_nk, stream, &handled);   // any K: neighbours through LDS in chunks, two passes
-        if (rc != WLSQM_OK || handled) return rc;
+    int rc = WLSQM_OK;
+    auto over = [&](FitLauncher* family) { rc = family(dimension, order, p, max_nk, stream, &handled); return rc != WLSQM_OK || handled; };
+    auto over_scratch = [&](bool gather) { rc = fit_through_dense_scratch(dimension, order, p, max_nk, stream, gather, &handled); return rc != WLSQM_OK || handled; };
+    const bool small = no <= 15;                                     // at most 15 unknowns: the tiled kernels' systems
+    const bool scratch_ok = repack_enabled() && !p.case_index && small && max_nk >= 2 && p.ncases >= 256;
+    // dense rows the tiled kernels cannot take as they are: repacked, and dispatched again from there
+    if (scratch_ok && !p.hoods && p.xk && p.fk && !dense_layout_ok(dimension, p, max_nk) && over_scratch(/*gather=*/false)) return rc;
+    if (over(launch_fit_stage)) return rc;                           // one lane per case, rows staged through LDS (round 4)
+    if (over(launch_fit_stage_refine)) return rc;                    // the same mapping with the refinement sweeps
+    if (over(launch_fit_ring)) return rc;                            // one-kernel fit of the 15-unknown systems
+    if (over(launch_fit_ring_gather)) return rc;                     // the same on index-based input (2D order 4)
+    if (over(launch_fit_moment)) return rc;                          // 2D order 4 in two kernels: moments, then the solve
+    if (over(launch_fit_tile)) return rc;                            // fixed-K tile tables
+    if (over(launch_fit_tilek)) return rc;                           // runtime-K tile kernels, with or without extras
+    if (over(launch_fit_sens)) return rc;                            // sensitivities of the shapes without a tile kernel
+    if (small && over(launch_fit_chunk_refine)) return rc;           // refinement of the 10- / 15-unknown systems
+    // index-based input no tiled kernel took: gathered into dense rows and dispatched again (the dense tables are complete)
+    if (scratch_ok && p.hoods && over_scratch(/*gather=*/true)) return rc;
+    if (small) {
+        if (over(launch_fit_chunk)) return rc;                       // any K: neighbours through LDS in chunks, two passes
         return launch_fit_lane(dimension, order, p, stream);
     }
-    rc = launch_fit_rows(dimension, order, p, stream, &handled);        // basic fit of the 3D order-3/4 systems
-    if (rc != WLSQM_OK || handled) return rc;
+    if (over(launch_fit_rows)) return rc;                            // basic fit of the 3D order-3/4 systems
     return launch_fit_wave(dimension, order, p, stream);
 }
 
@@ -360,6 +320,39 @@ static KParams params_from(const wlsqm_batch* b) {
     return p;
 }
 
+// The iteration counter of the device entry points.  It is only kept when the caller asks for it: unless the call is iterative AND
+// has an iterations_out, begin allocates nothing and end does not synchronise — the call enqueues kernels and nothing else, which is
+// legal inside a stream capture.  Between the two, p.iters_out is the counter (one device int, cleared).
+static int iter_counter_begin(KParams& p, const int32_t* iterations_out, hipStream_t s) {
+    if (!p.iterative || !iterations_out) return WLSQM_OK;
+    int* d_it = nullptr;
+    const int rc = scratch_alloc_async(reinterpret_cast<void**>(&d_it), sizeof(int), s);
+    if (rc != WLSQM_OK) return rc;
+    const hipError_t e = hipMemsetAsync(d_it, 0, sizeof(int), s);
+    if (e != hipSuccess) { (void)scratch_free_async(d_it, s); return hip_fail(e, "hipMemsetAsync"); }
+    p.iters_out = d_it;
+    return WLSQM_OK;
+}
+// rc: what the launches returned.  On success *iterations_out is 0 for a non-iterative call and the maximum over the cases
+// otherwise; the counter is freed whatever happened.
+static int iter_counter_end(KParams& p, int rc, int32_t* iterations_out, hipStream_t s) {
+    int* const d_it = p.iters_out;
+    p.iters_out = nullptr;
+    if (rc == WLSQM_OK && iterations_out) {
+        *iterations_out = 0;
+        if (d_it) {
+            hipError_t e = hipMemcpyAsync(iterations_out, d_it, sizeof(int), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) rc = hip_fail(e, "iterations_out");
+            // a case without unknowns is a no-op for the kernels, but the reference's loop still runs for it and stops at its
+            // second pass (impl.pyx:1026-1081): the maximum over the cases is never below 1
+            else if (*iterations_out < 1) *iterations_out = 1;
+        }
+    }
+    const int rc2 = scratch_free_async(d_it, s);
+    return rc != WLSQM_OK ? rc : rc2;
+}
+
 }  // namespace wlsqm
 
 using namespace wlsqm;
@@ -427,28 +420,10 @@ int wlsqm_hip_fit_many_device(const wlsqm_batch* b, int device, void* stream, in
     hipStream_t s = (hipStream_t)stream;
     KParams p = params_from(b);
     if (case_index) { p.case_index = (const long long*)case_index; p.ncases = ncases_sel; }
-    // The iteration counter is only kept when the caller asks for it: without iterations_out the call enqueues kernels and
-    // nothing else (no allocation, no host synchronisation: legal inside a stream capture).
-    int* d_it = nullptr;
-    if (b->iterative && iterations_out) {
-        rc = scratch_alloc_async(reinterpret_cast<void**>(&d_it), sizeof(int), s); if (rc != WLSQM_OK) return rc;
-        WLSQM_HIP_CHECK(hipMemsetAsync(d_it, 0, sizeof(int), s));
-        p.iters_out = d_it;
-    }
+    rc = iter_counter_begin(p, iterations_out, s);
+    if (rc != WLSQM_OK) return rc;
     rc = launch_fit(b->dimension, order_uniform, p, b->max_nk, s);
-    if (rc != WLSQM_OK) { (void)scratch_free_async(d_it, s); return rc; }
-    if (iterations_out) {
-        *iterations_out = 0;
-        if (d_it) {
-            WLSQM_HIP_CHECK(hipMemcpyAsync(iterations_out, d_it, sizeof(int), hipMemcpyDeviceToHost, s));
-            WLSQM_HIP_CHECK(hipStreamSynchronize(s));
-            // a case without unknowns is a no-op for the kernels, but the reference's loop still runs for it and stops at its
-            // second pass (impl.pyx:1026-1081): the maximum over the cases is never below 1
-            if (*iterations_out < 1) *iterations_out = 1;
-            rc = scratch_free_async(d_it, s);
-        }
-    }
-    return rc;
+    return iter_counter_end(p, rc, iterations_out, s);
 }
 
 }  // extern "C"
@@ -538,8 +513,7 @@ int wlsqm_hip_fit_many_device_orders(const wlsqm_batch* b, int device, void* str
     rc = scratch_alloc_async(reinterpret_cast<void**>(&ws), (size_t)(5 * n + 8 + 5 * nb) * sizeof(long long), s);
     if (rc != WLSQM_OK) return rc;
     long long* blk = ws + 8 + 5 * n;
-    int* d_it = nullptr;
-    auto cleanup = [&](int code) { (void)scratch_free_async(ws, s); (void)scratch_free_async(d_it, s); return code; };
+    auto cleanup = [&](int code) { (void)scratch_free_async(ws, s); return code; };
     if (nb > 0x7fffffffll) { set_error("fit_many_device_orders: batch too large for one launch"); return cleanup(WLSQM_EVALUE); }
     // (kernels only, no hipMemsetAsync: a memset node on memory allocated inside a stream capture aborted the replay on ROCm 7.2;
     // the scan writes all five totals, also for an empty batch)
@@ -559,32 +533,17 @@ int wlsqm_hip_fit_many_device_orders(const wlsqm_batch* b, int device, void* str
         if (e != hipSuccess) return cleanup(hip_fail(e, "order_scatter_kernel"));
     }
     KParams p = params_from(b);
-    if (b->iterative && iterations_out) {
-        rc = scratch_alloc_async(reinterpret_cast<void**>(&d_it), sizeof(int), s);
-        if (rc != WLSQM_OK) return cleanup(rc);
-        e = hipMemsetAsync(d_it, 0, sizeof(int), s);
-        if (e != hipSuccess) return cleanup(hip_fail(e, "hipMemsetAsync"));
-        p.iters_out = d_it;
-    }
-    for (int o = 0; o <= max_order; ++o) {            // buckets above max_order are empty by construction and never launched: a
+    rc = iter_counter_begin(p, iterations_out, s);
+    if (rc != WLSQM_OK) return cleanup(rc);
+    for (int o = 0; o <= max_order && rc == WLSQM_OK; ++o) {            // buckets above max_order are empty by construction and never launched: a
         // kernel of order o writes no(o) doubles per fi / sens row, and the caller's rows are only promised wide enough for max_order
         if (wlsqm_hip_number_of_dofs(b->dimension, o) < 0) continue;
         p.case_index = ws + 8 + (long long)o * n;
         p.ncases = n;                                 // the launch is sized for the whole batch; the bucket's real size stays on the device
         p.ncases_dev = ws + o;
         rc = launch_fit(b->dimension, o, p, b->max_nk, s);
-        if (rc != WLSQM_OK) return cleanup(rc);
     }
-    if (iterations_out) {
-        *iterations_out = 0;
-        if (d_it) {
-            e = hipMemcpyAsync(iterations_out, d_it, sizeof(int), hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) return cleanup(hip_fail(e, "iterations_out"));
-            if (*iterations_out < 1) *iterations_out = 1;
-        }
-    }
-    return cleanup(WLSQM_OK);
+    return cleanup(iter_counter_end(p, rc, iterations_out, s));
 }
 
 int wlsqm_hip_strict_intermediates_device(const wlsqm_batch* b, int device, void* stream, int order_uniform,
@@ -624,7 +583,7 @@ static HostCtx* host_ctx(int device) {
 static double now_s() { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec + 1e-9 * t.tv_nsec; }
 
 int wlsqm_hip_fit_many_host(const wlsqm_batch* b, int device, int32_t* iterations_out) {
-    const bool trace = getenv("WLSQM_HIP_TRACE") != nullptr;
+    const bool trace = env_present("WLSQM_HIP_TRACE");
     const double t_start = now_s();
     double t_prev = t_start;
     auto mark = [&](const char* what) {
@@ -664,11 +623,10 @@ int wlsqm_hip_fit_many_host(const wlsqm_batch* b, int device, int32_t* iteration
     // caller's rows.  (Uniform-order batches only: the order buckets have an index of their own.)  WLSQM_HIP_HOST_NK_ORDER=0: off.
     std::vector<int64_t> perm;
     {
-        const char* e = getenv("WLSQM_HIP_HOST_NK_ORDER");
         int32_t min_nk = n > 0 ? h_nk[0] : 0;
         bool same_order = true;
         for (int64_t j = 0; j < n; ++j) { if (h_nk[j] < min_nk) min_nk = h_nk[j]; same_order = same_order && h_order[j] == h_order[0]; }
-        if (!(e && e[0] == '0') && same_order && n >= 1024 && max_nk - min_nk >= 8) {
+        if (env_first("WLSQM_HIP_HOST_NK_ORDER") != '0' && same_order && n >= 1024 && max_nk - min_nk >= 8) {
             std::vector<int64_t> start((size_t)max_nk + 2, 0);
             for (int64_t j = 0; j < n; ++j) ++start[(size_t)h_nk[j] + 1];
             for (size_t v = 1; v < start.size(); ++v) start[v] += start[v - 1];
@@ -787,7 +745,7 @@ int wlsqm_hip_fit_many_host(const wlsqm_batch* b, int device, int32_t* iteration
     return WLSQM_OK;
 }
 
-static int cloud_params(KParams& p, int dimension, int order, int64_t ncases, int64_t max_nk, const double* S, const double* F,
+static int cloud_params(KParams& p, int dimension, int order, int64_t ncases, const double* S, const double* F,
                         const int32_t* hoods, int64_t hoods_stride_case, const int32_t* point_index, const int32_t* nk,
                         const int64_t* knowns, const int32_t* wm, double* fi, int64_t fi_stride_case) {
     if (dimension < 1 || dimension > 3) { set_error("dimension must be 1, 2 or 3"); return WLSQM_EVALUE; }
@@ -798,7 +756,6 @@ static int cloud_params(KParams& p, int dimension, int order, int64_t ncases, in
     p.hoods = hoods; p.shoods_j = hoods_stride_case; p.S = S; p.F = F; p.pidx = point_index;
     p.nk = nk; p.snk = 1; p.knowns = (const long long*)knowns; p.sknowns = 1; p.wm = wm; p.swm = 1;
     p.fi = fi; p.sfi_j = fi_stride_case; p.ncases = ncases;
-    (void)max_nk;
     return WLSQM_OK;
 }
 
@@ -809,7 +766,7 @@ int wlsqm_hip_fit_cloud_device(int dimension, int order, int64_t ncases, int64_t
                                double* sens, int64_t sens_stride_case, int64_t sens_stride_k, int do_sens,
                                int iterative, int max_iter, int device, void* stream, int32_t* iterations_out) {
     KParams p;
-    int rc = cloud_params(p, dimension, order, ncases, max_nk, S, F, hoods, hoods_stride_case, point_index, nk, knowns,
+    int rc = cloud_params(p, dimension, order, ncases, S, F, hoods, hoods_stride_case, point_index, nk, knowns,
                           weighting_method, fi, fi_stride_case);
     if (rc != WLSQM_OK) return rc;
     DeviceScope scope;
@@ -818,22 +775,10 @@ int wlsqm_hip_fit_cloud_device(int dimension, int order, int64_t ncases, int64_t
     hipStream_t s = (hipStream_t)stream;
     p.sens = (do_sens ? sens : nullptr); p.ss_j = sens_stride_case; p.ss_k = sens_stride_k;
     p.do_sens = (do_sens && sens) ? 1 : 0; p.iterative = iterative ? 1 : 0; p.max_iter = max_iter;
-    int* d_it = nullptr;               // as in wlsqm_hip_fit_many_device: only when the caller wants the count
-    if (iterative && iterations_out) {
-        rc = scratch_alloc_async(reinterpret_cast<void**>(&d_it), sizeof(int), s); if (rc != WLSQM_OK) return rc;
-        WLSQM_HIP_CHECK(hipMemsetAsync(d_it, 0, sizeof(int), s));
-        p.iters_out = d_it;
-    }
+    rc = iter_counter_begin(p, iterations_out, s);
+    if (rc != WLSQM_OK) return rc;
     rc = launch_fit(dimension, order, p, max_nk, s);
-    if (rc != WLSQM_OK) { (void)scratch_free_async(d_it, s); return rc; }
-    if (iterations_out) *iterations_out = 0;
-    if (d_it) {
-        WLSQM_HIP_CHECK(hipMemcpyAsync(iterations_out, d_it, sizeof(int), hipMemcpyDeviceToHost, s));
-        WLSQM_HIP_CHECK(hipStreamSynchronize(s));
-        if (*iterations_out < 1) *iterations_out = 1;
-        rc = scratch_free_async(d_it, s);
-    }
-    return rc;
+    return iter_counter_end(p, rc, iterations_out, s);
 }
 
 static int time_launches(int dimension, int order, const KParams& p, long long max_nk, hipStream_t s, int reps, float* ms_out) {
@@ -859,7 +804,7 @@ int wlsqm_hip_time_fit_cloud_device(int dimension, int order, int64_t ncases, in
                                     const int32_t* weighting_method, double* fi, int64_t fi_stride_case,
                                     int device, void* stream, int reps, float* ms_out) {
     KParams p;
-    int rc = cloud_params(p, dimension, order, ncases, max_nk, S, F, hoods, hoods_stride_case, point_index, nk, knowns,
+    int rc = cloud_params(p, dimension, order, ncases, S, F, hoods, hoods_stride_case, point_index, nk, knowns,
                           weighting_method, fi, fi_stride_case);
     if (rc != WLSQM_OK) return rc;
     DeviceScope scope;

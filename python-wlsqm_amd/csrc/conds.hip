@@ -8,7 +8,7 @@
 //   1. reduced normal matrix A[j,m] = sum_k w_k c[k,r2o[m]] c[k,r2o[j]]   (impl.pyx:566-602, via infra.remap)
 //   2. Ruiz equilibration exactly as lapackdrivers.pyx:553-623 (eps 1e-15, <= 100 sweeps), applied as :293-299
 //   3. singular values by one-sided Jacobi (Hestenes) rotations on the columns; cond = s_max / s_min.
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 
 namespace wlsqm {

@@ -12,7 +12,7 @@
 #include <new>
 #include <vector>
 
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_interp.hpp"
 #include "hostio.hpp"
 
@@ -61,23 +61,6 @@ struct wlsqm_expert {
 };
 
 using namespace wlsqm;
-
-namespace wlsqm {
-int nearest_search(int dimension, int64_t ndata, const double* S, int64_t nquery, const double* X, int64_t x_stride,
-                   long long* out, hipStream_t s);
-long long preferred_slots(int dimension, int order, long long max_nk);
-int launch_solve_many(int dimension, int order, const KParams& p, long long K, long long nrhs,
-                      const double* fk, long long sfk_r, long long sfk_j, double* fi, long long sfi_r, long long sfi_j,
-                      hipStream_t stream, bool* handled);
-int solve_op_build(int dimension, int order, const KParams& geom, long long K, const long long* h_knowns, long long ncases,
-                   DevBuf& d_op, DevBuf& d_T, int* any_known, hipStream_t s, bool* ok);
-int launch_solve_op(int dimension, int order, const KParams& geom, long long K, const double* op, const double* T, int any_known,
-                    long long nrhs, const double* fk, long long sfk_r, long long sfk_j, double* fi, long long sfi_r, long long sfi_j,
-                    hipStream_t stream, bool* handled);
-long long cond_workspace_doubles(int no);
-int launch_conds(int dimension, int order, const KParams& p, const int* order_arr, double* ws, long long CH,
-                 long long case0, double* out, hipStream_t stream);
-}
 
 static KParams expert_params(const wlsqm_expert* h, const double* d_fk, int64_t sfk_j, double* d_fi, int64_t sfi_j) {
     KParams p{};
@@ -313,10 +296,8 @@ int wlsqm_hip_expert_solve_device(wlsqm_expert* h, void* stream, const double* f
 // no <= 6 and K <= 32 only), "op" (solve_op.hip: stored solution operator, batched GEMM on the matrix cores) or unset = the
 // default rule below.
 static int solve_many_choice() {
-    const char* e = getenv("WLSQM_HIP_SOLVE_MANY");
-    if (e && e[0] == 'f') return 1;
-    if (e && e[0] == 'o') return 2;
-    return 0;
+    const char c = env_first("WLSQM_HIP_SOLVE_MANY");
+    return c == 'f' ? 1 : c == 'o' ? 2 : 0;
 }
 
 static int ensure_operator(wlsqm_expert* h, hipStream_t s) {

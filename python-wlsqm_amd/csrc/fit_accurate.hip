@@ -63,7 +63,7 @@
 #include <atomic>
 #include <type_traits>
 
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_strict.hpp"
 
@@ -767,11 +767,10 @@ static int launch_accurate(const KParams& p, hipStream_t stream) {
     if (groups <= 0) return WLSQM_OK;
     if (groups > 0x3fffffffLL) { set_error("too many cases for one launch"); return WLSQM_EVALUE; }
     const long long K = p.max_nk;
-    const bool dense = !p.hoods && !p.case_index && p.xk && p.fk && K >= 2 && K % 2 == 0 && p.sxk_k == DIM && p.sxk_j == K * DIM &&
-                       p.sfk_k == 1 && p.sfk_j == K && ((reinterpret_cast<uintptr_t>(p.xk) | reinterpret_cast<uintptr_t>(p.fk)) & 15u) == 0 &&
-                       !getenv("WLSQM_HIP_ACCURATE_NO_STAGE");
-    const char* nospec = getenv("WLSQM_HIP_ACCURATE_NO_SPEC");        // A/B and tests: the two-pass form for every group
-    if (dense && K % acc::CH == 0 && !(nospec && nospec[0] == '1')) {
+    const bool dense = !p.hoods && !p.case_index && p.xk && p.fk && K >= 2 && K % 2 == 0 && dense_rows(DIM, p, K) &&
+                       !env_present("WLSQM_HIP_ACCURATE_NO_STAGE");
+    const bool nospec = env_first("WLSQM_HIP_ACCURATE_NO_SPEC") == '1';      // A/B and tests: the two-pass form for every group
+    if (dense && K % acc::CH == 0 && !nospec) {
         // one status byte per group, written by the speculative kernel for EVERY group: no clearing, no counters, no state between calls
         // (round 5's work lists with their alternating counter sets are gone)
         CallScratch cs;

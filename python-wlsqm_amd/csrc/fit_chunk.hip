@@ -6,7 +6,7 @@
 // Same arithmetic as the tile kernels (wlsqm_tile.hpp): one wave per tile, four lanes per case (lane = h * 16 + c), every lane
 // takes 8 of a chunk's 32 slots, moments (wlsqm_moments.hpp), xor butterfly, lane h == 0 expands, eliminates knowns
 // (impl.pyx:792-823), factors and substitutes.  Dense contiguous rows with an even K (api.hip repacks anything else).
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_moments.hpp"
 
@@ -318,15 +318,13 @@ static int launch_chunk(const KParams& p, long long K, hipStream_t stream) {
 
 static bool chunk_layout_ok(int dimension, const KParams& p, long long K) {
     if (p.hoods || p.case_index || K < 2 || (K % 2) != 0 || K > 0x3fffffff) return false;
-    if (p.sxk_k != dimension || p.sxk_j != K * dimension || p.sfk_k != 1 || p.sfk_j != K) return false;
-    return ((reinterpret_cast<uintptr_t>(p.xk) | reinterpret_cast<uintptr_t>(p.fk)) & 15u) == 0;
+    return dense_rows(dimension, p, K);
 }
 
 // Dense contiguous basic fits of any K (even, 16-byte aligned rows) with at most 15 unknowns.
 int launch_fit_chunk(int dimension, int order, const KParams& p, long long K, hipStream_t stream, bool* handled) {
     *handled = false;
-    const char* off = getenv("WLSQM_HIP_DISABLE_TILE");
-    if (off && off[0] == '1') return WLSQM_OK;
+    if (!tiles_enabled()) return WLSQM_OK;
     if (p.do_sens || p.iterative || !chunk_layout_ok(dimension, p, K)) return WLSQM_OK;
 #define CCASE(D, O) if (dimension == D && order == O) { *handled = true; return launch_chunk<D, O>(p, K, stream); }
     CCASE(1, 0) CCASE(1, 1) CCASE(1, 2) CCASE(1, 3) CCASE(1, 4)
@@ -340,10 +338,8 @@ int launch_fit_chunk(int dimension, int order, const KParams& p, long long K, hi
 // shapes no tile kernel with extras takes (2D orders 3-4: K > 64 / every K), before the lane-per-case kernel.
 int launch_fit_chunk_refine(int dimension, int order, const KParams& p, long long K, hipStream_t stream, bool* handled) {
     *handled = false;
-    const char* off = getenv("WLSQM_HIP_DISABLE_TILE");
-    if (off && off[0] == '1') return WLSQM_OK;
-    const char* no_ = getenv("WLSQM_HIP_DISABLE_CHUNK_REFINE");                 // A/B against the lane kernel
-    if (no_ && no_[0] == '1') return WLSQM_OK;
+    if (!tiles_enabled()) return WLSQM_OK;
+    if (env_first("WLSQM_HIP_DISABLE_CHUNK_REFINE") == '1') return WLSQM_OK;    // A/B against the lane kernel
     if (!p.iterative || p.do_sens || !chunk_layout_ok(dimension, p, K)) return WLSQM_OK;
 #define CCASE(D, O) if (dimension == D && order == O) { *handled = true; return launch_chunk<D, O, false, true>(p, K, stream); }
     CCASE(1, 0) CCASE(1, 1) CCASE(1, 2) CCASE(1, 3) CCASE(1, 4)

@@ -10,7 +10,7 @@
 // This generic variant reads the case's rows straight from global memory with arbitrary
 // strides (the reference's memoryview contract); the contiguous fast path lives in
 // fit_tile.hip.
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 
 namespace wlsqm {

@@ -13,14 +13,11 @@
 // the launch boundaries and kernel tails cost more than the HBM round trip.)
 #include <cstdlib>
 
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_moments.hpp"
 
 namespace wlsqm {
-
-bool tile_moments_supported(int dimension, int order, const KParams& p, long long max_nk);
-int launch_tile_moments(int dimension, int order, const KParams& p, long long max_nk, hipStream_t stream, bool* handled);
 
 // Kernel B: expand the normal equations from the moments, eliminate knowns, LDL^T, substitution.  The 120 + 15 entries of
 // an order-4 case take 256 VGPRs + 78 AGPRs: one wave per SIMD.  Capping the kernel at 256 registers for two waves per
@@ -165,9 +162,9 @@ __global__ __launch_bounds__(64) void moment_solve_kernel(const KParams p, doubl
 
 // cases per chunk
 static long long chunk_cases() {
-    const char* e = getenv("WLSQM_HIP_MOMENT_CHUNK");             // tuning override
-    if (e) { const long long v = atoll(e); if (v > 0) return v; }
-    return 4ll << 20;
+    long long v = 0;
+    env_int("WLSQM_HIP_MOMENT_CHUNK", &v);                        // tuning override
+    return v > 0 ? v : 4ll << 20;
 }
 
 template <int DIM, int ORDER>
@@ -229,8 +226,7 @@ int launch_fit_moment_inverse(int dimension, int order, const KParams& p0, long 
 
 int launch_fit_moment(int dimension, int order, const KParams& p, long long max_nk, hipStream_t stream, bool* handled) {
     *handled = false;
-    const char* off = getenv("WLSQM_HIP_DISABLE_TILE");
-    if (off && off[0] == '1') return WLSQM_OK;
+    if (!tiles_enabled()) return WLSQM_OK;
     if (p.do_sens || p.iterative || p.case_index) return WLSQM_OK;
     if (!tile_moments_supported(dimension, order, p, max_nk)) return WLSQM_OK;
     if (dimension == 2 && order == 4) return launch_moment<2, 4>(p, max_nk, stream, handled);

@@ -20,7 +20,7 @@
 // Same operations for every lane, no divergence, no LDS traffic after the moments have been picked up.
 #include <type_traits>
 
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_moments.hpp"
 

@@ -4,18 +4,13 @@
 
 namespace wlsqm {
 
-// Dense contiguous 2D order-4 batches (the tile path's eligibility: fit_tile.hip tile_eligible).
-bool tile_dense_eligible(int dimension, const KParams& p, long long max_nk);
-
 int launch_fit_ring(int dimension, int order, const KParams& p, long long max_nk, hipStream_t stream, bool* handled) {
     *handled = false;
-    const char* off = getenv("WLSQM_HIP_DISABLE_TILE");
-    if (off && off[0] == '1') return WLSQM_OK;
-    const char* noring = getenv("WLSQM_HIP_DISABLE_RING");       // A/B against the two-kernel moment path
-    if (noring && noring[0] == '1') return WLSQM_OK;
+    if (!tiles_enabled()) return WLSQM_OK;
+    if (env_first("WLSQM_HIP_DISABLE_RING") == '1') return WLSQM_OK;      // A/B against the two-kernel moment path
     if (p.hoods || p.do_sens || p.iterative || p.case_index) return WLSQM_OK;
-    const char* v = getenv("WLSQM_TILE_VARIANT");                // tools/tune.py: A/B of the ring shapes against the tile kernels
-    const int var = v ? atoi(v) : 0;
+    long long var = 0;
+    env_int("WLSQM_TILE_VARIANT", &var);                         // tools/tune.py: A/B of the ring shapes against the tile kernels
     // 3D order 2 with 40 neighbour slots (BASELINE configs[4]): the ring shape is 5 % ahead of the one-wave tile kernel (interleaved
     // A/B at 1M cases: 0.341 against 0.359 ms; unroll 5 instead of 10: 0.350; compiled for two waves per SIMD it spills 524 B per
     // lane: 1.01 ms).  WLSQM_TILE_VARIANT = 1 keeps the tile kernel (tools/tune.py).

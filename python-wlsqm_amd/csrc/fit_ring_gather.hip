@@ -6,17 +6,13 @@
 
 namespace wlsqm {
 
-bool tile_moments_supported(int dimension, int order, const KParams& p, long long max_nk);   // fit_tile.hip: layout + alignment of the index-based tables
-
 int launch_fit_ring_gather(int dimension, int order, const KParams& p, long long max_nk, hipStream_t stream, bool* handled) {
     *handled = false;
     if (!p.hoods || dimension != 2 || order != 4) return WLSQM_OK;
-    const char* off = getenv("WLSQM_HIP_DISABLE_TILE");
-    if (off && off[0] == '1') return WLSQM_OK;
-    const char* noring = getenv("WLSQM_HIP_DISABLE_RING");       // A/B against the two-kernel moment path
-    if (noring && noring[0] == '1') return WLSQM_OK;
+    if (!tiles_enabled()) return WLSQM_OK;
+    if (env_first("WLSQM_HIP_DISABLE_RING") == '1') return WLSQM_OK;      // A/B against the two-kernel moment path
     if (p.do_sens || p.iterative || p.case_index) return WLSQM_OK;
-    if (!tile_moments_supported(dimension, order, p, max_nk)) return WLSQM_OK;
+    if (!tile_moments_supported(dimension, order, p, max_nk)) return WLSQM_OK;       // (layout + alignment of the index-based tables)
     if (reinterpret_cast<uintptr_t>(p.F) & 7u) return WLSQM_OK;
     // up to 64 slots: one DMA instruction per row, and ring + index buffer stay under 40 KB (four workgroups per CU)
 #define RING_CASE(KK) if (max_nk == KK) { *handled = true; return launch_ring_impl<2, 4, KK, 16, 1, true>(p, stream); }

@@ -22,7 +22,7 @@
 // per wave 15 % slower than the mailbox.  Sensitivities / refinement stay in fit_wave.hip: grafting its extras onto this kernel's
 // front end was measured (order 4 do_sens 8.6 vs 7.3 ms per 100k cases): their 64 LDS substitutions per case dominate and
 // the extra LDS state costs occupancy.
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_moments.hpp"
 
@@ -339,15 +339,13 @@ int launch_fit_rows_inverse(int dimension, int order, const KParams& p_in, doubl
 }
 
 // Basic fit (no sensitivities, no refinement) of the 3D order-3/4 systems on dense (possibly strided) or index-based input.
-int launch_fit_rows(int dimension, int order, const KParams& p, hipStream_t stream, bool* handled) {
+int launch_fit_rows(int dimension, int order, const KParams& p, long long /*K: any*/, hipStream_t stream, bool* handled) {
     *handled = false;
-    const char* off = getenv("WLSQM_HIP_DISABLE_ROWS");          // A/B against fit_wave.hip
-    if (off && off[0] == '1') return WLSQM_OK;
+    if (env_first("WLSQM_HIP_DISABLE_ROWS") == '1') return WLSQM_OK;      // A/B against fit_wave.hip
     if (p.do_sens || p.iterative) return WLSQM_OK;
     if (dimension == 3 && order == 3) {
         *handled = true;
-        const char* one = getenv("WLSQM_ROWS_ONE_CASE");         // A/B: one case per wave for order 3 too
-        if (one && one[0] == '1') return launch_rows<3, 3, 1, 64>(p, stream);
+        if (env_first("WLSQM_ROWS_ONE_CASE") == '1') return launch_rows<3, 3, 1, 64>(p, stream);      // A/B: one case per wave for order 3 too
         return launch_rows<3, 3, 3, 21>(p, stream);
     }
     if (dimension == 3 && order == 4) { *handled = true; return launch_rows<3, 4, 1, 64>(p, stream); }

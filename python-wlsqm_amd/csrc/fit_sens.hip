@@ -24,7 +24,7 @@
 // The batch is cut into slices so that the scratch for the inverses stays bounded (200k cases, slices of 32 / 96 / 256 / 1024 MB:
 // C3-like 1.27 / 1.07 / 1.05 / 1.04 ms, 3D order 4 at K = 100 22.3 / 20.3 / 19.2 / 18.7 ms with the first versions of the kernels
 // — no Infinity Cache effect to be had).
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 
 #ifndef WLSQM_SENS_NT
@@ -32,14 +32,6 @@
 #endif
 
 namespace wlsqm {
-
-bool chunk_inverse_ok(int dimension, int order, const KParams& p, long long K);
-int launch_fit_chunk_inverse(int dimension, int order, const KParams& p, long long K, hipStream_t stream);
-int launch_fit_wave_inverse(int dimension, int order, const KParams& p, double* inv, hipStream_t stream);
-int launch_fit_rows_inverse(int dimension, int order, const KParams& p, double* inv, hipStream_t stream);
-bool moment_inverse_ok(int dimension, int order, const KParams& p, long long max_nk);
-int launch_fit_moment_inverse(int dimension, int order, const KParams& p, long long max_nk, double* inv, hipStream_t stream);
-int launch_fit_stage_inverse(int dimension, int order, const KParams& p, long long K, double* inv, hipStream_t stream, bool* handled);      // fit_stage.hip
 
 typedef double sd4_ __attribute__((ext_vector_type(4)));
 
@@ -373,8 +365,7 @@ static int launch_apply(const KParams& p, const double* inv, bool grouped, hipSt
     long long grid = 0;
     int rc = persistent_grid(reinterpret_cast<const void*>(kern), 64, 0, 0, true, setup, &grid);
     if (rc != WLSQM_OK) return rc;
-    const char* e = getenv("WLSQM_HIP_SENS_GRID_MULT");
-    const double mult = (e && atof(e) > 0.0) ? atof(e) : 2.0;
+    const double mult = env_positive("WLSQM_HIP_SENS_GRID_MULT", 2.0);
     grid = (long long)((double)grid / grid_multiple() * mult);
     if (grid < 1) grid = 1;
     if (grid > p.ncases) grid = p.ncases;
@@ -398,9 +389,7 @@ static int apply_dispatch(int dimension, int order, const KParams& p, const doub
 // WLSQM_HIP_SENS_SLICE_MB sets the size of a slice's inverses (default 1024).
 int launch_fit_sens(int dimension, int order, const KParams& p, long long K, hipStream_t stream, bool* handled) {
     *handled = false;
-    const char* off = getenv("WLSQM_HIP_DISABLE_SENS_APPLY");
-    const char* off2 = getenv("WLSQM_HIP_DISABLE_TILE");
-    if ((off && off[0] == '1') || (off2 && off2[0] == '1')) return WLSQM_OK;
+    if (env_first("WLSQM_HIP_DISABLE_SENS_APPLY") == '1' || !tiles_enabled()) return WLSQM_OK;
     const bool want_sens = p.do_sens && p.sens;
     if ((!want_sens && !p.iterative) || p.hoods || p.case_index || !p.xk || !p.fk || K < 1) return WLSQM_OK;
     const int no = wlsqm_hip_number_of_dofs(dimension, order);
@@ -411,17 +400,15 @@ int launch_fit_sens(int dimension, int order, const KParams& p, long long K, hip
     // K = 80: 1.64 -> 1.70 (those stay on the generic kernel); 2D order 2 at K = 160: 5.12 -> 1.32, 3D order 2 at K = 160: 3.68 -> 2.03,
     // 1D order 2 at K = 100: 2.94 -> 0.81, 3D order 3 at K = 60: 6.64 -> 3.74, 3D order 4 at K = 100: 24.6 -> 10.9.
     if (p.iterative && !(big || K > 128 || no <= 6)) return WLSQM_OK;
-    const char* nomom = getenv("WLSQM_HIP_SENS_NO_MOMENT");               // A/B: the chunked kernel for 2D order 4 too
-    const bool mom = !big && !(nomom && nomom[0] == '1') && moment_inverse_ok(dimension, order, p, K);
+    const bool nomom = env_first("WLSQM_HIP_SENS_NO_MOMENT") == '1';      // A/B: the chunked kernel for 2D order 4 too
+    const bool mom = !big && !nomom && moment_inverse_ok(dimension, order, p, K);
     if (big ? !(dimension == 3 && (order == 3 || order == 4)) : (!mom && !chunk_inverse_ok(dimension, order, p, K))) return WLSQM_OK;
     if (p.ncases > 0x7fffffffLL) return WLSQM_OK;
     *handled = true;
-    const char* wf = getenv("WLSQM_HIP_SENS_WAVE");                       // A/B: the LDS form of fit_wave.hip for the 3D order-3/4 inverses
-    const bool wave_form = wf && wf[0] == '1';
-    const char* mb = getenv("WLSQM_HIP_SENS_SLICE_MB");
+    const bool wave_form = env_first("WLSQM_HIP_SENS_WAVE") == '1';       // A/B: the LDS form of fit_wave.hip for the 3D order-3/4 inverses
     // (round 5: 1 GB instead of 256 MB — 400k configs[2] cases in one slice instead of three: 1.335 -> 1.264 ms; the launches and the
     // workspace of every slice cost more than the Infinity Cache residency of a small slice's inverses gains)
-    const double slice_mb = (mb && atof(mb) > 0.0) ? atof(mb) : 1024.0;
+    const double slice_mb = env_positive("WLSQM_HIP_SENS_SLICE_MB", 1024.0);
     long long per = (long long)(slice_mb * 1048576.0 / (8.0 * no * no));
     per = per < 1024 ? 1024 : per;
     per = (per / 64) * 64;                                                 // whole tiles and whole groups of 64 cases

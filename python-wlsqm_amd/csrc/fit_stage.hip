@@ -34,7 +34,7 @@
 #include <atomic>
 #include <type_traits>
 
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_moments.hpp"
 
@@ -818,8 +818,7 @@ static int launch_stage(const KParams& p, hipStream_t stream) {
     // p.ragged = 0 (device-resident counts nobody has looked at): the plain kernel marks the waves none of whose cases reaches the row's last
     // chunk and the RAGGED copy runs those behind it — an idle launch for a batch of full rows; p.ragged = 1 (full rows, known): as before.
     constexpr bool RAG_SHAPE = !GATHER && NO <= 20 && !(DIM == 3 && ORDER == 4);
-    const char* rg = getenv("WLSQM_HIP_STAGE_RAGGED");                // 0: off (A/B)
-    const bool rag_on = RAG_SHAPE && !(rg && rg[0] == '0') && p.max_nk > stage::CH;
+    const bool rag_on = RAG_SHAPE && env_first("WLSQM_HIP_STAGE_RAGGED") != '0' && p.max_nk > stage::CH;      // 0: off (A/B)
     if constexpr (RAG_SHAPE) {
         if (rag_on && p.ragged == 2) {
             hipLaunchKernelGGL((fit_stage_kernel<DIM, ORDER, 0, false, 2>), dim3((unsigned)groups), dim3(64), 0, stream, p, (unsigned char*)nullptr);
@@ -858,8 +857,8 @@ static int launch_stage(const KParams& p, hipStream_t stream) {
         // (wlsqm_hip_set_order_hint; default: sorted, what every k-nearest-neighbour search returns) — not of what earlier launches on the
         // stream reported (round 5: host-mapped bytes written by sampled groups; the same call could be timed at 0.20 or 0.22 ms depending on
         // its predecessor).  WLSQM_HIP_STAGE_FORM=two / one forces a form (A/B, tests).
-        const char* e = getenv("WLSQM_HIP_STAGE_FORM");
-        const bool own_simd = (e && (e[0] == 't' || e[0] == 'o')) ? e[0] == 'o' : p.rows_sorted == 0;
+        const char form = env_first("WLSQM_HIP_STAGE_FORM");
+        const bool own_simd = (form == 't' || form == 'o') ? form == 'o' : p.rows_sorted == 0;
         if (mark) {
             if (own_simd) hipLaunchKernelGGL((fit_stage_kernel<DIM, ORDER, 5, false, 1>), dim3((unsigned)groups), dim3(64), 0, stream, p, status);
             else hipLaunchKernelGGL((fit_stage_kernel<DIM, ORDER, 0, false, 1>), dim3((unsigned)groups), dim3(64), 0, stream, p, status);
@@ -879,18 +878,14 @@ static int launch_stage(const KParams& p, hipStream_t stream) {
     return finish(GATHER ? "stage-gather" : "stage");
 }
 
-int launch_quad_solve(const KParams& p, hipStream_t stream);          // fit_quad.hip
-
 // The basic fit of a dense contiguous 2D order-4 batch that ALSO leaves every case's inverse normal matrix at inv[group][column][case][row]
 // (first kernel of the sensitivities' path, fit_sens.hip; round 5: instead of the four-lanes-per-case tile kernel + moment_solve_kernel pair).
 // *handled = false: the input is not the staged kernel's (strides, alignment, odd K): the caller keeps the pair.
 int launch_fit_stage_inverse(int dimension, int order, const KParams& p, long long K, double* inv, hipStream_t stream, bool* handled) {
     *handled = false;
-    const char* e = getenv("WLSQM_HIP_STAGE_INVERSE");
-    if ((e && e[0] == '0') || dimension != 2 || order != 4) return WLSQM_OK;
+    if (env_first("WLSQM_HIP_STAGE_INVERSE") == '0' || dimension != 2 || order != 4) return WLSQM_OK;
     if (p.hoods || p.case_index || !p.xk || !p.fk || K < 8 || K % 2 != 0 || K > 65536) return WLSQM_OK;
-    if (p.sxk_k != dimension || p.sxk_j != K * dimension || p.sfk_k != 1 || p.sfk_j != K) return WLSQM_OK;
-    if ((reinterpret_cast<uintptr_t>(p.xk) | reinterpret_cast<uintptr_t>(p.fk)) & 15u) return WLSQM_OK;
+    if (!dense_rows(dimension, p, K)) return WLSQM_OK;
     const long long groups = (p.ncases + 63) / 64;
     if (groups <= 0 || groups > 0x7fffffffLL) return WLSQM_OK;
     KParams q = p;
@@ -906,10 +901,8 @@ int launch_fit_stage_inverse(int dimension, int order, const KParams& p, long lo
 template <bool GATHER = false>
 static int launch_stage34(const KParams& p, hipStream_t stream) {
     long long SLICE = 1LL << 20;
-    if (const char* e = getenv("WLSQM_HIP_QUAD_SLICE")) {             // (tests: small slices; whole 64-case groups)
-        const long long v = atoll(e);
-        if (v >= 64) SLICE = v / 64 * 64;
-    }
+    long long v = 0;
+    if (env_int("WLSQM_HIP_QUAD_SLICE", &v) && v >= 64) SLICE = v / 64 * 64;      // (tests: small slices; whole 64-case groups)
     for (long long j0 = 0; j0 < p.ncases; j0 += SLICE) {
         KParams q = slice_cases(p, j0, p.ncases - j0 < SLICE ? p.ncases - j0 : SLICE);
         const long long groups = (q.ncases + 63) / 64;
@@ -939,10 +932,8 @@ static int launch_stage34(const KParams& p, hipStream_t stream) {
 // everything else keeps its kernels.  WLSQM_HIP_STAGE=0 disables it, =all sends every covered shape here (A/B).
 int launch_fit_stage(int dimension, int order, const KParams& p, long long K, hipStream_t stream, bool* handled) {
     *handled = false;
-    const char* e = getenv("WLSQM_HIP_STAGE");
-    if (e && e[0] == '0') return WLSQM_OK;
-    const char* off = getenv("WLSQM_HIP_DISABLE_TILE");
-    if (off && off[0] == '1') return WLSQM_OK;
+    const char sw = env_first("WLSQM_HIP_STAGE");
+    if (sw == '0' || !tiles_enabled()) return WLSQM_OK;
     if (p.do_sens || p.iterative || p.case_index) return WLSQM_OK;
     if (p.hoods) {
         // index-based input: the gathering form (WLSQM_HIP_STAGE_GATHER=0 disables it, =all sends every covered shape here: A/B).
@@ -950,9 +941,9 @@ int launch_fit_stage(int dimension, int order, const KParams& p, long long K, hi
         // ring / wave-per-case kernels: 2D order 4 at 64 neighbours 0.42 / 0.44 against 0.57 / 0.69 ms, 3D order 2 at 40 0.28 / 0.40
         // against 0.37 / 0.41, 2D order 2 at 24 0.094 / 0.124 against 0.124 / 0.132, 2D order 3 at 30 0.21 / 0.21 against 0.24 / 0.26,
         // 3D order 3 at 40 (400k) 0.30 against 1.62, 3D order 4 1.18 against 4.13 (profiles/r04y_stage_gather.txt)
-        const char* g = getenv("WLSQM_HIP_STAGE_GATHER");
-        if ((g && g[0] == '0') || !p.S || !p.F || K < 8 || K > 65536) return WLSQM_OK;
-        const bool gall = g && g[0] == 'a';
+        const char g = env_first("WLSQM_HIP_STAGE_GATHER");
+        if (g == '0' || !p.S || !p.F || K < 8 || K > 65536) return WLSQM_OK;
+        const bool gall = g == 'a';
 #define GCASE(D, O, COND) if (dimension == D && order == O && (gall || (COND))) { *handled = true; return launch_stage<D, O, true>(p, stream); }
         GCASE(3, 3, true)
         if (dimension == 3 && order == 4) { *handled = true; return launch_stage34<true>(p, stream); }
@@ -968,9 +959,8 @@ int launch_fit_stage(int dimension, int order, const KParams& p, long long K, hi
     }
     if (!p.xk || !p.fk) return WLSQM_OK;
     if (K < 8 || K % 2 != 0 || K > 65536) return WLSQM_OK;          // (row bytes and the tile's offsets are 32-bit)
-    if (p.sxk_k != dimension || p.sxk_j != K * dimension || p.sfk_k != 1 || p.sfk_j != K) return WLSQM_OK;
-    if ((reinterpret_cast<uintptr_t>(p.xk) | reinterpret_cast<uintptr_t>(p.fk)) & 15u) return WLSQM_OK;
-    const bool all = e && e[0] == 'a';
+    if (!dense_rows(dimension, p, K)) return WLSQM_OK;
+    const bool all = sw == 'a';
 #define SCASE(D, O, COND) if (dimension == D && order == O && (all || (COND))) { *handled = true; return launch_stage<D, O>(p, stream); }
     // (tools/sweep_stage.py, profiles/r04l_sweep_stage.txt: 400k cases, against the fixed-K tile / ring / moment kernels, neighbour
     // counts 8 .. 128: 2D order 4 1.05-2.3x, 3D order 2 1.05-1.9x, 2D order 3 0.98-1.56x, 2D order 2 0.94-0.99x up to 24 neighbours

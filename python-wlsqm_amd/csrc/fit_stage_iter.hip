@@ -35,7 +35,7 @@
 #include <atomic>
 #include <type_traits>
 
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_moments.hpp"
 
@@ -581,8 +581,9 @@ static int launch_stage_refine(const KParams& p, long long K, hipStream_t stream
     const int Q = (int)((K + CH - 1) / CH);
     const int XP2 = pitch2(Q * CH * DIM), FP2 = pitch2(Q * CH);
     const size_t bytes = (size_t)64 * (XP2 + FP2) * 16;
-    size_t bound = 53 * 1024;
-    if (const char* e = getenv("WLSQM_HIP_REFINE_RESIDENT_KB")) bound = (size_t)atol(e) * 1024;
+    long long bound_kb = 53;
+    const bool bound_set = env_int("WLSQM_HIP_REFINE_RESIDENT_KB", &bound_kb);
+    size_t bound = (size_t)bound_kb * 1024;
     if (bound > 160 * 1024) bound = 160 * 1024;
     // (from three sweeps on: below that the re-staging form's four to five waves per CU win — 2D order 4 at 26 neighbours, max_iter 0 / 1 /
     // 2 / 4 / 10: 0.132 / 0.216 / 0.297 / 0.433 / 0.813 against 0.158 / 0.218 / 0.276 / 0.394 / 0.738 ms resident, 3D order 2 at 20: 0.088 /
@@ -592,7 +593,7 @@ static int launch_stage_refine(const KParams& p, long long K, hipStream_t stream
     // 0.554 / 0.523 against 0.377 / 0.638 / 0.558 ms resident; 2D order 4 and 3D order 2 the other way round: 26 neighbours 0.81 against
     // 0.73, 20 neighbours 0.51 against 0.46)
     // (rows of at most 40 KB leave four waves per CU as well: resident always — 2D order 3 at 16 neighbours 0.234 against 0.258 ms)
-    const bool few = !getenv("WLSQM_HIP_REFINE_RESIDENT_KB") && bytes > 40 * 1024 && (p.max_iter < 3 || (DIM == 2 && ORDER == 3));
+    const bool few = !bound_set && bytes > 40 * 1024 && (p.max_iter < 3 || (DIM == 2 && ORDER == 3));
     if (!few && bytes <= bound && bytes >= (size_t)64 * ndofs(DIM, ORDER) * 8) {
         auto kern = fit_stage_refine_kernel<DIM, ORDER, true, false>;
         static std::atomic<unsigned> optin{0};                        // per device, once: more than 64 KB of dynamic LDS
@@ -609,19 +610,20 @@ static int launch_stage_refine(const KParams& p, long long K, hipStream_t stream
     }
     {
         // the weights beside the staging rows while four waves per CU still fit (WLSQM_HIP_REFINE_WCACHE=0: never)
-        const char* e = getenv("WLSQM_HIP_REFINE_WCACHE");
+        const char wc = env_first("WLSQM_HIP_REFINE_WCACHE");
         const int WP = (Q * CH) | 1;
         // (static LDS of the kernel: the padded staging rows, or the DMA form's two slots of a KiB per load instruction — 24 KB for the
         // 15-unknown systems, whose weight cache therefore ends at 30 neighbours instead of 48)
         constexpr bool dma15 = (WLSQM_SITER_DMA != 0) && ndofs(DIM, ORDER) == 15;
         constexpr int xni = 64 / (64 / (CH * DIM * 8 / 16)) + ((64 % (64 / (CH * DIM * 8 / 16))) ? 1 : 0), fni = 64 / (64 / (CH * 8 / 16));
         const size_t wbytes = (size_t)64 * WP * 8, stat = dma15 ? (size_t)2 * (xni + fni) * (1024 + 16 * WLSQM_SITER_DMA_SKEW) : (size_t)64 * (pitch2(CH * DIM) + pitch2(CH)) * 16;
-        size_t budget = 40 * 1024;                                   // four waves per CU (WLSQM_HIP_REFINE_CACHE_KB: A/B)
-        if (const char* b = getenv("WLSQM_HIP_REFINE_CACHE_KB")) budget = (size_t)atol(b) * 1024;
-        if (!(e && e[0] == '0') && p.max_iter >= 1 && ndofs(DIM, ORDER) > 6 && wbytes + stat <= budget && wbytes + stat <= 64 * 1024) {        // (no opt-in to more than 64 KB of LDS for this kernel)
+        long long budget_kb = 40;                                    // four waves per CU (WLSQM_HIP_REFINE_CACHE_KB: A/B)
+        env_int("WLSQM_HIP_REFINE_CACHE_KB", &budget_kb);
+        const size_t budget = (size_t)budget_kb * 1024;
+        if (wc != '0' && p.max_iter >= 1 && ndofs(DIM, ORDER) > 6 && wbytes + stat <= budget && wbytes + stat <= 64 * 1024) {        // (no opt-in to more than 64 KB of LDS for this kernel)
             // 3D: the values (the sweeps are bound by the re-staged bytes); 2D: the weights (by their instructions); =w / =f force one
             constexpr int DEF = DIM == 3 ? 2 : 1;
-            const int which = (e && e[0] == 'w') ? 1 : (e && e[0] == 'f') ? 2 : DEF;
+            const int which = wc == 'w' ? 1 : wc == 'f' ? 2 : DEF;
             if (which == 2) hipLaunchKernelGGL((fit_stage_refine_kernel<DIM, ORDER, false, false, 2>), dim3((unsigned)groups), dim3(64), wbytes, stream, p, 0, WP);
             else
             hipLaunchKernelGGL((fit_stage_refine_kernel<DIM, ORDER, false, false, 1>), dim3((unsigned)groups), dim3(64), wbytes, stream, p, 0, WP);
@@ -658,19 +660,17 @@ static int launch_stage_refine(const KParams& p, long long K, hipStream_t stream
 // cache 2D order 3 wins at every neighbour and sweep count, profiles/r04zb_time_refine_23.txt).
 int launch_fit_stage_refine(int dimension, int order, const KParams& p, long long K, hipStream_t stream, bool* handled) {
     *handled = false;
-    const char* off = getenv("WLSQM_HIP_DISABLE_TILE");
-    if (off && off[0] == '1') return WLSQM_OK;
+    if (!tiles_enabled()) return WLSQM_OK;
     if (!(p.iterative || p.do_sens) || p.case_index || p.hoods || p.it_stop != 0) return WLSQM_OK;
-    { const char* r = getenv("WLSQM_HIP_REFINE_ROUNDS"); if (r && r[0] == '1') return WLSQM_OK; }      // (the rounds experiment of fit_tilek.hip keeps its shapes)
+    if (env_first("WLSQM_HIP_REFINE_ROUNDS") == '1') return WLSQM_OK;      // (the rounds experiment of fit_tilek.hip keeps its shapes)
     if (p.do_sens && !p.sens) return WLSQM_OK;
-    const char* e = getenv(p.do_sens ? "WLSQM_HIP_STAGE_SENS" : "WLSQM_HIP_STAGE_REFINE");
-    if (e && e[0] == '0') return WLSQM_OK;
-    const bool all = e && e[0] == 'a';
+    const char sw = env_first(p.do_sens ? "WLSQM_HIP_STAGE_SENS" : "WLSQM_HIP_STAGE_REFINE");
+    if (sw == '0') return WLSQM_OK;
+    const bool all = sw == 'a';
     if (p.do_sens && !all) return WLSQM_OK;                           // (measured slower than the kernels these calls have: see above)
     if (!p.xk || !p.fk || !p.xi) return WLSQM_OK;
     if (K < 8 || K % 2 != 0 || K > 65536) return WLSQM_OK;          // (row bytes and the tile's offsets are 32-bit)
-    if (p.sxk_k != dimension || p.sxk_j != K * dimension || p.sfk_k != 1 || p.sfk_j != K) return WLSQM_OK;
-    if ((reinterpret_cast<uintptr_t>(p.xk) | reinterpret_cast<uintptr_t>(p.fk)) & 15u) return WLSQM_OK;
+    if (!dense_rows(dimension, p, K)) return WLSQM_OK;
     if (p.do_sens && (p.ss_j * 8 * 4 > 0x7fffffffLL)) return WLSQM_OK;            // (32-bit offsets inside a store instruction's four cases)
 #define RCASE(D, O, COND) if (dimension == D && order == O && (all || (COND))) { *handled = true; return launch_stage_refine<D, O>(p, K, stream); }
     RCASE(2, 2, p.max_iter <= 2 || (K >= 48 && p.max_iter <= 5) || (K > 64 && p.max_iter <= 8))     // (64 neighbours, max_iter 4: 0.504 against 0.596 ms; 160, max_iter 4: 1.31 against 2.08, 10: 2.71 against 2.58)

@@ -27,7 +27,7 @@
 #include <atomic>
 #include <type_traits>
 
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_strict.hpp"
 
@@ -1048,11 +1048,10 @@ static int launch_strict(const KParams& p, const StrictDebug& dbg, hipStream_t s
     // (sensitivities, refinement) — unless the neighbour rows do not fit the LDS or the intermediates are captured
     {
         constexpr int LPC = NO <= 2 ? 2 : NO <= 4 ? 4 : NO <= 8 ? 8 : NO <= 16 ? 16 : NO <= 32 ? 32 : 64;
-        const char* e = getenv("WLSQM_HIP_STRICT_NO_ROWS");
         const int KP = p.max_nk > 0 ? (int)p.max_nk : 1;
         const size_t rl = (size_t)((((3 + DIM) * KP) | 1) * (64 / LPC)) * sizeof(double);
         const bool want = NO > STRICT_REG_MAX_NO || p.do_sens || p.iterative;
-        if (want && !dbg.A && !dbg.w && !dbg.LU && rl <= 160 * 1024 && !(e && e[0] == '1')) {
+        if (want && !dbg.A && !dbg.w && !dbg.LU && rl <= 160 * 1024 && env_first("WLSQM_HIP_STRICT_NO_ROWS") != '1') {
             if (rl > 64 * 1024) {
                 WLSQM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fit_strict_rows_kernel<DIM, ORDER, LPC>),
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl));
@@ -1068,8 +1067,7 @@ static int launch_strict(const KParams& p, const StrictDebug& dbg, hipStream_t s
     // basic fits of the small systems: the all-unknown 64-case groups run the register kernel, the others the LDS kernel
     bool split = false;
     if constexpr (NO <= STRICT_REG_MAX_NO) {
-        const char* e = getenv("WLSQM_HIP_STRICT_NO_REG");
-        split = !p.do_sens && !p.iterative && !dbg.A && !dbg.w && !(e && e[0] == '1');
+        split = !p.do_sens && !p.iterative && !dbg.A && !dbg.w && env_first("WLSQM_HIP_STRICT_NO_REG") != '1';
         if (split) {
             const long long groups = (p.ncases + 63) / 64;
             hipLaunchKernelGGL((fit_strict_reg_kernel<DIM, ORDER, false>), dim3((unsigned)groups), dim3(64), 0, stream, p);
@@ -1085,8 +1083,6 @@ static int launch_strict(const KParams& p, const StrictDebug& dbg, hipStream_t s
     note_kernel("strict");
     return WLSQM_OK;
 }
-
-int launch_fit_accurate(int dimension, int order, const KParams& p, hipStream_t stream, bool* handled);      // fit_accurate.hip
 
 int launch_fit_strict(int dimension, int order, const KParams& p, const StrictDebug* dbg_in, hipStream_t stream) {
     const StrictDebug dbg = dbg_in ? *dbg_in : StrictDebug{};

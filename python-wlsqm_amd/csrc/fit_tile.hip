@@ -6,11 +6,6 @@
 
 namespace wlsqm {
 
-// per-family tables (other translation units); *handled stays false when the table has no entry
-int launch_fit_tile_even(int dimension, int order, const KParams& p, long long max_nk, hipStream_t stream, bool* handled);
-int launch_fit_tile_gather(int dimension, int order, const KParams& p, long long max_nk, hipStream_t stream, bool* handled);
-int launch_fit_tile_big(int dimension, int order, const KParams& p, long long max_nk, hipStream_t stream, bool* handled);
-
 // The tile path needs: no extras, all cases in order, dense contiguous arrays, 16-byte aligned bases
 // (index-based mode: contiguous 16-byte aligned hoods rows, 16-byte aligned S).
 static bool tile_eligible(int dim, const KParams& p, long long K) {
@@ -19,9 +14,7 @@ static bool tile_eligible(int dim, const KParams& p, long long K) {
         if (p.shoods_j != K || (K % 2) != 0) return false;
         return ((reinterpret_cast<uintptr_t>(p.hoods) | reinterpret_cast<uintptr_t>(p.S)) & 15u) == 0;
     }
-    if (p.sxk_k != dim || p.sxk_j != K * dim || p.sfk_k != 1 || p.sfk_j != K) return false;
-    if ((reinterpret_cast<uintptr_t>(p.xk) | reinterpret_cast<uintptr_t>(p.fk)) & 15u) return false;
-    return true;
+    return dense_rows(dim, p, K);
 }
 
 // exported for fit_ring.hip: dense contiguous input the tile kernels can take
@@ -89,14 +82,12 @@ int launch_tile_moments(int dimension, int order, const KParams& p, long long ma
 int launch_fit_tile(int dimension, int order, const KParams& p, long long max_nk, hipStream_t stream, bool* handled) {
     *handled = false;
     // WLSQM_HIP_DISABLE_TILE=1 forces the generic kernels (A/B measurements and the tile-vs-lane parity test)
-    const char* off = getenv("WLSQM_HIP_DISABLE_TILE");
-    if (off && off[0] == '1') return WLSQM_OK;
-    const char* nofix = getenv("WLSQM_HIP_DISABLE_FIXEDK");     // A/B: send the curated shapes to the runtime-K kernels too
-    if (nofix && nofix[0] == '1' && !p.hoods) return WLSQM_OK;
+    if (!tiles_enabled()) return WLSQM_OK;
+    if (env_first("WLSQM_HIP_DISABLE_FIXEDK") == '1' && !p.hoods) return WLSQM_OK;     // A/B: send the curated shapes to the runtime-K kernels too
     if (!tile_eligible(dimension, p, max_nk)) return WLSQM_OK;
     // WLSQM_TILE_VARIANT selects a tuning variant of the BASELINE configs (tools/tune.py); default = best measured
-    const char* v = getenv("WLSQM_TILE_VARIANT");
-    const int var = v ? atoi(v) : 0;
+    long long var = 0;
+    env_int("WLSQM_TILE_VARIANT", &var);
     const bool gather = p.hoods != nullptr;
 #define TILE_CASE(D, O, KK, ...)                                                 \
     if (dimension == D && order == O && max_nk == KK) { *handled = true; return launch_tile_any<D, O, KK, __VA_ARGS__>(p, stream, gather); }
@@ -108,7 +99,7 @@ int launch_fit_tile(int dimension, int order, const KParams& p, long long max_nk
             return var == 3 ? launch_tile_impl<2, 2, 32, 4, 1, 8, 2, true>(p, stream)
                             : launch_tile_impl<2, 2, 32, 4, 1, 8, 2, true, false, true>(p, stream);
         }
-        // Since the grids launch 16 workgroups per resident slot (wlsqm_internal.hpp) one wave per 32-case tile with two
+        // Since the grids launch 16 workgroups per resident slot (wlsqm_dispatch.hpp) one wave per 32-case tile with two
         // lanes per case leads: 0.159 against 0.166 ms for four lanes per case (variant 4) at 1M cases, 0.314 against 0.348 at
         // 2M (228 VGPRs, two waves per SIMD; unroll 4 / 16: 0.159 / 0.158 against 0.157; squeezed to 168 VGPRs for three waves,
         // by unroll 2 or __launch_bounds__(64, 3): 0.169 / 0.190).  Earlier A/B at 1M cases with resident-size grids (tools/tune.py), ms per launch: one wave per 16-case tile + moments + direct fk 0.167;
@@ -134,7 +125,7 @@ int launch_fit_tile(int dimension, int order, const KParams& p, long long max_nk
             default: return launch_tile_any<3, 2, 40, 1, 4, 2, 2, true, true>(p, stream, gather);
         }
     }
-    // The per-family tables first (every even K up to 128; fit_tile_even.hip / fit_tile_gather.hip / fit_tile_big.hip), then
+    // The per-family tables first (*handled stays false when a table has no entry; every even K up to 128; fit_tile_even.hip / fit_tile_gather.hip / fit_tile_big.hip), then
     // the shapes curated one by one: best of {entry form, moment form} x {four waves per 64-case tile, two waves per 32, one wave
     // per 16 cases with direct fk}, tools/tune.py at 1M cases; anything else -> fit_tilek.hip.
     {

@@ -10,7 +10,7 @@
 #include <cstdlib>
 
 #include <cstdio>
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_moments.hpp"
 #include "wlsqm_tile1.hpp"
@@ -605,8 +605,7 @@ static int launch_tile1(const KParams& p, long long K, hipStream_t stream, bool*
         // sweep 3 and 24-38 % after sweep 6 (WLSQM_HIP_REFINE_DEBUG=1), and a later round has to rebuild the factor of its cases
         // (configs[4]: 1.0 ms of the kernel's 1.45 ms for fit + 3 sweeps).  The divergence inside a tile is therefore small on the
         // GPU; what the refinement lines cost is the sweeps themselves.
-        const char* e = getenv("WLSQM_HIP_REFINE_ROUNDS");
-        const bool rounds = p.iterative && !p.do_sens && p.it_stop == 0 && p.max_iter >= 5 && p.ncases >= 4096 && (e && e[0] == '1');
+        const bool rounds = env_first("WLSQM_HIP_REFINE_ROUNDS") == '1' && p.iterative && !p.do_sens && p.it_stop == 0 && p.max_iter >= 5 && p.ncases >= 4096;
         if (rounds) {
             const long long n = p.ncases;
             long long* ws = nullptr;                  // [8] counters, [n] list A, [n] list B, [n] residual norms
@@ -626,7 +625,7 @@ static int launch_tile1(const KParams& p, long long K, hipStream_t stream, bool*
                 hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(KW), lds_bytes, stream, q, ntiles, G);
             }
             hipError_t le = hipGetLastError();
-            if (getenv("WLSQM_HIP_REFINE_DEBUG")) {           // survivors of the first two rounds (synchronises: diagnostics only)
+            if (env_present("WLSQM_HIP_REFINE_DEBUG")) {          // survivors of the first two rounds (synchronises: diagnostics only)
                 long long c[2] = {0, 0};
                 (void)hipMemcpyAsync(c, ws, sizeof(c), hipMemcpyDeviceToHost, stream);
                 (void)hipStreamSynchronize(stream);
@@ -647,14 +646,12 @@ static int launch_tile1(const KParams& p, long long K, hipStream_t stream, bool*
 // Runtime-K tile path: dense contiguous arrays with 16-byte rows (K*dim and K even), no extras, no bucketing.
 int launch_fit_tilek(int dimension, int order, const KParams& p, long long K, hipStream_t stream, bool* handled) {
     *handled = false;
-    const char* off = getenv("WLSQM_HIP_DISABLE_TILE");
-    if (off && off[0] == '1') return WLSQM_OK;
+    if (!tiles_enabled()) return WLSQM_OK;
     if (p.hoods) {                                               // index-based input: the one-wave kernel gathers per lane
         if (K < 4 || p.shoods_j != K) return WLSQM_OK;
     } else {
         if (K < 4 || ((K * dimension) % 2) != 0) return WLSQM_OK;   // rows of xk are multiples of 16 bytes
-        if (p.sxk_k != dimension || p.sxk_j != K * dimension || p.sfk_k != 1 || p.sfk_j != K) return WLSQM_OK;
-        if ((reinterpret_cast<uintptr_t>(p.xk) | reinterpret_cast<uintptr_t>(p.fk)) & 15u) return WLSQM_OK;
+        if (!dense_rows(dimension, p, K)) return WLSQM_OK;
     }
     // Two shapes (A/B over K = 16..64, tools/tune.py w1/w4): one wave per 16-case tile wins for 2D order 2 and 3D order 1
     // (+5..+20 %) and is the only one whose LDS image fits for large K; four waves per 64-case tile wins for the
@@ -663,8 +660,7 @@ int launch_fit_tilek(int dimension, int order, const KParams& p, long long K, hi
     const bool extras = p.do_sens || p.iterative;
     if (extras) {
         // sensitivities / iterative refinement: the one-wave kernel with EXTRAS (K <= 64), else the generic kernel
-        const char* ex = getenv("WLSQM_HIP_DISABLE_TILE_EXTRAS");
-        if (ex && ex[0] == '1') return WLSQM_OK;
+        if (env_first("WLSQM_HIP_DISABLE_TILE_EXTRAS") == '1') return WLSQM_OK;
         // `lone`: instantiations whose registers are planned for ONE wave per SIMD (__launch_bounds__(64, 1): up to 512 registers,
         // no scratch) instead of two.  The 10-unknown systems (2D order 3, 3D order 2) spill 0.4-1.2 KB per lane otherwise, and so
         // do the 32-neighbours-per-lane shapes.  400k cases, lone / paired, ms: 3D order 2 do_sens at K = 12 / 24 / 40 / 64 / 124:
@@ -707,12 +703,12 @@ int launch_fit_tilek(int dimension, int order, const KParams& p, long long K, hi
 #undef XB
         return WLSQM_OK;
     }
-    const char* sv = getenv("WLSQM_TILEK_SHAPE");
+    const char sv = env_first("WLSQM_TILEK_SHAPE");
     // the four-wave shape stages fk rows in 16-byte chunks and takes whole batches only (no index list)
     const bool can1 = K <= K1_LPC * K1_FMAX, can4 = (K % 2) == 0 && !p.case_index && !p.hoods;
     bool first1 = (dimension == 2 && order == 2) || (dimension == 3 && order == 1);
-    if (sv && sv[0] == '1') first1 = true;
-    if (sv && sv[0] == '4') first1 = false;
+    if (sv == '1') first1 = true;
+    if (sv == '4') first1 = false;
     // up to 32 neighbours: two lanes per case on 32-case tiles (1M cases, 2D order 2 at K = 15 / 16 / 31 / 32: 0.133 / 0.133 / 0.223 /
     // 0.219 ms against 0.196 / 0.192 / 0.249 / 0.247 with four lanes; 3D order 2 at K = 12: 0.176 against 0.289)
 #define KCASE(D, O)                                                                            \

@@ -13,7 +13,7 @@
 //   * the triangular solves run redundantly in every lane's registers with broadcast LDS
 //     reads of the factor — which also gives 64 right-hand sides at once for the
 //     sensitivity pass (impl.pyx:831-834 loops dgetrs over the nk right-hand sides).
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 
 namespace wlsqm {

@@ -9,7 +9,7 @@
 
 #include <omp.h>
 
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 
 namespace wlsqm {
 
@@ -18,10 +18,10 @@ namespace wlsqm {
 inline int copy_threads() {
     static int n = 0;
     if (!n) {
-        const char* e = getenv("WLSQM_HIP_COPY_THREADS");
-        int want = e ? atoi(e) : 16;
-        int have = omp_get_max_threads();
-        n = want < 1 ? 1 : (want > have ? have : want);
+        long long want = 16;
+        env_int("WLSQM_HIP_COPY_THREADS", &want);
+        const int have = omp_get_max_threads();
+        n = want < 1 ? 1 : (want > have ? have : (int)want);
     }
     return n;
 }

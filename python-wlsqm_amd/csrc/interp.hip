@@ -10,7 +10,7 @@
 // (8*dim bytes in, 8 out per point, plus the gathered model row).
 #include <vector>
 
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_interp.hpp"
 

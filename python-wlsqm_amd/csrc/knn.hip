@@ -19,7 +19,7 @@
 
 #include <hipcub/hipcub.hpp>
 
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_interp.hpp"
 
 namespace wlsqm {

@@ -15,7 +15,7 @@
 #include <climits>
 #include <cstring>
 
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "hostio.hpp"
 
 namespace wlsqm {

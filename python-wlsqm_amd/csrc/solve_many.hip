@@ -17,7 +17,7 @@
 // the fused kernel in expert.hip.
 #include <algorithm>
 
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_tile1.hpp"
 

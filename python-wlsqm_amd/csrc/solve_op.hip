@@ -27,7 +27,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 
 #ifndef WLSQM_OP_NT
@@ -283,9 +283,6 @@ __global__ __launch_bounds__(64 * WPG) void solve_op_mfma_kernel(const OpParams 
 
 // ---- host side
 
-long long preferred_slots(int dimension, int order, long long max_nk);
-int launch_fit(int dimension, int order, const KParams& p, long long max_nk, hipStream_t stream);
-
 bool solve_op_shape_ok(int dimension, int order, long long K) {
     const int no = ndofs(dimension, order);
     return order >= 0 && no <= 15 && K >= 10 && K <= 64 && (K % 2) == 0;      // (the operator rows are padded to a multiple of 8)
@@ -367,9 +364,10 @@ int launch_solve_op(int dimension, int order, const KParams& geom, long long K, 
     *handled = false;
     if (!solve_op_shape_ok(dimension, order, K) || sfk_j != K) return WLSQM_OK;
     if ((reinterpret_cast<uintptr_t>(fk) & 15u) || (sfk_r % 2) != 0) return WLSQM_OK;       // 16-byte pieces of every field's rows
-    const char* dbg = getenv("WLSQM_HIP_OP_DEBUG");      // experiments: 1 = no stores, 2 = only the first block of fields is loaded
+    long long dbg = 0;
+    env_int("WLSQM_HIP_OP_DEBUG", &dbg);                 // experiments: 1 = no stores, 2 = only the first block of fields is loaded
     const int no_ = ndofs(dimension, order);
-    OpParams P{op, T, geom.nk, geom.knowns, geom.ncases, (int)K, no_, any_known, dbg ? atoi(dbg) : 0,
+    OpParams P{op, T, geom.nk, geom.knowns, geom.ncases, (int)K, no_, any_known, (int)dbg,
                (unsigned)((0x100000000ull + (unsigned)no_ - 1) / (unsigned)no_), nrhs, fk, sfk_r, sfk_j, fi, sfi_r, sfi_j};
     int dev = 0;
     WLSQM_HIP_CHECK(hipGetDevice(&dev));
@@ -380,7 +378,8 @@ int launch_solve_op(int dimension, int order, const KParams& geom, long long K, 
         cus[dev] = prop.multiProcessorCount;
     }
     const int ncu = cus[dev < 16 && dev >= 0 ? dev : 0];
-    const char* wenv = getenv("WLSQM_HIP_OP_WPG");                   // A/B: waves (= consecutive cases) per workgroup
+    long long wpg_env = 0;
+    const bool wpg_set = env_int("WLSQM_HIP_OP_WPG", &wpg_env);      // A/B: waves (= consecutive cases) per workgroup
     // (sfi_j == no is not required: the store phase addresses every row by its stride; contiguous rows make the runs contiguous)
 #define OP_LAUNCH(KQ_, KN_, WPG_)                                                                                        \
     {                                                                                                                    \
@@ -393,7 +392,7 @@ int launch_solve_op(int dimension, int order, const KParams& geom, long long K, 
     }
 #define OP_CASE(KQ_, WDEF_)                                                                                   \
     if ((K + 7) / 8 * 8 == 4 * KQ_) {                                                                        \
-        const int wpg = wenv ? atoi(wenv) : WDEF_;                                                           \
+        const int wpg = wpg_set ? (int)wpg_env : WDEF_;                                                      \
         if (any_known) { if (wpg >= 8) OP_LAUNCH(KQ_, true, 8) else OP_LAUNCH(KQ_, true, 4) }                \
         else if (wpg >= 16 && KQ_ <= 10) OP_LAUNCH(KQ_, false, 16)                                           \
         else if (wpg >= 8) OP_LAUNCH(KQ_, false, 8)                                                          \

@@ -1,9 +1,9 @@
-// wlsqm_internal.hpp — host-side declarations shared by the translation units of libwlsqm_hip.so.
+// wlsqm_internal.hpp — the kernel parameter block and the host-side services (errors, scratch memory, device scope) shared by the
+// translation units of libwlsqm_hip.so.  The launchers, the environment switches and the dense-row test: wlsqm_dispatch.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <stdint.h>
-#include <cstdlib>
 #include <string>
 
 #include "wlsqm_hip.h"
@@ -93,10 +93,6 @@ inline KParams slice_cases(const KParams& p, long long j0, long long n) {
 void set_error(const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
 
-// Launch the fit kernels for one (dimension, order) bucket.  Returns WLSQM_* code.
-// max_nk: extent of the neighbour axis (upper bound of nk[j]).
-int launch_fit(int dimension, int order, const KParams& p, long long max_nk, hipStream_t stream);
-
 // Optional capture of the reference's intermediates by the strict kernel (tests: bit-for-bit against tests/golden/sweep_*.npz).
 struct StrictDebug {
     double* w; long long w_stride;                  // [case, k]
@@ -113,49 +109,10 @@ bool strict_mode();
 // the normal matrix assembled from its upper triangle)
 bool accurate_mode();
 
-// name of the kernel family the last launch_fit on this thread dispatched to ("lane", "tile", "wave")
+// name of the kernel family the last launch_fit on this thread dispatched to (what wlsqm_hip_last_kernel returns: "stage", "tile1",
+// "sens-apply", "strict", ...: every note_kernel call names one)
 const char* last_kernel_name();
 void note_kernel(const char* name);
-
-// Per-device launch facts of one persistent kernel (a process may drive several GPUs): CU count, the one-time opt-in to
-// more than 64 KB of dynamic LDS, and (when the LDS size never changes) the workgroups that fit one CU.
-struct KernelSetup { int cus[16] = {}; int per_cu[16] = {}; };
-
-// Workgroups launched per resident workgroup slot.  A grid of exactly the resident workgroups leaves the tail of the launch
-// unbalanced (1M C2 cases are 62 500 tiles over 3 072 waves: 20 or 21 tiles each, and the waves do not finish their tiles at
-// the same pace); launching several workgroups per slot lets the dispatcher hand the leftovers to whichever slot frees up first
-// (tools/tune.py g1 / g8 / g16 / g1000, interleaved: C2 0.1737 / 0.1665 / 0.1656 / 0.1655 ms, C5 0.3512 / 0.3426 / 0.3386 /
-// 0.3409, C3 0.672 / 0.650 / 0.639).  WLSQM_HIP_GRID_MULT overrides it (A/B).
-inline double grid_multiple() {
-    const char* e = getenv("WLSQM_HIP_GRID_MULT");
-    const double v = e ? atof(e) : 16.0;
-    return v > 0.0 ? v : 16.0;
-}
-
-// Grid of a persistent launch: resident workgroups per CU x CUs of the current device x grid_multiple()
-// (callers clamp it to the number of tiles).
-inline int persistent_grid(const void* kern, int threads, size_t lds_bytes, size_t lds_optin, bool fixed_lds, KernelSetup& ks,
-                           long long* grid) {
-    int dev = 0;
-    WLSQM_HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16) { set_error("device ordinal out of range"); return WLSQM_EVALUE; }
-    if (!ks.cus[dev]) {
-        hipDeviceProp_t prop;
-        WLSQM_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        if (lds_optin > 64 * 1024)
-            WLSQM_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_optin));
-        ks.cus[dev] = prop.multiProcessorCount;
-    }
-    int occ = fixed_lds ? ks.per_cu[dev] : 0;
-    if (!occ) {
-        WLSQM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, threads, lds_bytes));
-        if (occ < 1) occ = 1;
-        if (fixed_lds) ks.per_cu[dev] = occ;
-    }
-    *grid = (long long)((double)occ * ks.cus[dev] * grid_multiple());
-    if (*grid < 1) *grid = 1;
-    return WLSQM_OK;
-}
 
 // RAII device buffer
 struct DevBuf {

@@ -26,7 +26,7 @@
 
 #include <atomic>
 
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_moments.hpp"
 
@@ -599,9 +599,9 @@ __global__ __launch_bounds__(64, MINW) void fit_ring_kernel(const KParams p, con
 // tiles per workgroup: a multiple of 4 (one solve per 4 tiles); WLSQM_HIP_RING_TILES overrides (A/B: 1M C3 cases at
 // 4 / 8 / 16 / 64 tiles per workgroup 0.532 / 0.539 / 0.536 / 0.539 ms — the dispatcher balances short workgroups best)
 static int ring_tiles_per_wg() {
-    const char* e = getenv("WLSQM_HIP_RING_TILES");
-    const int v = e ? atoi(e) : 4;
-    return v >= 1 ? v : 4;
+    long long v = 4;
+    env_int("WLSQM_HIP_RING_TILES", &v);
+    return v >= 1 ? (int)v : 4;
 }
 
 template <int DIM, int K, bool GATHER> struct RingLaunchGeom {        // ring + (index-based) the index buffer of the tile ahead
@@ -624,7 +624,7 @@ static int launch_ring_impl(const KParams& p, hipStream_t stream) {
         optin[dev] = true;
     }
     int T = ring_tiles_per_wg();
-    if (DIM == 3 && !getenv("WLSQM_HIP_RING_TILES")) {
+    if (DIM == 3 && !env_present("WLSQM_HIP_RING_TILES")) {
         // The 3D kernel solves a group of four tiles behind the NEXT tile's prefetch (its fi stores are acknowledged under that
         // tile's arithmetic), so long workgroups hide all but their last solve — if the launch still fills its rounds: with W
         // resident waves, ceil(ntiles / T / W) rounds should be nearly full.  1M C5 cases (62 500 tiles, 1 024 waves), T = 4 / 16 / 20 /

@@ -3,7 +3,7 @@
 // (fit_accurate.hip): constants, row access, make_c_nD with the reference's grouping of every product, the IEEE weight.
 // Every translation unit that includes this file must compile with `#pragma clang fp contract(off)` around its kernels: the
 // reference is gcc -O2 on x86-64 (no contraction), and bit-identity between the kernels depends on it.
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 
 #pragma clang fp contract(off)

@@ -50,7 +50,7 @@
 #pragma once
 #include <cstdlib>
 
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_moments.hpp"
 
@@ -463,8 +463,8 @@ static int launch_tile_impl(const KParams& p, hipStream_t stream) {
     int rc = persistent_grid(reinterpret_cast<const void*>(kern), G::NT, lds_bytes, lds_bytes, true, setup, &grid);
     if (rc != WLSQM_OK) return rc;
     if (grid > ntiles) grid = ntiles;
-    const char* rs = getenv("WLSQM_HIP_TILE_RUN_STORE");
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::NT), lds_bytes, stream, p, ntiles | ((rs && rs[0] == '0') ? (1ll << 40) : 0));
+    const bool run_store = env_first("WLSQM_HIP_TILE_RUN_STORE") != '0';
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::NT), lds_bytes, stream, p, ntiles | (run_store ? 0 : (1ll << 40)));
     WLSQM_HIP_CHECK(hipGetLastError());
     if (!SPLIT) note_kernel(GATHER ? "tile-gather" : "tile");
     return WLSQM_OK;

@@ -2,7 +2,7 @@
 // solve_many_kernel (solve_many.hip): a 64-lane workgroup owns a tile of 16 cases, 4 lanes per case, lane (c, h)
 // takes the neighbours [h*KPL, (h+1)*KPL); xk goes through padded LDS rows, fk straight into registers.
 #pragma once
-#include "wlsqm_internal.hpp"
+#include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 
 namespace wlsqm {

@@ -416,3 +416,23 @@ def test_isa_record_is_of_these_sources():
               for f in sorted(glob.glob(os.path.join(ROOT, "include", "*.h")))]
     want = hashlib.sha256("".join(lines).encode()).hexdigest()
     assert first.split(": ")[1] == want, "profiles/isa_r06.txt was made from other sources: regenerate it (tools/isa_stats.sh)"
+
+
+def test_dispatch_header_is_the_one_place():
+    """csrc/wlsqm_dispatch.hpp is the one place for what the host code around the kernels shares (plain text scans): (a) getenv is
+    called there and nowhere else in csrc/; (b) every "WLSQM_..." string literal in csrc/ is a row of the header's table of
+    switches, and every row is read somewhere; (c) no .hip file declares a launch_* function that it does not define."""
+    csrc = os.path.join(ROOT, "python-wlsqm_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hpp"))}
+    assert [f for f, t in text.items() if "getenv(" in t] == ["wlsqm_dispatch.hpp"]
+    rows = re.findall(r"^//   (WLSQM_[A-Z0-9_]+) +(?:USER|A/B) ", text["wlsqm_dispatch.hpp"], flags=re.M)
+    assert len(rows) >= 40 and len(rows) == len(set(rows))
+    read = set(re.findall(r'"(WLSQM_[A-Z0-9_]+)"', "".join(text.values())))
+    assert read == set(rows), sorted(read ^ set(rows))
+    for f, t in text.items():
+        if f.endswith(".hip"):
+            # a prototype: a line that opens with type words (no statement) and the name, up to ");" with no body in between
+            head = r"^(?![^\n(]*\breturn\b)(?:[\w:<>&*]+\s+)+(launch_\w+)\([^;{}]*\)\s*"
+            declared = set(re.findall(head + ";", t, flags=re.M))
+            defined = set(re.findall(head + r"\{", t, flags=re.M))
+            assert declared <= defined, "%s declares %s" % (f, sorted(declared - defined))
