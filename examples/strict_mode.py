@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
-"""The two numerics modes on one batch.
+"""The numerics modes on one batch.
 
 FAST (default): MI355X-first arithmetic — moment form, neighbour sums split over lanes, FMA, unpivoted LDL^T.
 STRICT: every floating-point operation of the reference (make_c / weights / make_A / Ruiz scaling / pivoted LU / solve) in the
 reference's own order, so that the result differs from python-wlsqm's only by LAPACK's internal summation order.
-Both are as accurate against the exact derivatives; they differ from each other in the last digits, which is what this prints.
+ACCURATE: the strict arithmetic with the normal matrix assembled from its upper triangle; CONTRACTED: the accurate mode with its sums,
+LU update and substitutions fused (a += b * c in one rounding) — the two modes that stay within 1e-10 of the reference at a fraction of
+the strict mode's time.
+All are as accurate against the exact derivatives; they differ from each other in the last digits, which is what this prints.
 Run on a machine with one MI355X:  python examples/strict_mode.py"""
 import os
 import sys
@@ -35,9 +38,20 @@ with whip.strict():                                       # or WLSQM_HIP_STRICT=
     wlsqm.fit_2D_many_parallel(fi=fi_strict, **args)
     print("strict kernel:", whip.last_kernel())
 
+fi_accurate = np.zeros((n, 6))
+with whip.accurate():                                     # or WLSQM_HIP_STRICT=2 / "accurate", or whip.set_strict("accurate")
+    wlsqm.fit_2D_many_parallel(fi=fi_accurate, **args)
+    print("accurate kernel:", whip.last_kernel())
+
+fi_contracted = np.zeros((n, 6))
+with whip.contracted():                                   # or WLSQM_HIP_STRICT=3 / "contracted", or whip.set_strict("contracted")
+    wlsqm.fit_2D_many_parallel(fi=fi_contracted, **args)
+    print("contracted kernel:", whip.last_kernel())       # "accurate-fma"
+
 scale = np.abs(fi_strict).max(axis=0)
-print("largest difference between the modes per DOF column (relative to the column's largest value):")
-print("   ", np.array2string(np.abs(fi_fast - fi_strict).max(axis=0) / scale, precision=1))
-for name, fi in (("fast", fi_fast), ("strict", fi_strict)):
-    print("%-6s d2f/dx2: max error against the exact derivative %.2e (truncation error of the order-2 model dominates)"
+print("largest difference from the strict mode per DOF column (relative to the column's largest value):")
+for name, fi in (("fast", fi_fast), ("accurate", fi_accurate), ("contracted", fi_contracted)):
+    print("    %-10s" % name, np.array2string(np.abs(fi - fi_strict).max(axis=0) / scale, precision=1))
+for name, fi in (("fast", fi_fast), ("strict", fi_strict), ("accurate", fi_accurate), ("contracted", fi_contracted)):
+    print("%-10s d2f/dx2: max error against the exact derivative %.2e (truncation error of the order-2 model dominates)"
           % (name, np.abs(fi[:, wlsqm.i2_X2] - exact_xx).max()))

@@ -123,11 +123,23 @@ int wlsqm_hip_fit_many_device_orders(const wlsqm_batch* b, int device, void* str
  *    its upper triangle, entry (j, m) = sum_k (w c_m) c_j for m >= j, and mirrored; the equilibration then sees a symmetric matrix
  *    (row and column scales coincide bit for bit) and runs one pass per sweep.  Quotients and roots are correctly rounded (the
  *    compiler's IEEE sequences without their range scaling where every operand is checked to be in range, the full sequences
- *    otherwise).  Applies to the basic fits of the 2D / 3D systems up to 10 unknowns, per case, for the cases without a known
- *    DOF; every other case of an accurate-mode call runs mode 1.  Within 1e-10 of the reference on every column of BASELINE
+ *    otherwise).  Applies to the basic fits of the 2D / 3D systems up to 10 unknowns (2D orders 0-3, 3D orders 0-2) with EVERY
+ *    knowns mask (stray bits beyond the polynomial's DOFs included), both weightings, dense, strided or index-based input and
+ *    ragged neighbour counts; every other call of the mode (1D, 2D order 4, 3D orders 3-4, sensitivities, refinement) runs mode 1.  Within 1e-10 of the reference on every column of BASELINE
  *    configs[1] and configs[4] (as mode 1), at the fast kernels' order of magnitude in time.
+ * 3: contracted (csrc/fit_accurate.hip, its FMA instantiations; wlsqm_hip_last_kernel: "accurate-fma"): mode 2 with a += b * c
+ *    fused into one rounding in the neighbour sums of the matrix (acc = fma(w c_m, c_j, acc), the product w c_m rounded first)
+ *    and of the right-hand side (acc = fma(w f_k, c_a, acc)), in the update of the LU's trailing matrix and in the forward and
+ *    back substitution — and nowhere else: the monomials, the weights, the equilibration, the scaling, the term-by-term
+ *    elimination of known DOFs, every quotient and the un-scaling are mode 2's.  Coverage and dispatch are mode 2's, as stated
+ *    above: the same shapes, masks, weightings and input forms run the fused kernels, everything else runs mode 1.
+ *    Still within 1e-10 of the reference on every column of configs[1] and configs[4], but with less room: 5.4e-11 and 5.3e-11
+ *    on the 1M-point samples and 9.0e-11 on the 16M-point configs[4] sample (1 024 cases each) — a 10 % margin there, where
+ *    mode 2 is at 2.3e-11.
  * The mode belongs to the calling thread; its initial value is the environment variable WLSQM_HIP_STRICT (unset / 0: fast; 1;
- * 2 or "accurate").  wlsqm_hip_set_strict returns the previous mode. */
+ * 2 or "accurate"; 3 or "contracted" — first character 2 / a / A and 3 / c / C; before mode 3 existed the latter three selected
+ * mode 1, as every other value does).  wlsqm_hip_set_strict takes 0..3 (any other nonzero value: 1) and returns the previous
+ * mode. */
 int wlsqm_hip_set_strict(int mode);
 int wlsqm_hip_get_strict(void);
 

@@ -29,8 +29,10 @@ const char* last_kernel_name() { return g_kernel; }
 void note_kernel(const char* name) { g_kernel = name; }
 
 // Numerics mode of the calling thread: 0 = the fast kernels, 1 = reference-order arithmetic (fit_strict.hip), 2 = accurate
-// (fit_accurate.hip: reference-order arithmetic with the normal matrix assembled from its upper triangle).  The first use on a
-// thread takes WLSQM_HIP_STRICT from the environment (unset / 0, 1, 2 or "accurate"); wlsqm_hip_set_strict() overrides it.
+// (fit_accurate.hip: reference-order arithmetic with the normal matrix assembled from its upper triangle), 3 = contracted (the
+// accurate mode with its sums, LU update and substitutions fused).  The first use on a thread takes WLSQM_HIP_STRICT from the
+// environment (unset / 0, 1, 2 or "accurate", 3 or "contracted"); wlsqm_hip_set_strict() overrides it.  (The values 3.. / c.. / C..
+// meant strict, as "anything else", before mode 3 existed.)
 static thread_local int g_strict = -1;
 // what the calling thread says about the neighbour counts of the dense DEVICE-resident batches it hands over (wlsqm_hip_set_row_hint; the host
 // entry points look at the counts themselves): 1 every case fills its row (default), 2 ragged, 0 unknown (the kernels find out)
@@ -39,12 +41,13 @@ static thread_local int g_order_hint = 1;                            // the neig
 int row_hint_value() { return g_row_hint; }
 int order_hint_value() { return g_order_hint; }
 static int strict_mode_value();
-bool accurate_mode() { return strict_mode_value() == 2; }
+bool accurate_mode() { return strict_mode_value() >= 2; }
+bool contracted_mode() { return strict_mode_value() == 3; }
 bool strict_mode() { return strict_mode_value() >= 1; }
 static int strict_mode_value() {
     if (g_strict < 0) {
         const char c = env_first("WLSQM_HIP_STRICT");
-        g_strict = (!c || c == '0') ? 0 : ((c == '2' || c == 'a' || c == 'A') ? 2 : 1);
+        g_strict = (!c || c == '0') ? 0 : (c == '2' || c == 'a' || c == 'A') ? 2 : (c == '3' || c == 'c' || c == 'C') ? 3 : 1;
     }
     return g_strict;
 }
@@ -370,7 +373,7 @@ int wlsqm_hip_device_count(void) {
 
 int wlsqm_hip_set_strict(int mode) {
     const int prev = strict_mode_value();
-    g_strict = mode == 2 ? 2 : (mode ? 1 : 0);
+    g_strict = (mode == 2 || mode == 3) ? mode : (mode ? 1 : 0);
     return prev;
 }
 int wlsqm_hip_get_strict(void) { return strict_mode_value(); }

@@ -60,6 +60,13 @@
 // operations one for one, i.e. at least as close to the reference).  (Round 5's one-lane-per-case strict form of 2D order 4 with F known —
 // `LANE14`: bit-identical to the strict kernels, 1 693 spilled registers, slower than the row-per-lane kernel — is gone from the library; it is
 // in the history at commit c9ef97d.)
+//
+// THE CONTRACTED MODE (WLSQM_HIP_STRICT=3 / wlsqm_hip_set_strict(3); last_kernel "accurate-fma") is this file once more with the template
+// parameter FMA = true: the accurate mode with a <- fma(b, c, a) in the neighbour sums of the matrix ((w c_m) is rounded, then fused
+// with c_j) and of the right-hand side ((w f_k) rounded, fused with c_a), in the update of the trailing matrix of the LU and in the
+// two substitutions — the V_SYM | V_FMA switches of the tests' CPU checker, bit for bit on every path below (tests/test_gpu_contracted.py).
+// The monomials, the weights, the equilibration sweeps, the scaling, the term-by-term elimination of known DOFs, the quotients and
+// the un-scaling stay rounded operation by operation.  FMA = false instantiates exactly the code it did before the parameter existed.
 #include <atomic>
 #include <type_traits>
 
@@ -97,6 +104,15 @@ constexpr int GRP = WLSQM_ACC_GRP < CH ? WLSQM_ACC_GRP : CH;                    
 template <int N> __host__ __device__ constexpr int utri(int i, int m) { return i * N - i * (i - 1) / 2 + (m - i); }   // i <= m < N
 
 __host__ __device__ constexpr int minw(int NO) { return NO <= 6 ? WLSQM_ACC_MINW6 : WLSQM_ACC_MINW10; }
+
+// a += b c and a -= b c.  FMA (the CONTRACTED mode, WLSQM_HIP_STRICT=3): ONE rounding, spelled as the builtin — the file is compiled with
+// contraction off, so these are the only places where a product meets a sum unrounded (the V_FMA switch of the tests' CPU checker).
+// (Macros around the accurate mode's own statements, not functions: with the sum written as a function's return value the FMA = false
+// kernels came out of the register allocator with other spill counts — same operations, another order in the IR.  They read the
+// template parameter `FMA` of the function they are used in — lu_solve_store and accurate_group, nowhere else — and are undefined
+// again at the end of this file.)
+#define WLSQM_ACC_MAC(a, b, c)  do { if constexpr (FMA) (a) = __builtin_fma((b), (c), (a)); else (a) += (b) * (c); } while (0)
+#define WLSQM_ACC_NMAC(a, b, c) do { if constexpr (FMA) (a) = __builtin_fma(-(b), (c), (a)); else (a) -= (b) * (c); } while (0)
 
 }  // namespace acc
 
@@ -211,7 +227,9 @@ __device__ __forceinline__ bool ruiz_sym(const double (&U)[N * (N + 1) / 2], dou
 // (row-scaled sums, knowns eliminated); `known`: DOFs that are not written (rows of the identity in U: see the header).  The row
 // exchange is written as selects over the candidate rows; a wave none of whose cases leaves the diagonal pivot in a column skips it.
 // (The 2 N quotients here are the compiler's IEEE sequences: a pivot may be anything.)
-template <int N>
+// FMA: the update of the trailing matrix and the two substitutions are a <- fma(-l, u, a) (the contracted mode); the scaling, the
+// multipliers, the quotients and the un-scaling are rounded as ever.
+template <int N, bool FMA>
 __device__ __forceinline__ void lu_solve_store(const double (&U)[N * (N + 1) / 2], const double (&rs)[N], double (&b)[N], const unsigned known,
                                                double* fio) {
     double A[N][N];
@@ -243,7 +261,7 @@ __device__ __forceinline__ void lu_solve_store(const double (&U)[N * (N + 1) / 2
         for (int m = c0 + 1; m < N; ++m) {
             const double u = A[c0][m];
 #pragma unroll
-            for (int i = c0 + 1; i < N; ++i) A[i][m] -= A[i][c0] * u;
+            for (int i = c0 + 1; i < N; ++i) WLSQM_ACC_NMAC(A[i][m], A[i][c0], u);
         }
     }
 #pragma unroll
@@ -256,12 +274,12 @@ __device__ __forceinline__ void lu_solve_store(const double (&U)[N * (N + 1) / 2
 #pragma unroll
     for (int c0 = 0; c0 < N; ++c0)
 #pragma unroll
-        for (int i = c0 + 1; i < N; ++i) b[i] -= A[i][c0] * b[c0];
+        for (int i = c0 + 1; i < N; ++i) WLSQM_ACC_NMAC(b[i], A[i][c0], b[c0]);
 #pragma unroll
     for (int c0 = N - 1; c0 >= 0; --c0) {
         b[c0] /= A[c0][c0];
 #pragma unroll
-        for (int i = 0; i < c0; ++i) b[i] -= A[i][c0] * b[c0];
+        for (int i = 0; i < c0; ++i) WLSQM_ACC_NMAC(b[i], A[i][c0], b[c0]);
     }
     // un-scale (impl.pyx:838-846); `fio` == nullptr: the caller stores the wave's rows as one run (b is left holding the results)
 #pragma unroll
@@ -286,7 +304,9 @@ __device__ __forceinline__ void lu_solve_store(const double (&U)[N * (N + 1) / 2
 // bit afterwards.  A group with a wrong guess (unsorted neighbours: a ball query) or an operand outside the safe range of the fast
 // sequences is fitted again, from scratch, by the two-pass form: speculation, never approximation.
 // Returns true (wave-uniform, SPEC only) when the caller must run the two-pass form on this group; nothing has been stored then.
-template <int DIM, int ORDER, bool DENSE, bool SPEC>
+// FMA: the contracted mode — the neighbour sums of the matrix and of the right-hand side, the LU update and the substitutions fused
+// (WLSQM_ACC_MAC / _NMAC above), every other operation of this function exactly as in the accurate mode.
+template <int DIM, int ORDER, bool DENSE, bool SPEC, bool FMA>
 __device__ __forceinline__ bool accurate_group(const KParams& p, const long long t0, double* const lds) {
     using namespace strict;
     using namespace acc;
@@ -533,10 +553,10 @@ __device__ __forceinline__ bool accurate_group(const KParams& p, const long long
         for (int om = 0; om < N; ++om) {
             const double wc = w * c[om];
 #pragma unroll
-            for (int oj = 0; oj <= om; ++oj) U[utri<N>(oj, om)] += wc * c[oj];
+            for (int oj = 0; oj <= om; ++oj) WLSQM_ACC_MAC(U[utri<N>(oj, om)], wc, c[oj]);
         }
 #pragma unroll
-        for (int oj = 0; oj < N; ++oj) b[oj] += wf * c[oj];
+        for (int oj = 0; oj < N; ++oj) WLSQM_ACC_MAC(b[oj], wf, c[oj]);
     };
     // Known DOFs of the masked full system (the header): rows of the identity, right-hand side 0 (a wave-uniform test: the common
     // wave has none).
@@ -590,7 +610,7 @@ __device__ __forceinline__ bool accurate_group(const KParams& p, const long long
         // (systems up to 6 unknowns: the 10-unknown kernels are at their 512 registers and paid for it with spills in their sweeps)
         const bool run = DENSE && N <= 6 && (64 * N) % 2 == 0 && (N * 64 * 8 <= (int)sizeof(double) * (64 * XPITCH + 64 * FPITCH)) && nvalid == 64 &&
                          !p.case_index && p.sfi_j == N && ((reinterpret_cast<uintptr_t>(p.fi) & 15u) == 0) && __all(active && known == 0u);
-        if (active) lu_solve_store<N>(U, rs, b, known, run ? nullptr : fio);
+        if (active) lu_solve_store<N, FMA>(U, rs, b, known, run ? nullptr : fio);
         if (run) {
             __syncthreads();                                          // the last chunk has been read
 #pragma unroll
@@ -734,11 +754,11 @@ __host__ __device__ constexpr int acc_lds_doubles() {
 // SPEC: the speculative form.  status[g] = 1: the wave could not vouch for group g (an operand outside the safe range of the fast
 // sequences): the clean-up kernel behind this one fits it again with the IEEE sequences.  A workgroup takes the groups blockIdx.x,
 // blockIdx.x + gridDim.x, ...
-template <int DIM, int ORDER, bool DENSE, bool SPEC>
+template <int DIM, int ORDER, bool DENSE, bool SPEC, bool FMA>
 __global__ __launch_bounds__(64, acc::minw(ndofs(DIM, ORDER))) void fit_accurate_kernel(const KParams p, const long long ngroups, unsigned char* const status) {
     __shared__ __attribute__((aligned(16))) double lds[acc_lds_doubles<DIM, DENSE>()];
     for (long long g = blockIdx.x; g < ngroups; g += gridDim.x) {
-        const bool again = accurate_group<DIM, ORDER, DENSE, SPEC>(p, g * 64, lds);
+        const bool again = accurate_group<DIM, ORDER, DENSE, SPEC, FMA>(p, g * 64, lds);
         if constexpr (SPEC) { if (threadIdx.x == 0) status[g] = again ? 1 : 0; }
         if (DENSE) __syncthreads();                                   // the LDS is reused by the next group
     }
@@ -746,7 +766,7 @@ __global__ __launch_bounds__(64, acc::minw(ndofs(DIM, ORDER))) void fit_accurate
 
 // the groups the speculative kernel could not vouch for (none in the common case: ~2 us of idle waves, tools/ubench/launch_gap.hip):
 // a small grid looks at the status bytes, 64 groups per wave and step
-template <int DIM, int ORDER>
+template <int DIM, int ORDER, bool FMA>
 __global__ __launch_bounds__(64, acc::minw(ndofs(DIM, ORDER))) void fit_accurate_cleanup_kernel(const KParams p, const long long ngroups, const unsigned char* const status) {
     __shared__ __attribute__((aligned(16))) double lds[acc_lds_doubles<DIM, true>()];
     for (long long g0 = (long long)blockIdx.x * 64; g0 < ngroups; g0 += (long long)gridDim.x * 64) {
@@ -755,13 +775,13 @@ __global__ __launch_bounds__(64, acc::minw(ndofs(DIM, ORDER))) void fit_accurate
         while (todo) {                                                // wave-uniform
             const int q = __ffsll((long long)todo) - 1;
             todo &= todo - 1ull;
-            (void)accurate_group<DIM, ORDER, true, false>(p, (g0 + q) * 64, lds);
+            (void)accurate_group<DIM, ORDER, true, false, FMA>(p, (g0 + q) * 64, lds);
             __syncthreads();                                          // the LDS is reused by the next group
         }
     }
 }
 
-template <int DIM, int ORDER>
+template <int DIM, int ORDER, bool FMA>
 static int launch_accurate(const KParams& p, hipStream_t stream) {
     const long long groups = (p.ncases + 63) / 64;
     if (groups <= 0) return WLSQM_OK;
@@ -777,11 +797,11 @@ static int launch_accurate(const KParams& p, hipStream_t stream) {
         int rc = call_scratch_acquire(&cs, (size_t)groups, stream);
         if (rc != WLSQM_OK) return rc;
         unsigned char* const status = static_cast<unsigned char*>(cs.p);
-        hipLaunchKernelGGL((fit_accurate_kernel<DIM, ORDER, true, true>), dim3((unsigned)groups), dim3(64), 0, stream, p, groups, status);
+        hipLaunchKernelGGL((fit_accurate_kernel<DIM, ORDER, true, true, FMA>), dim3((unsigned)groups), dim3(64), 0, stream, p, groups, status);
         hipError_t le = hipGetLastError();
         if (le == hipSuccess) {
             const long long want = (groups + 63) / 64, resident = 512LL * acc::minw(ndofs(DIM, ORDER));
-            hipLaunchKernelGGL((fit_accurate_cleanup_kernel<DIM, ORDER>), dim3((unsigned)(want < resident ? want : resident)), dim3(64), 0, stream, p, groups, status);
+            hipLaunchKernelGGL((fit_accurate_cleanup_kernel<DIM, ORDER, FMA>), dim3((unsigned)(want < resident ? want : resident)), dim3(64), 0, stream, p, groups, status);
             le = hipGetLastError();
         }
         rc = call_scratch_release(&cs, stream);
@@ -789,9 +809,9 @@ static int launch_accurate(const KParams& p, hipStream_t stream) {
         return rc;
     }
     if (dense)
-        hipLaunchKernelGGL((fit_accurate_kernel<DIM, ORDER, true, false>), dim3((unsigned)groups), dim3(64), 0, stream, p, groups, (unsigned char*)nullptr);
+        hipLaunchKernelGGL((fit_accurate_kernel<DIM, ORDER, true, false, FMA>), dim3((unsigned)groups), dim3(64), 0, stream, p, groups, (unsigned char*)nullptr);
     else
-        hipLaunchKernelGGL((fit_accurate_kernel<DIM, ORDER, false, false>), dim3((unsigned)groups), dim3(64), 0, stream, p, groups, (unsigned char*)nullptr);
+        hipLaunchKernelGGL((fit_accurate_kernel<DIM, ORDER, false, false, FMA>), dim3((unsigned)groups), dim3(64), 0, stream, p, groups, (unsigned char*)nullptr);
     WLSQM_HIP_CHECK(hipGetLastError());
     return WLSQM_OK;
 }
@@ -799,11 +819,12 @@ static int launch_accurate(const KParams& p, hipStream_t stream) {
 // Accurate mode, basic fits of the 2D / 3D systems up to 10 unknowns: EVERY case of the call is fitted here — one kernel, and behind
 // it a clean-up kernel that is idle unless a group's operands left the safe range of the fast sequences.
 // *handled = false: the shape or the call has no accurate kernel (1D, 2D order 4, 3D orders 3-4, sensitivities, refinement) and the
-// strict kernels take every case.
+// strict kernels take every case.  FMA: the contracted mode's instantiations (launch_fit_strict picks: contracted_mode()).
+template <bool FMA>
 int launch_fit_accurate(int dimension, int order, const KParams& p, hipStream_t stream, bool* handled) {
     *handled = false;
     if (p.do_sens || p.iterative) return WLSQM_OK;
-#define CASE(D, O) if (dimension == D && order == O) { *handled = true; return launch_accurate<D, O>(p, stream); }
+#define CASE(D, O) if (dimension == D && order == O) { *handled = true; return launch_accurate<D, O, FMA>(p, stream); }
 #ifdef WLSQM_ACC_DEV_ONLY22      // (development: one shape, for quick looks at the ISA)
     CASE(2, 2)
 #else
@@ -813,5 +834,10 @@ int launch_fit_accurate(int dimension, int order, const KParams& p, hipStream_t 
 #undef CASE
     return WLSQM_OK;
 }
+template int launch_fit_accurate<false>(int, int, const KParams&, hipStream_t, bool*);
+template int launch_fit_accurate<true>(int, int, const KParams&, hipStream_t, bool*);
 
 }  // namespace wlsqm
+
+#undef WLSQM_ACC_MAC
+#undef WLSQM_ACC_NMAC

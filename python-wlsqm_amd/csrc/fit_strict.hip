@@ -1090,9 +1090,11 @@ int launch_fit_strict(int dimension, int order, const KParams& p, const StrictDe
     // call of the mode (2D order 4, 3D orders 3-4, 1D, sensitivities, refinement, the debug capture) is the strict mode's
     if (accurate_mode() && !dbg_in) {
         bool taken = false;
-        const int rc = launch_fit_accurate(dimension, order, p, stream, &taken);
+        const bool fma = contracted_mode();                          // mode 3: the same dispatch, the fused instantiations
+        const int rc = fma ? launch_fit_accurate<true>(dimension, order, p, stream, &taken)
+                           : launch_fit_accurate<false>(dimension, order, p, stream, &taken);
         if (rc != WLSQM_OK) return rc;
-        if (taken) { note_kernel("accurate"); return WLSQM_OK; }
+        if (taken) { note_kernel(fma ? "accurate-fma" : "accurate"); return WLSQM_OK; }
     }
 #define CASE(D, O) if (dimension == D && order == O) return launch_strict<D, O>(p, dbg, stream);
     CASE(1, 0) CASE(1, 1) CASE(1, 2) CASE(1, 3) CASE(1, 4)

@@ -16,7 +16,7 @@ namespace wlsqm {
 // two marked "first use").  "=c" compares the FIRST character of the value; unset or empty never matches.
 //
 //   name                             kind  values            effect
-//   WLSQM_HIP_STRICT                 USER  0 | 1 | 2,a,A     numerics mode of a thread at its first use: unset / empty / 0.. fast, 2.. / a.. / A.. accurate, anything else strict (api.hip)
+//   WLSQM_HIP_STRICT                 USER  0 | 1 | 2,a,A | 3,c,C   numerics mode of a thread at its first use: unset / empty / 0.. fast, 2.. / a.. / A.. accurate, 3.. / c.. / C.. contracted, anything else strict (api.hip; before the contracted mode existed, 3.. / c.. / C.. fell under "anything else")
 //   WLSQM_HIP_REPACK_MB              USER  integer > 0       scratch of one slice of the repack / gather passes in MB (default 512; api.hip)
 //   WLSQM_HIP_COPY_THREADS           USER  integer           host threads that pack rows for the host-array entry points (default 16, first use; hostio.hpp)
 //   WLSQM_HIP_TRACE                  USER  present           the host-array fit prints its phase timings to stderr (api.hip)
@@ -149,7 +149,8 @@ FitLauncher launch_tile_moments;               // fit_tile.hip: first kernel of 
 int launch_fit_lane(int dimension, int order, const KParams& p, hipStream_t stream);                              // fit_lane.hip
 int launch_fit_wave(int dimension, int order, const KParams& p, hipStream_t stream);                              // fit_wave.hip
 int launch_fit_strict(int dimension, int order, const KParams& p, const StrictDebug* dbg, hipStream_t stream);    // fit_strict.hip
-// accurate mode: offered every batch by launch_fit_strict before its own kernels (K is p.max_nk)
+// accurate and contracted mode: offered every batch by launch_fit_strict before its own kernels (K is p.max_nk); FMA = contracted_mode()
+template <bool FMA>
 int launch_fit_accurate(int dimension, int order, const KParams& p, hipStream_t stream, bool* handled);           // fit_accurate.hip
 
 // first kernels of the sensitivities' path (fit_sens.hip): the basic fit of one slice that also leaves every case's inverse normal matrix

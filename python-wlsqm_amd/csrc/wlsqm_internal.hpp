@@ -104,10 +104,13 @@ struct StrictDebug {
 // true when the calling thread asked for reference-order numerics (WLSQM_HIP_STRICT / wlsqm_hip_set_strict): launch_fit then
 // dispatches every shape to fit_strict.hip
 bool strict_mode();
-// true for mode 2, "accurate" (fit_accurate.hip): strict_mode() is true as well — every call takes the strict dispatch, in which the
+// true for mode 2, "accurate", and mode 3, "contracted" (fit_accurate.hip): strict_mode() is true as well — every call takes the strict dispatch, in which the
 // basic fits of the 2D / 3D systems up to 10 unknowns without a known DOF run fit_accurate_kernel (reference-order arithmetic with
 // the normal matrix assembled from its upper triangle)
 bool accurate_mode();
+// true for mode 3 alone: the accurate dispatch runs the FMA = true instantiations of fit_accurate.hip (the accurate mode's arithmetic
+// with the neighbour sums, the LU update and the substitutions fused; "accurate-fma")
+bool contracted_mode();
 
 // name of the kernel family the last launch_fit on this thread dispatched to (what wlsqm_hip_last_kernel returns: "stage", "tile1",
 // "sens-apply", "strict", ...: every note_kernel call names one)

@@ -13,24 +13,26 @@ from . import _binding as B
 import contextlib
 
 __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_cloud_device", "device_count", "knn", "ball", "nearest",
-           "last_kernel", "set_strict", "get_strict", "strict", "accurate", "strict_intermediates",
+           "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
            "getrf_batched", "getrs_batched", "gesv_batched", "sytrf_batched", "sytrs_batched", "sysv_batched", "symmetrize_batched"]
 
 
 def _mode_code(mode):
-    """False / 0 -> 0 (fast), True / 1 / "strict" -> 1, 2 / "accurate" -> 2."""
+    """False / 0 -> 0 (fast), True / 1 / "strict" -> 1, 2 / "accurate" -> 2, 3 / "contracted" -> 3."""
     if isinstance(mode, str):
         m = mode.lower()
+        if m in ("contracted", "3"):
+            return 3
         if m in ("accurate", "2"):
             return 2
         if m in ("strict", "1", "true"):
             return 1
         if m in ("fast", "0", "false", ""):
             return 0
-        raise ValueError("numerics mode must be 'fast', 'strict' or 'accurate', got %r" % (mode,))
+        raise ValueError("numerics mode must be 'fast', 'strict', 'accurate' or 'contracted', got %r" % (mode,))
     if mode is True:
         return 1
-    return 2 if int(mode) == 2 else (1 if mode else 0)
+    return int(mode) if int(mode) in (2, 3) else (1 if mode else 0)
 
 
 def set_strict(on):
@@ -38,22 +40,25 @@ def set_strict(on):
     the environment), True / "strict" = reference-order arithmetic (csrc/fit_strict.hip: the reference's operations one for one,
     IEEE divide and sqrt, no contraction), 2 / "accurate" = the same arithmetic with the normal
     matrix assembled from its upper triangle (csrc/fit_accurate.hip: as close to the reference as the strict mode — 1e-10 on every
-    column of BASELINE configs[1] / configs[4] — at a fraction of its time; cases it does not cover run the strict kernels).
-    Returns the previous mode: False, True or 2."""
+    column of BASELINE configs[1] / configs[4] — at a fraction of its time; cases it does not cover run the strict kernels),
+    3 / "contracted" = the accurate mode with its neighbour sums, LU update and substitutions fused (a <- fma(b, c, a); the same
+    kernels and coverage; still within 1e-10 on every column of those configs, with a thinner margin: 9.0e-11 on the 16M-point
+    configs[4] sample).
+    Returns the previous mode: False, True, 2 or 3."""
     prev = B.lib().wlsqm_hip_set_strict(_mode_code(on))
-    return 2 if prev == 2 else bool(prev)
+    return prev if prev in (2, 3) else bool(prev)
 
 
 def get_strict():
-    """False (fast), True (strict) or 2 (accurate)."""
+    """False (fast), True (strict), 2 (accurate) or 3 (contracted)."""
     v = B.lib().wlsqm_hip_get_strict()
-    return 2 if v == 2 else bool(v)
+    return v if v in (2, 3) else bool(v)
 
 
 @contextlib.contextmanager
 def strict(on=True):
     """``with wlsqm.hip.strict(): ...`` — reference-order numerics inside the block (None: leave the mode alone;
-    ``strict("accurate")`` / ``strict(2)``: the accurate mode)."""
+    ``strict("accurate")`` / ``strict(2)``: the accurate mode; ``strict("contracted")`` / ``strict(3)``: the contracted mode)."""
     if on is None:
         yield
         return
@@ -67,6 +72,11 @@ def strict(on=True):
 def accurate():
     """``with wlsqm.hip.accurate(): ...`` — the accurate numerics mode inside the block."""
     return strict(2)
+
+
+def contracted():
+    """``with wlsqm.hip.contracted(): ...`` — the contracted numerics mode (the accurate mode with fused sums) inside the block."""
+    return strict(3)
 
 
 def device_count():

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Fast / accurate / strict kernel times on BASELINE shapes (ms per launch, HIP events): python tools/time_accurate.py [ncases] [configs] [shuffle]
+"""Fast / accurate / contracted / strict kernel times on BASELINE shapes (ms per launch, HIP events): python tools/time_accurate.py [ncases] [configs] [shuffle]
 ("shuffle": the neighbours of every case in random order, as a ball query delivers them.)  One line per (config, mode): ms, fraction of the 8 TB/s HBM peak from the algorithmic bytes, kernel family."""
 import os, sys
 import numpy as np
@@ -31,7 +31,7 @@ def main():
         nk_d = torch.full((n,), nk, dtype=torch.int32, device=dev)
         wm_d = torch.full((n,), cfg["wm"], dtype=torch.int32, device=dev)
         kn_d = torch.full((n,), int(os.environ.get("WLSQM_TIME_KNOWNS", cfg["knowns"])), dtype=torch.int64, device=dev)
-        modes = [{"fast": False, "accurate": 2, "strict": True}[m] for m in os.environ.get("WLSQM_TIME_MODES", "fast,accurate,strict").split(",")]
+        modes = [{"fast": False, "accurate": 2, "contracted": 3, "strict": True}[m] for m in os.environ.get("WLSQM_TIME_MODES", "fast,accurate,strict").split(",")]
         for mode in modes:
             fi = torch.zeros((n, no), dtype=torch.float64, device=dev); fi[:, 0] = F_d
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -43,7 +43,7 @@ def main():
             for _ in range(reps): run()
             ev1.record(); torch.cuda.synchronize()
             ms = ev0.elapsed_time(ev1) / reps
-            print("%s %-8s n=%d: %8.4f ms  frac %.3f  (%s)" % (name, {False: "fast", 2: "accurate", True: "strict"}[mode], n, ms,
+            print("%s %-8s n=%d: %8.4f ms  frac %.3f  (%s)" % (name, {False: "fast", 2: "accurate", 3: "contracted", True: "strict"}[mode], n, ms,
                                                                 BYTES[name] * n / (ms * 1e-3) / 8e12, whip.last_kernel()), flush=True)
 
 if __name__ == "__main__":
