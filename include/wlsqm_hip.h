@@ -293,6 +293,56 @@ int wlsqm_hip_expert_destroy(wlsqm_expert* h);
 int wlsqm_hip_interpolate_fit_host(int dimension, int order, const double* xi, const double* fi,
                                    const double* x, int64_t x_stride, int64_t nx, int diff, double* out, int device);
 
+/* ---- interpolation plans (extension): search once, evaluate many times, device-resident (csrc/interp_plan.hip) ----
+ * A plan holds everything about "these models evaluated at these points" that does not depend on the coefficients: its own
+ * packed copies of the origins xi[nmodels, dimension], the orders and the points x[nx, dimension], and per point the model
+ * number (mode 0 = nearest: the nearest origin, ties to the smaller index, or the caller's I_dev) or the list of the models
+ * whose origin lies within r (mode 1 = continuous).  The caller's arrays may be freed after create.
+ *
+ * create: all pointers are DEVICE pointers; strides in elements, rows of `dimension` contiguous coordinates.  order_dev: one
+ * int32 per model, or order_stride 0 for one shared value.  I_dev (nullable, nearest only): the model per point given by the
+ * caller instead of searched.  r is read in continuous mode only.  May allocate and synchronises `stream`, as prepare() does.
+ * WLSQM_EVALUE on a bad dimension, mode or order, r <= 0 (continuous), nmodels outside 1 .. 2^31 - 1, nx outside 0 .. 2^31 - 2,
+ * non-finite origins where they are searched, or I_dev in continuous mode; WLSQM_EMEMORY when the lists do not fit.
+ * create_expert: the origins and orders of the solver's prepared geometry (WLSQM_ERUNTIME before prepare()); the plan keeps
+ * copies and does not refer to the solver afterwards.
+ *
+ * Lists (continuous): int32 model numbers in CSR form.  Within a point the models come in the order of the grid walk: the
+ * cells of the uniform grid over the origins in ascending (z, y, x), the origins of one cell in ascending model number — a
+ * function of the inputs alone, so two plans of the same inputs hold identical lists.
+ *
+ * eval_*: out[f][d][m] = d^diffs[d] model(x_m) of field f, at out + f * out_stride_field + d * out_stride_diff + m; the
+ * coefficients of model j of field f are fi + f * fi_stride_field + j * fi_stride_model, at least `no` of them.  diffs is a
+ * HOST array of DOF numbers, ndiff <= 35, passed to the kernel by value.  Semantics as wlsqm_hip_expert_interpolate: a diff
+ * that is negative or >= the model's number of DOFs gives 0, a model number outside 0 .. nmodels - 1 gives NaN, the
+ * continuous weight is (1 - sqrt(d2 / r2))^2 and an empty list gives NaN.  A value does not depend on what else the call
+ * asks for: the result for (point, field, diff) is bit-identical whether the diff is asked alone or among others, in any
+ * position or repeated, whether the field is alone or in a stack, eager or replayed from a graph.
+ * The eval calls ONLY ENQUEUE one kernel on `stream`: no allocation, no host synchronisation, no copy — they are legal inside
+ * a stream capture.  Ordering against the work that produces fi (a solve_device on another stream, say) is plain stream
+ * order and is the CALLER's business: enqueue the evaluation on the stream of the solve, or make that stream wait for it.
+ * nx == 0 or ndiff == 0 is a no-op that returns WLSQM_OK.
+ * eval_expert evaluates the coefficients of the solver's latest solve of any kind (after solve_device that is the caller's
+ * own array, which must still be allocated); WLSQM_ERUNTIME before the first solve. */
+typedef struct wlsqm_interp_plan wlsqm_interp_plan;
+int wlsqm_hip_interp_plan_create(wlsqm_interp_plan** out, int device, void* stream, int dimension, int64_t nmodels,
+                                 const double* xi_dev, int64_t xi_stride, const int32_t* order_dev, int64_t order_stride,
+                                 int mode, const double* x_dev, int64_t x_stride, int64_t nx, double r, const int64_t* I_dev);
+int wlsqm_hip_interp_plan_create_expert(wlsqm_interp_plan** out, wlsqm_expert* h, void* stream, int mode,
+                                        const double* x_dev, int64_t x_stride, int64_t nx, double r, const int64_t* I_dev);
+/* every output is nullable: points, list entries in all, the longest list, device bytes the plan holds */
+int wlsqm_hip_interp_plan_info(const wlsqm_interp_plan* plan, int64_t* nx, int64_t* nlist, int64_t* max_list, int64_t* bytes);
+/* nearest: I_dev[nx]; continuous: off_dev[nx + 1], idx_dev[nlist] (int64 device arrays, for inspection and for feeding
+ * wlsqm_hip_expert_interpolate's lists); enqueued on `stream` */
+int wlsqm_hip_interp_plan_export(const wlsqm_interp_plan* plan, void* stream, int64_t* I_or_off_dev, int64_t* idx_dev);
+int wlsqm_hip_interp_plan_eval_device(const wlsqm_interp_plan* plan, void* stream, int64_t nfields,
+                                      const double* fi_dev, int64_t fi_stride_field, int64_t fi_stride_model,
+                                      const int32_t* diffs, int ndiff, double* out_dev, int64_t out_stride_field,
+                                      int64_t out_stride_diff);
+int wlsqm_hip_interp_plan_eval_expert(const wlsqm_interp_plan* plan, wlsqm_expert* h, void* stream, const int32_t* diffs,
+                                      int ndiff, double* out_dev, int64_t out_stride_diff);
+int wlsqm_hip_interp_plan_destroy(wlsqm_interp_plan* plan);
+
 /* ---- batched dense solves: wlsqm.utils.lapackdrivers (lapackdrivers.pyx, the m* / *factor* families) ----
  * `count` independent problems in the reference's layout, Fortran order throughout: A is (n, n, nlhs) with element
  * (i, j, k) at A[i + n*j + n*n*k]; b is (n, count), ipiv (n, nlhs) int32 with LAPACK's 1-based entries, info one

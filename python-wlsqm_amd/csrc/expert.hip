@@ -93,6 +93,20 @@ static int expert_launch(const wlsqm_expert* h, KParams p, hipStream_t s) {
     return WLSQM_OK;
 }
 
+namespace wlsqm {
+
+int expert_view(const wlsqm_expert* h, ExpertView* v) {
+    if (!h || !v) { set_error("null argument"); return WLSQM_EVALUE; }
+    const wlsqm_expert_geometry& g = *h->g;
+    v->device = g.device; v->dimension = g.dimension; v->nmodels = g.ncases;
+    v->xi = g.d_xi.as<double>(); v->order = g.d_order.as<int>();
+    v->ready = g.ready; v->solved = h->solved;
+    v->fi = h->fi_view; v->sfi = h->fi_view_stride;
+    return WLSQM_OK;
+}
+
+}  // namespace wlsqm
+
 extern "C" {
 
 int wlsqm_hip_expert_create(wlsqm_expert** out, int device, int dimension, int64_t ncases,

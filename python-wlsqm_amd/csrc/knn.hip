@@ -20,15 +20,10 @@
 #include <hipcub/hipcub.hpp>
 
 #include "wlsqm_dispatch.hpp"
+#include "wlsqm_grid.hpp"
 #include "wlsqm_interp.hpp"
 
 namespace wlsqm {
-
-struct KnnGrid {
-    double lo[3], inv_cell[3], cell[3];
-    int g[3];
-    int dim;
-};
 
 __device__ __forceinline__ unsigned long long key_of(double v) {      // order-preserving map double -> uint64
     const unsigned long long u = (unsigned long long)__double_as_longlong(v);
@@ -73,11 +68,6 @@ __global__ __launch_bounds__(256) void knn_bbox_kernel(const double* __restrict_
         atomicMin(&mm[m], key_of(lo));
         atomicMax(&mm[3 + m], key_of(hi));
     }
-}
-
-__device__ __forceinline__ int cell_coord(double x, const KnnGrid& G, int m) {
-    int c = (int)((x - G.lo[m]) * G.inv_cell[m]);
-    return c < 0 ? 0 : (c >= G.g[m] ? G.g[m] - 1 : c);
 }
 
 __global__ void knn_cell_kernel(const double* __restrict__ S, long long n, KnnGrid G, unsigned* __restrict__ cell,
@@ -234,15 +224,8 @@ __global__ __launch_bounds__(64) void knn_query_kernel(const double* __restrict_
 
 using namespace wlsqm;
 
-// Uniform grid over a device-resident cloud: bounding box, cells of ~4 points, points sorted by cell.
-struct GridIndex {
-    KnnGrid G{};
-    long long ncells = 1;
-    DevBuf d_perm, d_start, d_Ss;
-    int build(int dimension, int64_t npoints, const double* S, hipStream_t s);
-};
-
-int GridIndex::build(int dimension, int64_t npoints, const double* S, hipStream_t s) {
+// Uniform grid over a device-resident cloud (wlsqm_grid.hpp): bounding box, cells of ~4 points, points sorted by cell.
+int wlsqm::GridIndex::build(int dimension, int64_t npoints, const double* S, hipStream_t s) {
     int rc;
     const long long n = npoints;
     const unsigned blocks = (unsigned)((n + 255) / 256);

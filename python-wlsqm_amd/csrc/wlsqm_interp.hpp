@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "wlsqm_hip.h"
 #include "wlsqm_kernels.hpp"
 
 namespace wlsqm {
@@ -25,6 +26,17 @@ int launch_interp(int dimension, const InterpParams& q, hipStream_t stream);
 // Continuous mode without lists (knn.hip): every evaluation point walks the cells of a uniform grid over the model origins
 // that its ball of radius r touches and averages the models inside.  q.I / q.list_* are ignored.
 int interp_continuous(int dimension, const InterpParams& q, double r, hipStream_t stream);
+
+// What an interpolation plan (interp_plan.hip) needs of a solver (expert.hip): the prepared geometry's packed origins xi[nmodels, dimension]
+// and orders, and the coefficients of the latest solve of any kind (fi, rows sfi apart; null before the first).
+struct ExpertView {
+    int device, dimension;
+    long long nmodels;
+    const double* xi; const int* order;
+    bool ready, solved;
+    const double* fi; long long sfi;
+};
+int expert_view(const wlsqm_expert* h, ExpertView* v);
 
 // value (or derivative q.diff) of model `model` at xp; *d2_out (nullable) receives |xp - xi[model]|^2
 template <int DIM>

@@ -125,6 +125,21 @@ def lib():
                                                C.c_void_p, C.c_double, C.c_int, C.c_void_p]
     L.wlsqm_hip_interpolate_fit_host.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                                  C.c_int64, C.c_int, C.c_void_p, C.c_int]
+    # interpolation plans (wlsqm.hip.InterpolationPlan, ExpertSolver.interpolation_plan)
+    if hasattr(L, "wlsqm_hip_interp_plan_create"):                   # (older builds of the library, as above)
+        L.wlsqm_hip_interp_plan_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64,
+                                                   C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p]
+        L.wlsqm_hip_interp_plan_create_expert.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                                          C.c_int64, C.c_double, C.c_void_p]
+        L.wlsqm_hip_interp_plan_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 4
+        L.wlsqm_hip_interp_plan_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.wlsqm_hip_interp_plan_eval_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                                        C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int64, C.c_int64]
+        L.wlsqm_hip_interp_plan_eval_expert.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p,
+                                                        C.c_int64]
+        L.wlsqm_hip_interp_plan_destroy.argtypes = [C.c_void_p]
+        for name in ("create", "create_expert", "info", "export", "eval_device", "eval_expert", "destroy"):
+            getattr(L, "wlsqm_hip_interp_plan_" + name).restype = C.c_int
     # batched dense solves (wlsqm.utils.lapackdrivers, wlsqm.hip.*_batched)
     for op in ("getrf", "gesv", "sytrf", "sysv"):
         solve = op in ("gesv", "sysv")

@@ -85,9 +85,11 @@ class ExpertSolver:
                 raise RuntimeError("In guest mode, the host ExpertSolver has been closed")
             B.check(B.lib().wlsqm_hip_expert_create_guest(C.byref(h), host._handle, self.algorithm,
                                                           int(self.do_sens), self.max_iter))
+            self._device = host._device
         else:
+            self._device = B.default_device()
             B.check(B.lib().wlsqm_hip_expert_create(
-                C.byref(h), B.default_device(), self.dimension, ncases,
+                C.byref(h), self._device, self.dimension, ncases,
                 np.ascontiguousarray(nk).ctypes.data, np.ascontiguousarray(order).ctypes.data,
                 np.ascontiguousarray(knowns).ctypes.data, np.ascontiguousarray(weighting_method).ctypes.data,
                 self.algorithm, int(self.do_sens), self.max_iter))
@@ -278,6 +280,26 @@ class ExpertSolver:
         B.check(lib.wlsqm_hip_expert_interpolate_continuous(self._handle, xv.ctypes.data, B.es(xv, 0), nx, float(r), int(diff),
                                                             out.ctypes.data))
         return out, np.asanyarray(None)
+
+    def interpolation_plan(self, x, mode='nearest', r=None, I=None, stream=None):
+        """Search once, evaluate many times (extension): a wlsqm.hip.InterpolationPlan of the prepared geometry's models at the
+        points x — (nx, dim) [1D: (nx,)], a float64 device tensor (contiguous last axis, any row stride) or a numpy array, which
+        is uploaded once.  mode, r and I as in interpolate() (I: an int64 device tensor or an array).  Needs prepare(), not
+        prep_interpolate().  ``plan.evaluate(diff)`` then evaluates the latest solve of this solver (or any coefficient tensor
+        passed as fi=) by enqueueing one kernel on a stream: no search, no transfer, no synchronisation, any number of diffs
+        in one launch, legal inside a graph capture behind solve_device()."""
+        if not self.ready:
+            raise RuntimeError("Solver is not in the ready state; prepare() must be called before interpolation_plan()")
+        from .. import hip as whip
+        if isinstance(x, np.ndarray) or (I is not None and not hasattr(I, "data_ptr")):
+            import torch
+            dev = torch.device("cuda", self._device)
+            if isinstance(x, np.ndarray):
+                xv = B.view(x, np.float64, 1 if self.dimension == 1 else 2, "x")
+                x = torch.from_numpy(np.ascontiguousarray(xv)).to(dev)
+            if I is not None and not hasattr(I, "data_ptr"):
+                I = torch.from_numpy(np.ascontiguousarray(np.asarray(I, dtype=np.int64))).to(dev)
+        return whip.InterpolationPlan._for_solver(self, x, mode, r, I, stream)
 
     def solve_device(self, fk, fi, stream=None):
         """Device-resident solve (extension): fk (ncases, max_nk) and fi (ncases, >= no) are torch CUDA tensors

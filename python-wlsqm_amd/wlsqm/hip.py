@@ -13,6 +13,7 @@ from . import _binding as B
 import contextlib
 
 __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_cloud_device", "device_count", "knn", "ball", "nearest",
+           "InterpolationPlan",
            "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
            "getrf_batched", "getrs_batched", "gesv_batched", "sytrf_batched", "sytrs_batched", "sysv_batched", "symmetrize_batched"]
 
@@ -396,6 +397,221 @@ def nearest(S, X, stream=None):
     s, dev = _stream_and_device(S, stream)
     B.check(B.lib().wlsqm_hip_nearest_device(dim, int(S.shape[0]), _ptr(S), int(X.shape[0]), _ptr(X), dim, _ptr(out), dev, s))
     return out
+
+
+# ---- interpolation plans: search once, evaluate many times (csrc/interp_plan.hip) ----
+
+def _diff_list(diff):
+    """(list of int diffs, True when `diff` was a single int)."""
+    if diff is None:
+        raise ValueError("diff cannot be None")
+    if hasattr(diff, "__len__") or hasattr(diff, "__iter__"):
+        diffs = [int(d) for d in diff]
+        if len(diffs) > 35:
+            raise ValueError("at most 35 diffs per call; got %d" % len(diffs))
+        return diffs, False
+    return [int(diff)], True
+
+
+class InterpolationPlan:
+    """Everything about "these models evaluated at these points" that does not depend on the coefficients, computed once and
+    kept on the device (wlsqm_hip_interp_plan_*): packed copies of the origins, the orders and the points, and per point the
+    model (mode='nearest': the nearest origin, ties to the smaller index, or the caller's `I`) or the list of the models within
+    `r` (mode='continuous').  ``evaluate()`` then only enqueues one kernel on a stream, so it can be captured into a graph
+    behind the solve that makes the coefficients.
+
+    xi (nmodels, dim) [1D: (nmodels,)] the origins, `order` an int or an int32 tensor (nmodels,), x (nx, dim) [1D: (nx,)] the
+    evaluation points: float64 device tensors, contiguous last axis, any row stride.  I: int64 device tensor (nx,), nearest mode
+    only; an entry outside 0 .. nmodels - 1 gives NaN at that point.  The constructor synchronises `stream`; the plan keeps no
+    reference to its arguments (and never to a coefficient array)."""
+
+    def __init__(self, xi, order, x, mode='nearest', r=None, I=None, stream=None):
+        self._handle = None
+        self._solver = None
+        dim = self._check_args(None, x, mode, r, I)
+        import torch
+        if xi.dim() not in (1, 2) or (1 if xi.dim() == 1 else int(xi.shape[1])) != dim:
+            raise ValueError("xi must be (nmodels,) or (nmodels, dim) with the coordinates of x; got %s" % (tuple(xi.shape),))
+        _check(xi, "xi", "float64", xi.dim())
+        if xi.dim() == 2 and xi.stride(1) != 1:
+            raise ValueError("Buffer and memoryview are not contiguous in the same dimension. (argument xi)")
+        nmodels = int(xi.shape[0])
+        if nmodels < 1:
+            raise ValueError("xi must hold at least one origin")
+        _same_device(x, xi, I)
+        if hasattr(order, "data_ptr"):
+            _check(order, "order", "int32", 1)
+            _rows(nmodels, order=order)
+            _same_device(x, order)
+            order_t, order_stride = order, int(order.stride(0))
+            self._max_no = _ndofs(dim, int(order[:nmodels].max())) if nmodels else 0
+        else:
+            self._max_no = _ndofs(dim, order)
+            order_t, order_stride = torch.tensor([int(order)], dtype=torch.int32, device=x.device), 0
+        s, dev = _stream_and_device(x, stream)
+        h = C.c_void_p()
+        B.check(B.lib().wlsqm_hip_interp_plan_create(C.byref(h), dev, s, dim, nmodels, _ptr(xi), int(xi.stride(0)), _ptr(order_t),
+                                                     order_stride, self._mode_code, _ptr(x), int(x.stride(0)), int(x.shape[0]),
+                                                     float(r) if r is not None else 0.0, _ptr(I)))
+        self._finish(h, x, dim, nmodels)
+
+    @classmethod
+    def _for_solver(cls, solver, x, mode, r, I, stream):
+        """ExpertSolver.interpolation_plan: the origins and orders are those of the solver's prepared geometry."""
+        import weakref
+        self = cls.__new__(cls)
+        self._handle = None
+        self._solver = None
+        dim = self._check_args(solver.dimension, x, mode, r, I)
+        _same_device(x, I)
+        self._max_no = solver._max_no
+        s, dev = _stream_and_device(x, stream)
+        if dev != solver._device:
+            raise ValueError("x is on device %d, the solver's geometry on device %d" % (dev, solver._device))
+        h = C.c_void_p()
+        B.check(B.lib().wlsqm_hip_interp_plan_create_expert(C.byref(h), solver._handle, s, self._mode_code, _ptr(x), int(x.stride(0)),
+                                                            int(x.shape[0]), float(r) if r is not None else 0.0, _ptr(I)))
+        self._finish(h, x, dim, solver.ncases)
+        self._solver = weakref.ref(solver)
+        return self
+
+    def _check_args(self, dim, x, mode, r, I):
+        if mode not in ('nearest', 'continuous'):
+            raise ValueError("mode must be one of 'nearest', 'continuous'; got '%s'" % (mode,))
+        if mode == 'continuous' and r is None:
+            raise ValueError("r must be specified in mode='continuous'")
+        if mode == 'continuous' and not float(r) > 0.0:
+            raise ValueError("r must be positive; got %r" % (r,))
+        if mode == 'continuous' and I is not None:
+            raise ValueError("'I' names the model of every point in mode='nearest' only")
+        if not hasattr(x, "data_ptr") or not hasattr(x, "is_cuda"):
+            raise ValueError("argument x must be a device (HIP) tensor")
+        if dim is None:
+            dim = 1 if x.dim() == 1 else (int(x.shape[1]) if x.dim() == 2 else 0)
+        if dim not in (1, 2, 3):
+            raise ValueError("x must be (nx,) or (nx, dim) with dim 1..3; got %s" % (tuple(x.shape),))
+        _check(x, "x", "float64", 1 if dim == 1 else 2)
+        if dim > 1 and (int(x.shape[1]) != dim or (x.shape[0] > 0 and x.stride(1) != 1)):
+            raise ValueError("x must be (nx, %d) with a contiguous last axis" % dim)
+        if I is not None:
+            _check(I, "I", "int64", 1)
+            if I.shape[0] != x.shape[0]:
+                raise ValueError("When 'I' is specified, 'I' must have the same length as x; got len(I) = %d, len(x) = %d."
+                                 % (I.shape[0], x.shape[0]))
+            if I.shape[0] > 1 and I.stride(0) != 1:
+                raise ValueError("I must be contiguous")
+        self._mode_code = 0 if mode == 'nearest' else 1
+        self.mode, self.r = mode, (float(r) if mode == 'continuous' else None)
+        return dim
+
+    def _finish(self, h, x, dim, nmodels):
+        self._handle = h
+        self.dimension, self.nmodels, self.nx = dim, int(nmodels), int(x.shape[0])
+        self._device = x.device
+        self._I = None
+
+    def close(self):
+        """Release the device-side state now (also done by __del__); harmless when called again."""
+        if getattr(self, "_handle", None):
+            B.lib().wlsqm_hip_interp_plan_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not getattr(self, "_handle", None):
+            raise RuntimeError("the interpolation plan has been closed")
+        return self._handle
+
+    def _stream(self, stream):
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+        return C.c_void_p(int(stream) if stream else 0)
+
+    def memory_used(self):
+        """Bytes of device memory the plan holds."""
+        b = C.c_int64(0)
+        B.check(B.lib().wlsqm_hip_interp_plan_info(self._live(), None, None, None, C.byref(b)))
+        return int(b.value)
+
+    @property
+    def I(self):
+        """mode='nearest': the model of every point, an int64 device tensor (nx,) (what interpolate() returns as I); else None."""
+        if self.mode != 'nearest':
+            return None
+        if self._I is None:
+            import torch
+            out = torch.empty((self.nx,), dtype=torch.int64, device=self._device)
+            if self.nx > 0:
+                B.check(B.lib().wlsqm_hip_interp_plan_export(self._live(), self._stream(None), _ptr(out), None))
+            self._I = out
+        return self._I
+
+    def lists(self):
+        """mode='continuous': (off, idx), int64 device tensors (nx + 1,) and (number of entries,): the models within r of point m are
+        idx[off[m]:off[m + 1]], in the order of the grid walk (cells in ascending (z, y, x), ascending model number inside a cell)."""
+        if self.mode != 'continuous':
+            raise ValueError("lists() belongs to mode='continuous'; a mode='nearest' plan has I")
+        import torch
+        n = C.c_int64(0)
+        B.check(B.lib().wlsqm_hip_interp_plan_info(self._live(), None, C.byref(n), None, None))
+        off = torch.empty((self.nx + 1,), dtype=torch.int64, device=self._device)
+        idx = torch.empty((int(n.value),), dtype=torch.int64, device=self._device)
+        B.check(B.lib().wlsqm_hip_interp_plan_export(self._handle, self._stream(None), _ptr(off), _ptr(idx) if n.value else None))
+        return off, idx
+
+    def evaluate(self, diff=0, fi=None, out=None, stream=None):
+        """Evaluate the models, or their derivatives `diff` (a DOF number, or a sequence of at most 35), at the plan's points.
+
+        fi (nmodels, >= no) or a stack (R, nmodels, >= no): float64 device tensor(s) of coefficients, contiguous last axis;
+        fi=None: the latest solve of the solver that made the plan.  Returns a device tensor (nx,) for an int `diff`,
+        (ndiff, nx) for a sequence, with a leading axis R for a stack; `out` may be preallocated (that shape, contiguous last
+        axis).  A diff the model does not have gives 0.  Every value is bit-identical whatever else the call asks for.
+        Only enqueues one kernel on `stream` (default: torch's current stream): no allocation when `out` is given, no
+        synchronisation.  Ordering against the solve that writes fi is stream order: evaluate on the stream of the solve."""
+        import torch
+        diffs, single = _diff_list(diff)
+        h = self._live()
+        ndiff = len(diffs)
+        solver = None
+        if fi is None:
+            solver = self._solver() if self._solver is not None else None
+            if solver is None or not getattr(solver, "_handle", None):
+                raise RuntimeError("fi=None evaluates the latest solve of the solver that made the plan; this plan has none (any more)")
+            R, stacked = 1, False
+        else:
+            _check(fi, "fi", "float64", fi.dim() if fi.dim() in (2, 3) else 2)
+            if fi.device != self._device:
+                raise ValueError("all tensors must be on the same device")
+            stacked = fi.dim() == 3
+            R = int(fi.shape[0]) if stacked else 1
+            if fi.shape[-2] < self.nmodels or fi.shape[-1] < self._max_no or (fi.shape[-1] > 1 and fi.stride(-1) != 1):
+                raise ValueError("fi must be (nmodels, >= no) = (%d, >= %d), or a stack of those, with a contiguous last axis; got %s"
+                                 % (self.nmodels, self._max_no, tuple(fi.shape)))
+        shape = ((R,) if stacked else ()) + (() if single else (ndiff,)) + (self.nx,)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=self._device)
+        else:
+            _check(out, "out", "float64", len(shape))
+            if tuple(out.shape) != shape or out.device != self._device or (self.nx > 1 and out.stride(-1) != 1):
+                raise ValueError("out must be a float64 device tensor of shape %s with a contiguous last axis" % (shape,))
+        if self.nx == 0 or ndiff == 0 or R == 0:
+            return out
+        so_f = int(out.stride(0)) if stacked else 0
+        so_d = 0 if single else int(out.stride(1 if stacked else 0))
+        arr = (C.c_int32 * ndiff)(*diffs)
+        s = self._stream(stream)
+        if fi is None:
+            B.check(B.lib().wlsqm_hip_interp_plan_eval_expert(h, solver._handle, s, arr, ndiff, _ptr(out), so_d))
+        else:
+            B.check(B.lib().wlsqm_hip_interp_plan_eval_device(h, s, R, _ptr(fi), int(fi.stride(0)) if stacked else 0,
+                                                              int(fi.stride(-2)), arr, ndiff, _ptr(out), so_f, so_d))
+        return out
 
 
 # ---- batched dense solves (the kernels behind wlsqm.utils.lapackdrivers), device-resident ----
