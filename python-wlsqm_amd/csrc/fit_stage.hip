@@ -28,6 +28,10 @@
 // non-temporal, pieces in a line shared with the next chunk default); 3D order 4's moment halves lost their scratch.  What was measured
 // on the way, and what did not pay: DESIGN section 4.1 (round-5 part), profiles/r05g_ab_stage_dma.txt.
 //
+// The dense 2D systems up to 6 unknowns have the LDS-DMA form too (PART 6: one slot of 12.2 KB, 122 registers, twelve waves per CU), taken by
+// launches whose rows are whole 128-byte lines on line-aligned bases; the form that owns its SIMD (PART 5), the RAGGED copy and every other
+// launch of these systems keep the register-staged code (launch_stage; profiles/stage_c2_dma_occupancy.txt).
+//
 // One sum per moment over k (descending: the chunks are staged last-first, see the kernel) in ONE lane: of the fast kernels this one is
 // the closest to the reference's summation
 // (profiles/r03_attribution.txt: the lane-split sums are the largest single contribution to the fast kernels' distance from it).
@@ -130,6 +134,10 @@ __device__ __forceinline__ void stage_group(const KParams& p, const unsigned grp
     // s_waitcnt vmcnt — all that orders a ds_read behind an LDS-DMA of the same wave (MI355X_MICROARCH.md, co-residence item 7).
 #ifndef WLSQM_STAGE_DMA
 #define WLSQM_STAGE_DMA 18           // bit 0: the systems up to 6 unknowns, 1: 7..10, 2: 11..15, 3: 20, 4: 35
+// (bit 0 stays off: the dense 2D systems up to 6 unknowns get the DMA form as a kernel of its own, PART 6, for the launches it was measured
+// on — rows of whole lines on line-aligned bases, see launch_stage.  With the skewed image one slot is enough there: BASELINE configs[1]
+// 0.1524 ms register-staged, 0.132-0.134 with one slot at 2 / 3 / 4 waves per SIMD compiled for, 0.149-0.151 with two slots (25 KB per wave:
+// six waves per CU); every transfer non-temporal 0.182-0.184 / 0.157-0.159: profiles/stage_c2_dma_occupancy.txt.)
 #endif
 #ifndef WLSQM_STAGE_DMA_NT
 #define WLSQM_STAGE_DMA_NT 0        // the transfers with the non-temporal policy
@@ -145,11 +153,14 @@ __device__ __forceinline__ void stage_group(const KParams& p, const unsigned grp
 #ifndef WLSQM_STAGE_DMA_SLOTS10
 #define WLSQM_STAGE_DMA_SLOTS10 1    // ... of the systems with 7..10 unknowns (two waves per SIMD: 17 KB each)
 #endif
-    constexpr bool DMA = !GATHER && PART != 5 && (((WLSQM_STAGE_DMA) >> (NO <= 6 ? 0 : NO <= 10 ? 1 : NO <= 15 ? 2 : NO <= 20 ? 3 : 4)) & 1);
+    // PART = 6 (2D systems up to 6 unknowns; launch_stage): PART 0 with its chunks by LDS-DMA into ONE slot, whatever the mask says
+    constexpr bool DMA6 = PART == 6;
+    static_assert(!DMA6 || (DIM == 2 && NO <= 6 && !GATHER && RAG != 2), "PART 6: the dense 2D systems up to 6 unknowns");
+    constexpr bool DMA = DMA6 || (!GATHER && PART != 5 && (((WLSQM_STAGE_DMA) >> (NO <= 6 ? 0 : NO <= 10 ? 1 : NO <= 15 ? 2 : NO <= 20 ? 3 : 4)) & 1));
 #ifndef WLSQM_STAGE_DMA_SLOTS35
 #define WLSQM_STAGE_DMA_SLOTS35 2
 #endif
-    constexpr int NSLOT = DMA ? ((NO > 6 && NO <= 10) ? WLSQM_STAGE_DMA_SLOTS10 : NO == 35 ? WLSQM_STAGE_DMA_SLOTS35 : WLSQM_STAGE_DMA_SLOTS) : 1, PF = NSLOT - 1;
+    constexpr int NSLOT = DMA6 ? 1 : DMA ? ((NO > 6 && NO <= 10) ? WLSQM_STAGE_DMA_SLOTS10 : NO == 35 ? WLSQM_STAGE_DMA_SLOTS35 : WLSQM_STAGE_DMA_SLOTS) : 1, PF = NSLOT - 1;
     // SKEW (round 6): instruction i lands at i (1 KiB + 16 B), not at i KiB.  A lane reads ITS case's neighbours with
     // ds_read_b128, and the 16 lanes of a read group (MI355X_MICROARCH.md: {0-3, 12-15, 20-27}, ...) must hit 16 different 16-byte slots of the
     // 256-byte bank row; in the dense KiB image the slot of case c was (12 (c mod 5)) mod 16 (3D: 192-byte chunks, 5 cases per KiB) — four
@@ -859,6 +870,27 @@ static int launch_stage(const KParams& p, hipStream_t stream) {
         // its predecessor).  WLSQM_HIP_STAGE_FORM=two / one forces a form (A/B, tests).
         const char form = env_first("WLSQM_HIP_STAGE_FORM");
         const bool own_simd = (form == 't' || form == 'o') ? form == 'o' : p.rows_sorted == 0;
+        if constexpr (DIM == 2 && NO <= 6) {
+            // THE LDS-DMA FORM of the two-wave form (PART 6) for rows that are whole 128-byte lines on line-aligned bases (the values' rows: K a
+            // multiple of 16, which makes the coordinates' rows whole lines too): a chunk's coordinates are then exactly one line, transferred
+            // non-temporal by the split policy, and its values half a line with the default policy.  BASELINE configs[1] 0.1524 -> 0.132-0.134 ms
+            // (profiles/stage_c2_dma_occupancy.txt).  Other K and bases off a line keep the register-staged kernel: not measured, so not moved.
+            // The form that owns its SIMD and the RAGGED copy keep the register-staged code as well.
+            // WLSQM_HIP_STAGE_DMA6=0: the register-staged kernel for these launches too (A/B, tests); its label is then "stage-reg", as it is
+            // for a launch that is kept off this form by its bases alone.
+            const bool lines = p.max_nk % 16 == 0;
+            const bool based = ((reinterpret_cast<uintptr_t>(p.xk) | reinterpret_cast<uintptr_t>(p.fk)) & 127u) == 0;
+            if (!own_simd && lines) {
+                if (based && env_first("WLSQM_HIP_STAGE_DMA6") != '0') {
+                    if (mark) hipLaunchKernelGGL((fit_stage_kernel<DIM, ORDER, 6, false, 1>), dim3((unsigned)groups), dim3(64), 0, stream, p, status);
+                    else hipLaunchKernelGGL((fit_stage_kernel<DIM, ORDER, 6, false, 0>), dim3((unsigned)groups), dim3(64), 0, stream, p, status);
+                    return finish("stage");
+                }
+                if (mark) hipLaunchKernelGGL((fit_stage_kernel<DIM, ORDER, 0, false, 1>), dim3((unsigned)groups), dim3(64), 0, stream, p, status);
+                else hipLaunchKernelGGL((fit_stage_kernel<DIM, ORDER, 0, false, 0>), dim3((unsigned)groups), dim3(64), 0, stream, p, status);
+                return finish("stage-reg");
+            }
+        }
         if (mark) {
             if (own_simd) hipLaunchKernelGGL((fit_stage_kernel<DIM, ORDER, 5, false, 1>), dim3((unsigned)groups), dim3(64), 0, stream, p, status);
             else hipLaunchKernelGGL((fit_stage_kernel<DIM, ORDER, 0, false, 1>), dim3((unsigned)groups), dim3(64), 0, stream, p, status);

@@ -30,6 +30,7 @@ namespace wlsqm {
 //   WLSQM_HIP_STAGE_GATHER           A/B   =0 | =a           the same for index-based input (fit_stage.hip)
 //   WLSQM_HIP_STAGE_RAGGED           A/B   =0                never the RAGGED copy of the staged kernel (fit_stage.hip)
 //   WLSQM_HIP_STAGE_FORM             A/B   =t | =o           two waves per SIMD / one wave that owns its SIMD, whatever the order hint says (fit_stage.hip)
+//   WLSQM_HIP_STAGE_DMA6             A/B   =0                dense 2D systems up to 6 unknowns, rows of whole 128-byte lines: the register-staged kernel instead of its LDS-DMA form (fit_stage.hip)
 //   WLSQM_HIP_STAGE_INVERSE          A/B   =0                the inverses of dense 2D order 4 from the tile + moment-solve pair again (fit_stage.hip)
 //   WLSQM_HIP_QUAD_SLICE             A/B   integer >= 64     cases per slice of the 3D order-4 moment workspace (tests: small slices; fit_stage.hip)
 //   WLSQM_HIP_STAGE_REFINE           A/B   =0 | =a           refinement: never / every covered shape on the staged kernel (fit_stage_iter.hip)

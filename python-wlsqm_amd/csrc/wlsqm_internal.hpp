@@ -113,7 +113,9 @@ bool accurate_mode();
 bool contracted_mode();
 
 // name of the kernel family the last launch_fit on this thread dispatched to (what wlsqm_hip_last_kernel returns: "stage", "tile1",
-// "sens-apply", "strict", ...: every note_kernel call names one)
+// "sens-apply", "strict", ...: every note_kernel call names one).  "stage-reg" is the register-staged kernel that "stage" names too, said
+// of a launch whose rows have the LDS-DMA form (launch_stage, fit_stage.hip: dense 2D, up to 6 unknowns, K a multiple of 16) and that was
+// kept off it, by a base off a 128-byte line or by WLSQM_HIP_STAGE_DMA6=0: the label tells a caller that its buffers cost it the faster form.
 const char* last_kernel_name();
 void note_kernel(const char* name);
 
