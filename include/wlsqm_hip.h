@@ -187,6 +187,38 @@ int wlsqm_hip_fit_cloud_device(int dimension, int order, int64_t ncases, int64_t
                                double* sens, int64_t sens_stride_case, int64_t sens_stride_k, int do_sens,
                                int iterative, int max_iter, int device, void* stream, int32_t* iterations_out);
 
+/* ---- the adjoint of the fit (extension; csrc/fit_adjoint.hip) ----
+ * The fit is a linear map of its data (fk and the known entries of fi); these two functions apply its transpose.  Given
+ * g[j * g_stride_case + a] = dL/dfi_out[j, a] for the number_of_dofs(dimension, order) DOFs of every case, they write
+ *   grad_fk[j * gfk_stride_case + k * gfk_stride_k] = dL/dfk[j, k] for EVERY k < max_nk: exact zeros for nk[j] <= k (the caller's
+ *     buffer may hold anything), and a whole row of zeros for a case with every DOF known (the fit's no-op);
+ *   grad_fi[j * gfi_stride_case + a] = dL/dfi_in[j, a]: g[j, a] minus the fit's dependence on that value for a true known, g[j, a] for a
+ *     DOF dropped by stray high mask bits (it leaves the fit as it came in), 0 for an unknown (its incoming value is never read).
+ *     grad_fi may be NULL (not wanted), and may alias g: each case reads its row of g before it writes.
+ * Of `b` the geometry is read — dimension, ncases, xk, nk, xi, knowns, weighting_method, max_nk with their strides; b->fk, b->fi,
+ * b->sens and b->order are NOT read (the Jacobian depends on the geometry, the weights and the mask only) and may be NULL;
+ * b->iterative and b->do_sens must be 0 (WLSQM_EVALUE: the refinement's stop test is data-dependent, it has no adjoint here).
+ * order_uniform, case_index / nsel, device and stream as for wlsqm_hip_fit_many_device.  Nothing but one kernel launch: no
+ * allocation, no host synchronisation, no state; it can be captured into a hipGraph.  The arithmetic is always the fast kernels'
+ * (FMA, LDL^T), whatever the calling thread's numerics mode: the four modes round the same linear map differently.
+ * 1D orders 0-4, 2D orders 0-4, 3D orders 0-2; 3D orders 3 and 4: WLSQM_EVALUE, "fit_adjoint: unsupported (dimension, order)". */
+int wlsqm_hip_fit_adjoint_device(const wlsqm_batch* b, int device, void* stream, int order_uniform,
+                                 const double* g, int64_t g_stride_case,
+                                 double* grad_fk, int64_t gfk_stride_case, int64_t gfk_stride_k,
+                                 double* grad_fi, int64_t gfi_stride_case,
+                                 const int64_t* case_index, int64_t nsel);
+
+/* The same for index-based input: the geometry arguments of wlsqm_hip_fit_cloud_device (F, fi, sens and the refinement are not
+ * part of it).  grad_slots[j * gs_stride_case + k] = dL/dF[hoods[j, k]] contributed by case j, for every k < max_nk (zeros from
+ * nk[j] on; the padding of a hoods row is never dereferenced); summing the slots into dL/dF (npoints) is the caller's scatter.
+ * g, grad_fi (nullable, may alias g) as above. */
+int wlsqm_hip_fit_cloud_adjoint_device(int dimension, int order, int64_t ncases, int64_t max_nk,
+                                       const double* S, const int32_t* hoods, int64_t hoods_stride_case,
+                                       const int32_t* point_index, const int32_t* nk, const int64_t* knowns,
+                                       const int32_t* weighting_method,
+                                       const double* g, int64_t g_stride_case, double* grad_slots, int64_t gs_stride_case,
+                                       double* grad_fi, int64_t gfi_stride_case, int device, void* stream);
+
 /* ---- ExpertSolver (expert.pyx:66-781): handle-based prepare-once / solve-many ---- */
 typedef struct wlsqm_expert wlsqm_expert;
 

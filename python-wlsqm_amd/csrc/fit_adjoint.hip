@@ -1,0 +1,299 @@
+// fit_adjoint.hip — the adjoint (vector-Jacobian product) of the WLSQM fit for gfx950 (wave64); DESIGN.md section 12.
+//
+// The fit is a linear map of its data: fi_U = M_UU^-1 (sum_k w_k fk_k c_{k,U} - M_{U,Kn} fi_Kn), U the unknowns, Kn the true knowns,
+// D the DOFs dropped by stray high mask bits (effective_mask, wlsqm_kernels.hpp).  Given gbar = dL/dfi_out (n, no) the adjoint is
+//   y_U = M_UU^-1 gbar_U (M is symmetric; y = 0 outside U),
+//   grad_fk[k] = w_k (c_k . y) for k < nk and exactly 0 for nk <= k < K,
+//   grad_fi[a] = gbar[a] - sum_k c_k[a] grad_fk[k] for a in Kn (= gbar[a] - (M y)[a]: no column of M has to survive the factorisation),
+//                gbar[a] for a in D, 0 for a in U,
+// and a case with every DOF known (the fit's no-op) has grad_fk = 0, grad_fi = gbar.  Neither fk nor the values in fi enter.
+// One __device__ routine, adjoint_case, holds this arithmetic (the fast kernels': moment-free accumulate, FMA, LDL^T) and two kernels
+// call it with their own row access, so a case's bits do not depend on the form that ran it:
+//   "adjoint-lane": one lane per case, arbitrary strides, dense or index-based rows (the row access of fit_lane.hip), case_index;
+//   "adjoint-rows": a wave owns 64 consecutive cases of dense rows: the lanes copy the wave's contiguous run of xk into LDS with 16-byte
+//                   loads at an odd pitch, both passes read it from there (HBM is read once), grad_fk is written into the image
+//                   (slot k * DIM of a row is dead once pass two has read neighbour k) and leaves as the wave's contiguous run.
+#include "wlsqm_dispatch.hpp"
+#include "wlsqm_kernels.hpp"
+
+namespace wlsqm {
+
+constexpr int ADJ_BLOCK = 64;                       // one wave per workgroup, as fit_lane.hip
+constexpr size_t ADJ_LDS_BUDGET = 80 * 1024;        // per wave: at least two waves resident on a CU's 160 KiB
+
+// Row access of the lane form: dense (xk rows with strides) or index-based (hoods row into S); grad_fk rows with strides.
+template <int DIM>
+struct AdjLaneRows {
+    const double* xr; long long sxk_k;
+    const int* hr; const double* S;                 // hr != nullptr: index-based
+    double* out; long long sout_k;
+    __device__ __forceinline__ void offset(int k, const double (&xi)[DIM], double (&d)[DIM]) const {
+        const double* q = hr ? S + (long long)hr[k] * DIM : xr + k * sxk_k;
+#pragma unroll
+        for (int m = 0; m < DIM; ++m) d[m] = q[m] - xi[m];
+    }
+    __device__ __forceinline__ void put(int k, double v) const { out[k * sout_k] = v; }
+};
+
+// Row access of the rows form: the case's row of the wave's LDS image; grad_fk[k] overwrites the first coordinate of neighbour k.
+template <int DIM>
+struct AdjLdsRows {
+    double* row;
+    __device__ __forceinline__ void offset(int k, const double (&xi)[DIM], double (&d)[DIM]) const {
+#pragma unroll
+        for (int m = 0; m < DIM; ++m) d[m] = row[k * DIM + m] - xi[m];
+    }
+    __device__ __forceinline__ void put(int k, double v) const { row[k * DIM] = v; }
+};
+
+// M += w c c^T (upper triangle): accumulate() of wlsqm_kernels.hpp without its right-hand side, the fused operation spelled out
+template <int N>
+__device__ __forceinline__ void accumulate_matrix(double (&M)[N * (N + 1) / 2], const double (&c)[N], double w) {
+    double t[N];
+#pragma unroll
+    for (int a = 0; a < N; ++a) t[a] = (a == 0) ? w : w * c[a];   // c[0] == 1
+#pragma unroll
+    for (int b = 0; b < N; ++b) M[tri<N>(0, b)] += t[b];
+#pragma unroll
+    for (int a = 1; a < N; ++a)
+#pragma unroll
+        for (int b = a; b < N; ++b) M[tri<N>(a, b)] = fma(t[a], c[b], M[tri<N>(a, b)]);
+}
+
+// The adjoint of one case.  grow: the case's gbar row (read in full before anything is written: it may alias gfi); gfi: nullable.
+// K: neighbour slots of the row (nk <= K); rows.put(k, .) receives grad_fk[k] for every k < K.
+template <int DIM, int ORDER, class Rows>
+__device__ __forceinline__ void adjoint_case(const Rows& rows, const double (&xi)[DIM], int nk, int K, bool uniform,
+                                             unsigned long long known, unsigned long long dropped, const double* grow, double* gfi) {
+    constexpr int NO = ndofs(DIM, ORDER);
+    constexpr int NE = NO * (NO + 1) / 2;
+    constexpr unsigned long long FULL = (1ull << NO) - 1ull;
+    double gb[NO], y[NO];
+#pragma unroll
+    for (int a = 0; a < NO; ++a) { gb[a] = grow[a]; y[a] = gb[a]; }
+    if (known == FULL) {                            // nothing to solve: the fit leaves fi as it came in
+        for (int k = 0; k < K; ++k) rows.put(k, 0.0);
+        if (gfi) {
+#pragma unroll
+            for (int a = 0; a < NO; ++a) gfi[a] = gb[a];
+        }
+        return;
+    }
+    // pass 1: largest squared distance; not needed for uniform weights
+    double max_d2 = 0.0;
+    if (!uniform) {
+        for (int k = 0; k < nk; ++k) {
+            double d[DIM];
+            rows.offset(k, xi, d);
+            double d2 = d[0] * d[0];
+            if constexpr (DIM >= 2) d2 += d[1] * d[1];
+            if constexpr (DIM == 3) d2 += d[2] * d[2];
+            if (d2 > max_d2) max_d2 = d2;
+        }
+    }
+    const double inv_max = inverse_max(max_d2);
+    // pass 2: M = C^T W C (upper triangle)
+    double M[NE];
+#pragma unroll
+    for (int e = 0; e < NE; ++e) M[e] = 0.0;
+    for (int k = 0; k < nk; ++k) {
+        double d[DIM], c[NO];
+        rows.offset(k, xi, d);
+        const double d2 = monomials<DIM, ORDER>(d, c);
+        accumulate_matrix<NO>(M, c, weight(d2, inv_max, uniform));
+    }
+    // knowns: rows and columns masked to identity, their entries of the right-hand side zeroed (the values are zero: nothing moves)
+    {
+        double zero[NO];
+#pragma unroll
+        for (int a = 0; a < NO; ++a) zero[a] = 0.0;
+        eliminate_knowns<NO>(M, y, known, zero);
+    }
+    ldlt_factor<NO>(M);
+    ldlt_solve<NO>(M, y);                           // y_U = M_UU^-1 gbar_U, y = 0 outside U
+    // pass 3: grad_fk[k] = w_k (c_k . y); the true knowns' columns collect sum_k c_k[a] grad_fk[k] = (M y)[a]
+    const bool sums = gfi != nullptr && (known & ~dropped) != 0ull;
+    double acc[NO];
+#pragma unroll
+    for (int a = 0; a < NO; ++a) acc[a] = 0.0;
+    for (int k = 0; k < nk; ++k) {
+        double d[DIM], c[NO];
+        rows.offset(k, xi, d);
+        const double d2 = monomials<DIM, ORDER>(d, c);
+        const double w = weight(d2, inv_max, uniform);
+        double s = y[0];
+#pragma unroll
+        for (int a = 1; a < NO; ++a) s = fma(c[a], y[a], s);
+        const double gk = w * s;
+        rows.put(k, gk);
+        if (sums) {
+            acc[0] += gk;
+#pragma unroll
+            for (int a = 1; a < NO; ++a) acc[a] = fma(c[a], gk, acc[a]);
+        }
+    }
+    for (int k = nk; k < K; ++k) rows.put(k, 0.0);  // the padding of a ragged row: exact zeros
+    if (gfi) {
+#pragma unroll
+        for (int a = 0; a < NO; ++a) {
+            double v = 0.0;                                          // an unknown's incoming value is never read by the fit
+            if ((known >> a) & 1ull) v = ((dropped >> a) & 1ull) ? gb[a] : gb[a] - acc[a];
+            gfi[a] = v;
+        }
+    }
+}
+
+template <int DIM, int ORDER>
+__global__ __launch_bounds__(ADJ_BLOCK) void adjoint_lane_kernel(const KParams p, const AdjointArgs q) {
+    constexpr int NO = ndofs(DIM, ORDER);
+    const long long t = (long long)blockIdx.x * ADJ_BLOCK + threadIdx.x;
+    if (t >= live_cases(p)) return;
+    const long long j = p.case_index ? p.case_index[t] : t;
+    const int K = (int)p.max_nk;
+    const int nk = max(min(p.nk[j * p.snk], K), 0);                   // never past the end of a row
+    const bool uniform = (p.wm[j * p.swm] == WLSQM_WEIGHT_UNIFORM);
+    unsigned long long known, dropped;
+    effective_mask<NO>(p.knowns[j * p.sknowns], known, dropped);
+    double xi[DIM];
+    AdjLaneRows<DIM> rows;
+    double* out = q.gfk + j * q.sgfk_j;
+    if (p.hoods) {
+        const long long pj = own_point(p, j);
+#pragma unroll
+        for (int m = 0; m < DIM; ++m) xi[m] = p.S[pj * DIM + m];
+        rows = AdjLaneRows<DIM>{nullptr, 0, p.hoods + j * p.shoods_j, p.S, out, q.sgfk_k};
+    } else {
+#pragma unroll
+        for (int m = 0; m < DIM; ++m) xi[m] = p.xi[j * p.sxi_j + m];
+        rows = AdjLaneRows<DIM>{p.xk + j * p.sxk_j, p.sxk_k, nullptr, nullptr, out, q.sgfk_k};
+    }
+    adjoint_case<DIM, ORDER>(rows, xi, nk, K, uniform, known, dropped, q.g + j * q.sg_j, q.gfi ? q.gfi + j * q.sgfi_j : nullptr);
+}
+
+// Copies between the wave's contiguous global run of `rows` rows of `len` doubles and its LDS image (row r at r * pitch, element e of
+// a global row at LDS offset e * step).  16-byte pieces, a lane's position (row, element) advanced without a division per piece; a run of
+// an odd number of doubles (odd len and odd rows) ends in one 8-byte piece.  The run's base is 16-byte aligned: the launcher checked the
+// buffer's base, and a wave's offset into it is 64 rows.
+template <bool TO_LDS>
+__device__ __forceinline__ void adjoint_copy_run(double* lds, int pitch, int step, double* run, int rows, int len) {
+    const int total = rows * len;                                    // doubles; at most 64 rows of an image below ADJ_LDS_BUDGET
+    const int pairs = total >> 1;
+    const int lane = threadIdx.x;
+    int r = (2 * lane) / len, e = (2 * lane) % len;
+    const int qs = (2 * ADJ_BLOCK) / len, rs = (2 * ADJ_BLOCK) % len;
+    double2* run2 = reinterpret_cast<double2*>(run);
+#pragma unroll 4
+    for (int i = lane; i < pairs; i += ADJ_BLOCK) {
+        int r1 = r, e1 = e + 1;
+        if (e1 == len) { e1 = 0; ++r1; }
+        if constexpr (TO_LDS) {
+            const double2 v = run2[i];
+            lds[r * pitch + e * step] = v.x;
+            lds[r1 * pitch + e1 * step] = v.y;
+        } else {
+            double2 v;
+            v.x = lds[r * pitch + e * step];
+            v.y = lds[r1 * pitch + e1 * step];
+            run2[i] = v;
+        }
+        e += rs; r += qs;
+        if (e >= len) { e -= len; ++r; }
+    }
+    if ((total & 1) && lane == 0) {
+        const int i = total - 1;
+        if constexpr (TO_LDS) lds[(i / len) * pitch + (i % len) * step] = run[i];
+        else run[i] = lds[(i / len) * pitch + (i % len) * step];
+    }
+}
+
+template <int DIM, int ORDER>
+__global__ __launch_bounds__(ADJ_BLOCK) void adjoint_rows_kernel(const KParams p, const AdjointArgs q, int pitch) {
+    constexpr int NO = ndofs(DIM, ORDER);
+    extern __shared__ double adj_lds[];
+    const long long j0 = (long long)blockIdx.x * ADJ_BLOCK;
+    const int K = (int)p.max_nk;
+    const long long left = p.ncases - j0;
+    const int ncw = left < ADJ_BLOCK ? (int)left : ADJ_BLOCK;          // the tail group has fewer than 64 cases
+    adjoint_copy_run<true>(adj_lds, pitch, 1, const_cast<double*>(p.xk) + j0 * K * DIM, ncw, K * DIM);
+    __syncthreads();
+    if ((int)threadIdx.x < ncw) {
+        const long long j = j0 + threadIdx.x;
+        const int nk = max(min(p.nk[j * p.snk], K), 0);
+        const bool uniform = (p.wm[j * p.swm] == WLSQM_WEIGHT_UNIFORM);
+        unsigned long long known, dropped;
+        effective_mask<NO>(p.knowns[j * p.sknowns], known, dropped);
+        double xi[DIM];
+#pragma unroll
+        for (int m = 0; m < DIM; ++m) xi[m] = p.xi[j * p.sxi_j + m];
+        const AdjLdsRows<DIM> rows{adj_lds + (int)threadIdx.x * pitch};
+        adjoint_case<DIM, ORDER>(rows, xi, nk, K, uniform, known, dropped, q.g + j * q.sg_j, q.gfi ? q.gfi + j * q.sgfi_j : nullptr);
+    }
+    __syncthreads();
+    adjoint_copy_run<false>(adj_lds, pitch, DIM, q.gfk + j0 * K, ncw, K);
+}
+
+// LDS pitch of a row of `len` doubles: odd, so that the 32 lanes of a ds_read_b64 lane group, one row each, hit 32 different bank pairs
+static int adjoint_pitch(long long len) { return (int)(len | 1); }
+
+// The rows form takes dense rows of xk and of grad_fk (dense_rows: contiguous at a pitch of K slots, bases 16-byte aligned), every
+// case of the batch in order, and an image of 64 rows within the LDS budget.
+static bool adjoint_rows_eligible(int dim, const KParams& p, const AdjointArgs& q, long long K) {
+    if (p.hoods || p.case_index || p.ncases_dev || !p.xk || K < 1) return false;
+    KParams t = p;
+    t.fk = q.gfk; t.sfk_j = q.sgfk_j; t.sfk_k = q.sgfk_k;          // grad_fk has fk's layout
+    if (!dense_rows(dim, t, K)) return false;
+    return (size_t)adjoint_pitch(K * dim) * ADJ_BLOCK * sizeof(double) <= ADJ_LDS_BUDGET;
+}
+
+// Which form runs when WLSQM_HIP_ADJOINT_FORM is unset: the one that measured faster for the shape (1M cases, one
+// MI355X, rows / lane): 2D order 2 at 32 neighbours 0.305 / 1.46 ms, 3D order 2 at 40 0.94 / 1.45, 1D order 2 at 8 (4M cases) 0.15 / 0.56,
+// but 2D order 4 at 64 1.91 / 1.56: the 15-unknown system's 469 registers leave the rows form one wave per SIMD with nothing to hide
+// its LDS latency behind, and the lane form's second and third passes find their rows in L2.  So: the systems up to 10 unknowns.
+static bool adjoint_rows_default(int dimension, int order) {
+    return wlsqm_hip_number_of_dofs(dimension, order) <= 10;
+}
+
+template <int DIM, int ORDER>
+static int launch_adjoint(const KParams& p, const AdjointArgs& q, bool rows, hipStream_t stream) {
+    const long long blocks = (p.ncases + ADJ_BLOCK - 1) / ADJ_BLOCK;
+    if (blocks <= 0) return WLSQM_OK;
+    if (blocks > 0x7fffffffLL) { set_error("too many cases for one launch"); return WLSQM_EVALUE; }
+    if (rows) {
+        const int pitch = adjoint_pitch(p.max_nk * DIM);
+        const size_t lds = (size_t)pitch * ADJ_BLOCK * sizeof(double);
+        if (lds > 64 * 1024) {                                       // the opt-in to more than 64 KiB of dynamic LDS, once per device
+            static bool opted[16] = {};
+            int dev = 0;
+            WLSQM_HIP_CHECK(hipGetDevice(&dev));
+            if (dev < 0 || dev >= 16) { set_error("device ordinal out of range"); return WLSQM_EVALUE; }
+            if (!opted[dev]) {
+                WLSQM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&adjoint_rows_kernel<DIM, ORDER>),
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)ADJ_LDS_BUDGET));
+                opted[dev] = true;
+            }
+        }
+        hipLaunchKernelGGL((adjoint_rows_kernel<DIM, ORDER>), dim3((unsigned)blocks), dim3(ADJ_BLOCK), lds, stream, p, q, pitch);
+        WLSQM_HIP_CHECK(hipGetLastError());
+        note_kernel("adjoint-rows");
+        return WLSQM_OK;
+    }
+    hipLaunchKernelGGL((adjoint_lane_kernel<DIM, ORDER>), dim3((unsigned)blocks), dim3(ADJ_BLOCK), 0, stream, p, q);
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("adjoint-lane");
+    return WLSQM_OK;
+}
+
+int launch_fit_adjoint(int dimension, int order, const KParams& p, const AdjointArgs& q, hipStream_t stream) {
+    if (p.ncases <= 0) return WLSQM_OK;
+    const char form = env_first("WLSQM_HIP_ADJOINT_FORM");          // =l: the lane form for everything; =r: the rows form wherever eligible
+    const bool rows = form != 'l' && adjoint_rows_eligible(dimension, p, q, p.max_nk) && (form == 'r' || adjoint_rows_default(dimension, order));
+#define CASE(D, O) if (dimension == D && order == O) return launch_adjoint<D, O>(p, q, rows, stream);
+    CASE(1, 0) CASE(1, 1) CASE(1, 2) CASE(1, 3) CASE(1, 4)
+    CASE(2, 0) CASE(2, 1) CASE(2, 2) CASE(2, 3) CASE(2, 4)
+    CASE(3, 0) CASE(3, 1) CASE(3, 2)
+#undef CASE
+    set_error("fit_adjoint: unsupported (dimension, order)");
+    return WLSQM_EVALUE;
+}
+
+}  // namespace wlsqm

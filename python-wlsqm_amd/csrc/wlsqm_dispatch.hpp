@@ -61,6 +61,7 @@ namespace wlsqm {
 //   WLSQM_HIP_SOLVE_MANY             A/B   =f | =o           the stacked solve on the FMA kernel / on the stored-operator MFMA kernel (expert.hip)
 //   WLSQM_HIP_OP_WPG                 A/B   integer           waves per workgroup of the MFMA kernel (solve_op.hip)
 //   WLSQM_HIP_OP_DEBUG               A/B   integer           experiments of that kernel: 1 no stores, 2 only the first block of fields loaded (solve_op.hip)
+//   WLSQM_HIP_ADJOINT_FORM           A/B   =l | =r           the adjoint of the fit: the lane form for every batch / the rows form wherever it is eligible, whatever measured faster for the shape (fit_adjoint.hip)
 
 // first character of the value; '\0' when the switch is unset or empty
 inline char env_first(const char* name) { const char* e = getenv(name); return e ? e[0] : '\0'; }
@@ -164,6 +165,17 @@ int launch_fit_rows_inverse(int dimension, int order, const KParams& p, double* 
 int launch_fit_wave_inverse(int dimension, int order, const KParams& p, double* inv, hipStream_t stream);         // fit_wave.hip
 
 int launch_quad_solve(const KParams& p, hipStream_t stream);                                                      // fit_quad.hip: the solve behind fit_stage.hip's 3D order-4 moments
+
+// The adjoint of the fit (fit_adjoint.hip): what it reads and writes beside the geometry in KParams (xk / hoods + S, nk, xi,
+// knowns, wm, case_index; fk, fi and sens are not read).  g[j * sg_j + a] = dL/dfi_out; gfk[j * sgfk_j + k * sgfk_k] receives dL/dfk for
+// every k < p.max_nk (zeros from nk[j] on); gfi[j * sgfi_j + a] (nullable: not wanted) receives dL/dfi_in and may alias g.
+struct AdjointArgs {
+    const double* g;   long long sg_j;
+    double* gfk;       long long sgfk_j, sgfk_k;
+    double* gfi;       long long sgfi_j;
+};
+// p.max_nk is the extent of the neighbour axis (set by the caller); 3D orders 3-4: WLSQM_EVALUE
+int launch_fit_adjoint(int dimension, int order, const KParams& p, const AdjointArgs& q, hipStream_t stream);
 
 // fit_tile.hip: the tile path's eligibility, for the families that share it
 bool tile_dense_eligible(int dimension, const KParams& p, long long max_nk);                  // dense contiguous input the tile kernels can take

@@ -95,6 +95,14 @@ def lib():
     L.wlsqm_hip_fit_cloud_device.argtypes = cloud + [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                                      C.c_void_p, C.POINTER(C.c_int32)]
     L.wlsqm_hip_time_fit_cloud_device.argtypes = cloud + [C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float)]
+    # the adjoint of the fit (wlsqm.hip.fit_many_adjoint_device, fit_cloud_adjoint_device, differentiable_fit_*)
+    L.wlsqm_hip_fit_adjoint_device.argtypes = [C.POINTER(Batch), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                               C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+    L.wlsqm_hip_fit_adjoint_device.restype = C.c_int
+    L.wlsqm_hip_fit_cloud_adjoint_device.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                     C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+    L.wlsqm_hip_fit_cloud_adjoint_device.restype = C.c_int
     L.wlsqm_hip_expert_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.wlsqm_hip_knn_device.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]

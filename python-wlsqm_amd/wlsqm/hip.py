@@ -13,6 +13,7 @@ from . import _binding as B
 import contextlib
 
 __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_cloud_device", "device_count", "knn", "ball", "nearest",
+           "fit_many_adjoint_device", "fit_cloud_adjoint_device", "differentiable_fit_many", "differentiable_fit_cloud",
            "InterpolationPlan",
            "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
            "getrf_batched", "getrs_batched", "gesv_batched", "sytrf_batched", "sytrs_batched", "sysv_batched", "symmetrize_batched"]
@@ -333,6 +334,240 @@ def time_fit_cloud_device(dimension, order, S, F, hoods, fi, nk, knowns, weighti
     ms = C.c_float(0.0)
     B.check(B.lib().wlsqm_hip_time_fit_cloud_device(*a, dev, s, int(reps), C.byref(ms)))
     return float(ms.value)
+
+
+# ---- the adjoint of the fit: gradients through device-resident fits (csrc/fit_adjoint.hip) ----
+
+def _adjoint_order(dimension, order):
+    if hasattr(order, "data_ptr"):
+        raise ValueError("the adjoint takes an integer order (one polynomial order for the whole batch)")
+    no = _ndofs(dimension, order)
+    if dimension == 3 and int(order) >= 3:
+        raise ValueError("fit_adjoint: unsupported (dimension, order)")
+    return no
+
+
+def _adjoint_rows(t, name, ncases, no):
+    """g / grad_fi: float64 device tensor (>= ncases, >= no), contiguous last axis."""
+    _check(t, name, "float64", 2)
+    if t.stride(1) != 1:
+        raise ValueError("Buffer and memoryview are not contiguous in the same dimension. (argument %s)" % name)
+    _rows(ncases, **{name: t})
+    if t.shape[1] < no:
+        raise ValueError("%s has %d columns, need at least number_of_dofs = %d" % (name, t.shape[1], no))
+
+
+def fit_many_adjoint_device(dimension, order, xk, nk, xi, knowns, weighting_method, g, grad_fk=None, grad_fi=None, case_index=None,
+                            stream=None):
+    """The vector-Jacobian product of fit_many_device (basic fit, integer `order`): given g (n, >= no) = dL/dfi_out, returns
+    (grad_fk, grad_fi) = (dL/dfk (n, K), dL/dfi_in (n, no)).  The fit is linear in fk and in the known entries of fi, so neither
+    enters: the geometry arguments are those of fit_many_device (xk (n, K, dim) [1D: (n, K)], nk, xi, knowns, weighting_method).
+
+    grad_fk[j, k] is exactly 0 for nk[j] <= k; grad_fi[j, a] is g[j, a] minus the fit's dependence on the value for a known DOF, g[j, a]
+    for a DOF dropped by stray high mask bits, 0 for an unknown (its incoming value is never read); a case with every DOF known has
+    grad_fk = 0 and grad_fi = g.  The outputs are allocated when not given (with `case_index`: zero-filled, the kernel writes the
+    selected rows only); grad_fi=False: not wanted (returned as None); grad_fi may be g itself.  One kernel launch on `stream`
+    (default: torch's current stream), no allocation when both outputs are given, no synchronisation: it can be captured.
+    The arithmetic is always the fast kernels' (FMA, LDL^T), whatever numerics mode the forward fit ran in: the modes round the
+    same linear map differently.  3D orders 3 and 4 are not covered (ValueError)."""
+    import torch
+    no = _adjoint_order(dimension, order)
+    ncases = nk.shape[0]
+    _check(nk, "nk", "int32", 1); _check(knowns, "knowns", "int64", 1); _check(weighting_method, "weighting_method", "int32", 1)
+    if dimension == 1:
+        _check(xk, "xk", "float64", 2); _check(xi, "xi", "float64", 1)
+    else:
+        _check(xk, "xk", "float64", 3); _check(xi, "xi", "float64", 2)
+        if xk.stride(2) != 1 or xi.stride(1) != 1:
+            raise ValueError("Buffer and memoryview are not contiguous in the same dimension.")
+        if xk.shape[2] < dimension or xi.shape[1] < dimension:
+            raise ValueError("xk / xi must have %d coordinates on the last axis" % dimension)
+    _rows(ncases, xk=xk, xi=xi, knowns=knowns, weighting_method=weighting_method)
+    _adjoint_rows(g, "g", ncases, no)
+    K = int(xk.shape[1])
+    new = torch.zeros if case_index is not None else torch.empty
+    if grad_fk is None:
+        grad_fk = new((ncases, K), dtype=torch.float64, device=g.device)
+    _check(grad_fk, "grad_fk", "float64", 2)
+    _rows(ncases, grad_fk=grad_fk)
+    if grad_fk.shape[1] < K:
+        raise ValueError("grad_fk has %d neighbour slots per case, xk has %d" % (grad_fk.shape[1], K))
+    if grad_fi is None:
+        grad_fi = new((ncases, no), dtype=torch.float64, device=g.device)
+    elif grad_fi is False:
+        grad_fi = None
+    if grad_fi is not None:
+        _adjoint_rows(grad_fi, "grad_fi", ncases, no)
+    _same_device(g, xk, nk, xi, knowns, weighting_method, grad_fk, grad_fi, case_index)
+    b = B.Batch()
+    b.dimension, b.ncases = dimension, ncases
+    b.xk, b.xk_stride_case, b.xk_stride_k = xk.data_ptr(), xk.stride(0), xk.stride(1)
+    b.nk, b.nk_stride = nk.data_ptr(), nk.stride(0)
+    b.xi, b.xi_stride_case = xi.data_ptr(), xi.stride(0)
+    b.knowns, b.knowns_stride = knowns.data_ptr(), knowns.stride(0)
+    b.weighting_method, b.wm_stride = weighting_method.data_ptr(), weighting_method.stride(0)
+    b.max_nk = K
+    s, dev = _stream_and_device(g, stream)
+    ci, nsel = None, 0
+    if case_index is not None:
+        _check(case_index, "case_index", "int64", 1)
+        ci, nsel = C.c_void_p(case_index.data_ptr()), int(case_index.shape[0])
+    B.check(B.lib().wlsqm_hip_fit_adjoint_device(C.byref(b), dev, s, int(order), _ptr(g), int(g.stride(0)),
+                                                 _ptr(grad_fk), int(grad_fk.stride(0)), int(grad_fk.stride(1)),
+                                                 _ptr(grad_fi), int(grad_fi.stride(0)) if grad_fi is not None else 0, ci, nsel))
+    return grad_fk, grad_fi
+
+
+def fit_cloud_adjoint_device(dimension, order, S, hoods, nk, knowns, weighting_method, g, point_index=None, grad_F=None, grad_fi=None,
+                             stream=None, slots=None):
+    """The vector-Jacobian product of fit_cloud_device: given g (ncases, >= no) = dL/dfi_out, returns (grad_F, grad_fi) =
+    (dL/dF (npoints,), dL/dfi_in (ncases, no)).  The kernel runs index-based (xk = S[hoods] is never formed) and writes one gradient
+    per neighbour slot, (ncases, K), exact zeros in the padding of a ragged row; one ``index_add_`` then sums the slots into grad_F
+    (the padding of `hoods` may hold anything: it is never dereferenced by the kernel and is pointed at point 0 for the scatter).
+    grad_F (overwritten) and grad_fi are allocated when not given; grad_fi=False: not wanted; `slots`: a float64 device tensor
+    (ncases, K) that receives the per-slot gradients (allocated otherwise).  Asynchronous on `stream`."""
+    import torch
+    no = _adjoint_order(dimension, order)
+    _check(hoods, "hoods", "int32", 2)
+    _check(S, "S", "float64", 1 if dimension == 1 else 2)
+    _check(nk, "nk", "int32", 1); _check(knowns, "knowns", "int64", 1); _check(weighting_method, "weighting_method", "int32", 1)
+    if not S.is_contiguous() or hoods.stride(1) != 1:
+        raise ValueError("S must be contiguous; hoods must have a contiguous last axis")
+    for t in (nk, knowns, weighting_method):
+        if t.stride(0) != 1:
+            raise ValueError("nk, knowns, weighting_method must have unit stride")
+    ncases, K = int(hoods.shape[0]), int(hoods.shape[1])
+    npoints = int(S.shape[0])
+    _rows(ncases, nk=nk, knowns=knowns, weighting_method=weighting_method)
+    if point_index is not None:
+        _check(point_index, "point_index", "int32", 1)
+        _rows(ncases, point_index=point_index)
+    elif npoints < ncases:
+        raise ValueError("S has %d points but there are %d cases (xi of case j is S[j] without point_index)" % (npoints, ncases))
+    if dimension > 1 and S.shape[1] != dimension:
+        raise ValueError("S must be (npoints, %d)" % dimension)
+    _adjoint_rows(g, "g", ncases, no)
+    if slots is None:
+        slots = torch.empty((ncases, K), dtype=torch.float64, device=g.device)
+    _check(slots, "slots", "float64", 2)
+    if slots.shape[0] < ncases or slots.shape[1] < K or slots.stride(1) != 1:
+        raise ValueError("slots must be at least (ncases, %d) with a contiguous last axis; got %s" % (K, tuple(slots.shape)))
+    if grad_fi is None:
+        grad_fi = torch.empty((ncases, no), dtype=torch.float64, device=g.device)
+    elif grad_fi is False:
+        grad_fi = None
+    if grad_fi is not None:
+        _adjoint_rows(grad_fi, "grad_fi", ncases, no)
+    if grad_F is None:
+        grad_F = torch.zeros((npoints,), dtype=torch.float64, device=g.device)
+    else:
+        _check(grad_F, "grad_F", "float64", 1)
+        if grad_F.shape[0] < npoints:
+            raise ValueError("grad_F has fewer entries than S has points")
+    _same_device(g, S, hoods, nk, knowns, weighting_method, point_index, slots, grad_fi, grad_F)
+    s, dev = _stream_and_device(g, stream)
+    B.check(B.lib().wlsqm_hip_fit_cloud_adjoint_device(int(dimension), int(order), ncases, K, _ptr(S), _ptr(hoods), int(hoods.stride(0)),
+                                                       _ptr(point_index), _ptr(nk), _ptr(knowns), _ptr(weighting_method),
+                                                       _ptr(g), int(g.stride(0)), _ptr(slots), int(slots.stride(0)),
+                                                       _ptr(grad_fi), int(grad_fi.stride(0)) if grad_fi is not None else 0, dev, s))
+    # the scatter: torch ops, on the stream of the kernel
+    ext = torch.cuda.ExternalStream(int(stream), device=g.device) if stream else None
+    with (torch.cuda.stream(ext) if ext is not None else contextlib.nullcontext()):
+        live = torch.arange(K, device=g.device)[None, :] < nk[:ncases, None]
+        idx = torch.where(live, hoods[:ncases].long(), torch.zeros((), dtype=torch.int64, device=g.device))
+        grad_F.zero_()
+        grad_F.index_add_(0, idx.reshape(-1), slots[:ncases, :K].reshape(-1))
+    return grad_F, grad_fi
+
+
+_AUTOGRAD = None
+
+
+def _autograd_functions():
+    """The two torch.autograd.Function classes (made at first use: the module does not import torch)."""
+    global _AUTOGRAD
+    if _AUTOGRAD is not None:
+        return _AUTOGRAD
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    def pass_through(g, ncases, no):
+        """dL/dfi_in starts as a copy of g where fi has rows or columns the fit never touches (they leave as they came in)."""
+        return g.clone() if (g.shape[0] != ncases or g.shape[1] != no) else None
+
+    class FitMany(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, fk, fi, dimension, order, xk, nk, xi, knowns, weighting_method, strict, stream):
+            out = fi.detach().clone()
+            fit_many_device(dimension, order, xk, fk.detach(), nk, xi, out, knowns, weighting_method, strict=strict, stream=stream)
+            ctx.geometry = (dimension, order, xk, nk, xi, knowns, weighting_method, stream, tuple(fk.shape))
+            return out
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gout):
+            dimension, order, xk, nk, xi, knowns, weighting_method, stream, fk_shape = ctx.geometry
+            need_fk, need_fi = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if not (need_fk or need_fi):
+                return (None,) * 11
+            g = gout.contiguous()
+            ncases, K, no = int(nk.shape[0]), int(fk_shape[1]), _ndofs(dimension, order)
+            gfk = (torch.zeros if fk_shape[0] != ncases else torch.empty)(fk_shape, dtype=torch.float64, device=g.device)
+            gfi = pass_through(g, ncases, no) if need_fi else False
+            _, gfi = fit_many_adjoint_device(dimension, order, xk[:, :K], nk, xi, knowns, weighting_method, g, grad_fk=gfk,
+                                             grad_fi=gfi, stream=stream)
+            return (gfk if need_fk else None, gfi if need_fi else None) + (None,) * 9
+
+    class FitCloud(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, F, fi, dimension, order, S, hoods, nk, knowns, weighting_method, point_index, strict, stream):
+            out = fi.detach().clone()
+            fit_cloud_device(dimension, order, S, F.detach(), hoods, out, nk, knowns, weighting_method, point_index=point_index,
+                             strict=strict, stream=stream)
+            ctx.geometry = (dimension, order, S, hoods, nk, knowns, weighting_method, point_index, stream, tuple(F.shape))
+            return out
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gout):
+            dimension, order, S, hoods, nk, knowns, weighting_method, point_index, stream, F_shape = ctx.geometry
+            need_F, need_fi = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if not (need_F or need_fi):
+                return (None,) * 12
+            g = gout.contiguous()
+            gF = torch.empty(F_shape, dtype=torch.float64, device=g.device)
+            gfi = pass_through(g, int(hoods.shape[0]), _ndofs(dimension, order)) if need_fi else False
+            _, gfi = fit_cloud_adjoint_device(dimension, order, S, hoods, nk, knowns, weighting_method, g, point_index=point_index,
+                                              grad_F=gF, grad_fi=gfi, stream=stream)
+            return (gF if need_F else None, gfi if need_fi else None) + (None,) * 10
+
+    _AUTOGRAD = (FitMany, FitCloud)
+    return _AUTOGRAD
+
+
+def _no_geometry_grad(*tensors):
+    for t in tensors:
+        if t is not None and getattr(t, "requires_grad", False):
+            raise ValueError("the geometry is not differentiable")
+
+
+def differentiable_fit_many(dimension, order, xk, fk, nk, xi, fi, knowns, weighting_method, strict=None, stream=None):
+    """fit_many_device as a differentiable function of fk and fi: returns fi_out, a NEW tensor (fi is cloned, the fit runs in place on
+    the clone), through which autograd reaches fk and fi (the basic fit, integer `order`; refinement is not offered: its stop test
+    is data-dependent).  The backward pass is fit_many_adjoint_device: one kernel, computed only for the inputs that require a gradient;
+    it always runs the fast arithmetic, whatever `strict` the forward used.  The geometry (xk, xi) is not differentiable:
+    ValueError when it requires a gradient.  Once differentiable."""
+    _adjoint_order(dimension, order)
+    _no_geometry_grad(xk, xi)
+    return _autograd_functions()[0].apply(fk, fi, dimension, int(order), xk, nk, xi, knowns, weighting_method, strict, stream)
+
+
+def differentiable_fit_cloud(dimension, order, S, F, hoods, fi, nk, knowns, weighting_method, point_index=None, strict=None, stream=None):
+    """fit_cloud_device as a differentiable function of the field F (npoints,) and of fi: returns fi_out, a new tensor.  The backward
+    pass is fit_cloud_adjoint_device (index-based kernel + one index_add_ into dL/dF).  S is not differentiable (ValueError)."""
+    _adjoint_order(dimension, order)
+    _no_geometry_grad(S)
+    return _autograd_functions()[1].apply(F, fi, dimension, int(order), S, hoods, nk, knowns, weighting_method, point_index, strict, stream)
 
 
 def knn(S, k, stream=None, nquery=None):
