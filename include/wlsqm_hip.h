@@ -296,6 +296,22 @@ int wlsqm_hip_expert_solve_many_device(wlsqm_expert* h, void* stream, int64_t nr
 int wlsqm_hip_expert_solve_many(wlsqm_expert* h, int64_t nrhs,
                                 const double* fk, int64_t fk_stride_rhs, int64_t fk_stride_case, int64_t fk_stride_k,
                                 double* fi, int64_t fi_stride_rhs, int64_t fi_stride_case);
+/* Extension: the adjoint (vector-Jacobian product) of wlsqm_hip_expert_solve_many_device on the prepared geometry (csrc/solve_op.hip,
+ * csrc/fit_adjoint.hip).  g[nrhs][ncases][g_stride_case] = dL/dfi_out (device, DOF axis contiguous).  Writes
+ * grad_fk[r][j][k] = dL/dfk for EVERY k < gfk_slots (gfk_slots >= max(nk); exact zeros from nk[j] on and for a case with every DOF
+ * known) and, when grad_fi is not NULL, grad_fi[r][j][a] = dL/dfi_in for every a < no[j] (0 for an unknown, g for a DOF dropped by
+ * stray high mask bits, g minus the fit's dependence on the value for a known DOF; columns beyond no[j] are untouched).  g, grad_fk
+ * and grad_fi must not overlap.  Two routes to the same numbers: the stored operator's transpose as one batched GEMM on the matrix
+ * cores (wlsqm_hip_last_kernel(): "solve-op-adjoint-mfma"; the shapes of wlsqm_hip_expert_prepare_operator, grad_fk 16-byte aligned
+ * with even strides and an even gfk_slots), or one adjoint of the fit per field on the resident geometry (every other case; mixed
+ * orders in buckets).  The operator is built on demand as for the stacked solve (that call synchronises `stream`) but never while
+ * `stream` is capturing; with the operator present the call only enqueues kernels.  Always the fast arithmetic, whatever the
+ * numerics mode.  WLSQM_ERUNTIME before prepare(); WLSQM_EVALUE for an ALGO_ITERATIVE solver (the stop test is data-dependent) and
+ * for 3D orders 3 and 4 ("fit_adjoint: unsupported (dimension, order)"). */
+int wlsqm_hip_expert_solve_adjoint_device(wlsqm_expert* h, void* stream, int64_t nrhs,
+                                          const double* g, int64_t g_stride_rhs, int64_t g_stride_case,
+                                          double* grad_fk, int64_t gfk_stride_rhs, int64_t gfk_stride_case, int64_t gfk_slots,
+                                          double* grad_fi /* nullable */, int64_t gfi_stride_rhs, int64_t gfi_stride_case);
 /* expert.pyx:429-464 conds(): 2-norm condition number of the Ruiz-scaled reduced matrix of every case
  * (impl.pyx:662-682), out[ncases] on the host.  Diagnostics path (one-sided Jacobi SVD per case). */
 int wlsqm_hip_expert_conds(wlsqm_expert* h, double* out);

@@ -402,6 +402,95 @@ int wlsqm_hip_expert_solve_many_device(wlsqm_expert* h, void* stream, int64_t nr
     return rc;
 }
 
+// The adjoint of solve_many_device (extension).  Two routes to the same numbers: the stored operator's
+// transpose as one batched GEMM (solve_op.hip), or per field one adjoint of the fit on the resident geometry (fit_adjoint.hip: the
+// definition, every shape it serves).  WLSQM_HIP_SOLVE_ADJOINT = "g" / "o" forces one; unset, the operator from the stack size at
+// which it measured faster (profiles/solve_adjoint_timings.json).  Always the fast arithmetic, whatever the numerics mode.
+static int solve_adjoint_choice() {
+    const char c = env_first("WLSQM_HIP_SOLVE_ADJOINT");
+    return c == 'g' ? 1 : c == 'o' ? 2 : 0;
+}
+
+// Smallest MEASURED stack at which the operator route beat nrhs fit adjoints, per shape class (1M cases, one MI355X; DESIGN.md section 13,
+// profiles/solve_adjoint_timings.json): up to 6 unknowns (2D order 2 at 32 neighbours: it loses at 1 field, 0.87 against 0.31 ms — the
+// operator itself is 1.5 KB per case — and wins from 4, 1.00 against 1.22 ms); the larger systems were measured at 64 fields only (3D
+// order 2: 7.7x, 2D order 4: 8.0x), so their class starts there until smaller stacks are measured.
+static int64_t solve_adjoint_op_from(int no) {
+    return no <= 6 ? 4 : 64;
+}
+
+static int zero_columns(double* base, int64_t from, int64_t to, int64_t stride_rhs, int64_t stride_case, int64_t nrhs, int64_t ncases,
+                        hipStream_t s) {
+    if (to <= from) return WLSQM_OK;
+    const size_t width = (size_t)(to - from) * 8, pitch = (size_t)stride_case * 8;
+    if (nrhs == 1 || stride_rhs == ncases * stride_case) {           // one stack of rows at one pitch
+        WLSQM_HIP_CHECK(hipMemset2DAsync(base + from, pitch, 0, width, (size_t)(nrhs * ncases), s));
+        return WLSQM_OK;
+    }
+    for (int64_t r = 0; r < nrhs; ++r)
+        WLSQM_HIP_CHECK(hipMemset2DAsync(base + r * stride_rhs + from, pitch, 0, width, (size_t)ncases, s));
+    return WLSQM_OK;
+}
+
+int wlsqm_hip_expert_solve_adjoint_device(wlsqm_expert* h, void* stream, int64_t nrhs,
+                                          const double* g, int64_t g_stride_rhs, int64_t g_stride_case,
+                                          double* grad_fk, int64_t gfk_stride_rhs, int64_t gfk_stride_case, int64_t gfk_slots,
+                                          double* grad_fi, int64_t gfi_stride_rhs, int64_t gfi_stride_case) {
+    if (!h || !g || !grad_fk) { set_error("null argument"); return WLSQM_EVALUE; }
+    if (nrhs < 1) { set_error("nrhs must be >= 1"); return WLSQM_EVALUE; }
+    if (!h->g->ready) { set_error("Solver is not in the ready state; prepare() must be called before solve()"); return WLSQM_ERUNTIME; }
+    if (h->algorithm == WLSQM_ALGO_ITERATIVE) {
+        set_error("solve_adjoint: the refinement's stop test is data-dependent, an ALGO_ITERATIVE solver has no adjoint"); return WLSQM_EVALUE;
+    }
+    wlsqm_expert_geometry& G = *h->g;
+    if (G.dimension == 3 && G.max_no > 10) { set_error("fit_adjoint: unsupported (dimension, order)"); return WLSQM_EVALUE; }
+    if (gfk_slots < G.max_nk || gfk_stride_case < gfk_slots) { set_error("grad_fk rows narrower than max(nk)"); return WLSQM_EVALUE; }
+    if (g_stride_case < G.max_no || (grad_fi && gfi_stride_case < G.max_no)) {
+        set_error("gradient rows narrower than the number of DOFs"); return WLSQM_EVALUE;
+    }
+    DeviceScope scope; int rc = scope.enter(G.device);
+    if (rc != WLSQM_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int choice = solve_adjoint_choice();
+    if (choice != 1 && G.uniform_order && (choice == 2 || nrhs >= solve_adjoint_op_from(G.max_no))) {
+        if (G.op_state == 0) {
+            // built on demand (the forward's rule: it synchronises) — never while the stream is capturing: the geometric route only enqueues
+            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+            if (cap == hipStreamCaptureStatusNone && (rc = ensure_operator(h, s))) return rc;
+        }
+        if (G.op_state == 1) {
+            bool handled = false;
+            KParams p = expert_params(h, nullptr, 0, nullptr, 0);
+            rc = launch_solve_op_adjoint(G.dimension, G.order[0], p, G.slots, G.d_op.as<double>(), G.d_T.as<double>(), G.op_any_known, nrhs,
+                                         g, g_stride_rhs, g_stride_case, grad_fk, gfk_stride_rhs, gfk_stride_case, gfk_slots,
+                                         grad_fi, gfi_stride_rhs, gfi_stride_case, s, &handled);
+            if (rc != WLSQM_OK) return rc;
+            if (handled)       // the operator rows hold the slots rounded up to 8: a wider row of the caller's is zero from there on
+                return zero_columns(grad_fk, (G.slots + 7) / 8 * 8, gfk_slots, gfk_stride_rhs, gfk_stride_case, nrhs, G.ncases, s);
+        }
+    }
+    // geometric route: per field one adjoint of the fit on the resident geometry, bucketed by order as expert_launch does
+    const int64_t Kq = std::min<int64_t>(G.slots, gfk_slots);
+    for (int64_t r = 0; r < nrhs; ++r) {
+        KParams p = expert_params(h, nullptr, 0, nullptr, 0);
+        p.max_nk = Kq; p.iterative = 0; p.iters_out = nullptr;
+        const AdjointArgs q{g + r * g_stride_rhs, g_stride_case, grad_fk + r * gfk_stride_rhs, gfk_stride_case, 1,
+                            grad_fi ? grad_fi + r * gfi_stride_rhs : nullptr, gfi_stride_case};
+        if (G.uniform_order) {
+            if ((rc = launch_fit_adjoint(G.dimension, G.order[0], p, q, s))) return rc;
+            continue;
+        }
+        for (int o = 0; o <= 4; ++o) {
+            if (G.off[o + 1] == G.off[o]) continue;
+            p.case_index = G.d_idx.as<long long>() + G.off[o];
+            p.ncases = G.off[o + 1] - G.off[o];
+            if ((rc = launch_fit_adjoint(G.dimension, o, p, q, s))) return rc;
+        }
+    }
+    return zero_columns(grad_fk, Kq, gfk_slots, gfk_stride_rhs, gfk_stride_case, nrhs, G.ncases, s);
+}
+
 int wlsqm_hip_expert_solve_many(wlsqm_expert* h, int64_t nrhs,
                                 const double* fk, int64_t fk_stride_rhs, int64_t fk_stride_case, int64_t fk_stride_k,
                                 double* fi, int64_t fi_stride_rhs, int64_t fi_stride_case) {

@@ -406,4 +406,225 @@ int launch_solve_op(int dimension, int order, const KParams& geom, long long K, 
     return WLSQM_OK;
 }
 
+
+// ---- the adjoint: the TRANSPOSED operator on the matrix cores ---------------------------------------------
+// For case j and field r, g = dL/dfi_out[r][j][:no]:
+//     grad_fk[r][j][k] = sum_a op[j][a][k] g[a]           (the rows of op are zero for knowns and dropped DOFs, its columns from nk[j] on),
+//     grad_fi[r][j][a] = 0 for an unknown, g[a] for a dropped DOF, g[a_t] - sum_a T[j][a][t] g[a] for the t-th true known a_t
+// (the forward is fi_U = S f - T v).  The mirror of solve_op_mfma_kernel: one wave per case, a workgroup of WPG consecutive cases,
+// fields in blocks of 16, v_mfma_f64_16x16x4_f64 with
+//     A[i][a] = op^T (row i = one of 16 neighbour slots of a k-block, contraction over the DOFs a = 4 s + q, no <= 15 padded to 16:
+//               four MFMA steps),   B[a][c] = g of field r0 + c,   D[i][c] -> grad_fk.
+// Row i = 4 v + q of k-block b is slot 16 b + 8 (v / 2) + 2 q + v % 2: a lane's accumulator elements (0, 1) and (2, 3) are two pairs
+// of CONSECUTIVE slots, and the four lane groups q of one 16-byte store instruction cover 64 contiguous bytes of a field's grad_fk
+// row (the forward's load-side argument, mirrored).  op^T of the case, 4 NB doubles per lane, is loaded once and kept for all fields.
+// The g rows are the scattered side (no doubles per field, 16 fields a field stride apart), so they travel as the forward's fi does:
+// the workgroup reads, per field, the WPG * no contiguous doubles its cases own (8 B per lane, consecutive lanes on consecutive
+// addresses) into an LDS slab [16][(WPG * no) | 1] (odd pitch: the bank argument above solve_op_mfma_kernel), one block of fields
+// ahead in registers; the waves take their B operands from the slab, build grad_fi IN the slab (unknowns zeroed, dropped DOFs left,
+// knowns overwritten) and the workgroup writes it out as the same contiguous runs.  T^T g is one more set of four MFMAs with
+// A' = T^T (rows t < OP_NKN) on the same B operands: lane (q, c) finds the t = q sum of field c in accumulator element 0.
+struct OpAdjParams {
+    const double* op; const double* T;
+    const int* nk; const long long* knowns;
+    long long ncases; int KP, kst, no;             // KP: operator row length; kst (even) <= KP: grad_fk slots the kernel stores
+    long long nrhs;
+    const double* g; long long sg_r, sg_j;
+    double* gfk; long long sgfk_r, sgfk_j;
+    double* gfi; long long sgfi_r, sgfi_j;         // gfi nullable
+};
+
+// NR: elements of the [16 fields][WPG cases][no] block of g / grad_fi per lane = ceil(16 no / 64) (two up to 8 unknowns, three for 10, four for 15)
+template <int NB, bool KNOWN, int WPG, int NR>
+__global__ __launch_bounds__(64 * WPG) void solve_op_adjoint_kernel(const OpAdjParams P) {
+    constexpr int OPA_ROUNDS = NR;
+    extern __shared__ __attribute__((aligned(16))) double lds[];      // [2][16][runp]
+    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, q = l >> 4, c16 = l & 15;
+    const int no = P.no, run = WPG * no, runp = run | 1, KP = P.KP;
+    const unsigned long long full = (1ull << no) - 1ull;
+    const bool want_fi = P.gfi != nullptr;                            // kernel-uniform
+    // this lane's elements of the [16][run] block of g / grad_fi: element e -> field e / run, case (e % run) / no, DOF e % no
+    // (packed: field in bits 0-7, case in 8-15, DOF in 16-23; -1: no such element)
+    int el[OPA_ROUNDS];
+#pragma unroll
+    for (int i = 0; i < OPA_ROUNDS; ++i) {
+        const int e = (int)threadIdx.x + i * 64 * WPG;
+        const int row = e / no, a = e - row * no, f = row / WPG, cs = row - f * WPG;
+        el[i] = (e < 16 * run) ? (f | (cs << 8) | (a << 16)) : -1;
+    }
+    auto slab_at = [&](int i) { return (int)threadIdx.x + i * 64 * WPG + (el[i] & 255) * (runp - run); };
+    // slot of this lane's row of the A operand inside a k-block (row c16 = 4 v + q'), and of its accumulator pairs
+    const int aslot = 8 * (c16 >> 3) + 2 * (c16 & 3) + ((c16 >> 2) & 1);
+    for (long long j0 = (long long)blockIdx.x * WPG; j0 < P.ncases; j0 += (long long)gridDim.x * WPG) {
+        const long long j = j0 + wave;
+        const bool have = j < P.ncases;                               // wave-uniform
+        const long long jc = have ? j : P.ncases - 1;
+        const unsigned long long raw = (unsigned long long)P.knowns[jc];
+        unsigned long long known = raw & full, dropped = 0;
+        {
+            int extra = __popcll(raw & ~full);                        // infra.pyx:119-121 quirk (effective_mask)
+            for (int t = no - 1; t >= 0 && extra > 0; --t)
+                if (!((known >> t) & 1ull)) { known |= 1ull << t; dropped |= 1ull << t; --extra; }
+        }
+        const bool work = have && known != full;
+        const unsigned long long tk = known & ~dropped, unk = ~known & full;
+        // op^T of the case: A[b][s] = op[j][4 s + q][16 b + aslot]; DOFs >= no and slots outside the operator row (KP is a multiple of
+        // 8, not of 16) are zeros, not loads
+        double A[NB][4];
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int a = 4 * s + q, slot = 16 * b + aslot;
+                A[b][s] = (work && a < no && slot < KP) ? P.op[(jc * no + a) * (long long)KP + slot] : 0.0;
+            }
+        double Tl[KNOWN ? 4 : 1] = {};
+        int kq = -1;                                                  // the known DOF whose grad_fi this lane group writes (t = q)
+        if (KNOWN && work && tk) {
+            int t = 0;
+            for (int a = 0; a < no && t < OP_NKN; ++a)
+                if ((tk >> a) & 1ull) { if (t == q) kq = a; ++t; }
+            if (want_fi && c16 < OP_NKN) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                    if (4 * s + q < no) Tl[KNOWN ? s : 0] = P.T[(jc * OP_ROWS + op_row_of_dof(4 * s + q)) * OP_NKN + c16];
+            }
+        }
+        // per-case parts of this lane's element addresses
+        long long og[OPA_ROUNDS], oi[OPA_ROUNDS];
+        bool ev[OPA_ROUNDS];
+#pragma unroll
+        for (int i = 0; i < OPA_ROUNDS; ++i) {
+            const int f = el[i] & 255, cs = (el[i] >> 8) & 255, a = (el[i] >> 16) & 255;
+            ev[i] = el[i] >= 0 && j0 + cs < P.ncases;
+            og[i] = f * P.sg_r + (j0 + cs) * P.sg_j + a;
+            oi[i] = f * P.sgfi_r + (j0 + cs) * P.sgfi_j + a;
+        }
+        // The operator piece is IN its registers before the loop over the fields: the compiler cannot count loads in flight across the
+        // loop header (the comment in solve_op_mfma_kernel), and without this it waits out the NEXT block's g, just requested, at the
+        // first MFMA of every block
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) asm volatile("" ::"v"(A[b][s]));
+        if (KNOWN) {
+#pragma unroll
+            for (int s = 0; s < (KNOWN ? 4 : 1); ++s) asm volatile("" ::"v"(Tl[s]));
+        }
+        double pre[OPA_ROUNDS];
+        auto fetch = [&](long long r0) {
+#pragma unroll
+            for (int i = 0; i < OPA_ROUNDS; ++i)
+                pre[i] = (ev[i] && r0 + (el[i] & 255) < P.nrhs) ? P.g[og[i] + r0 * P.sg_r] : 0.0;    // fields past the last one: zeros
+        };
+        fetch(0);
+        int parity = 0;
+        __syncthreads();                                              // the previous group's store phase has read both slabs
+        for (long long r0 = 0; r0 < P.nrhs; r0 += 16) {
+            double* slab = lds + parity * 16 * runp;
+#pragma unroll
+            for (int i = 0; i < OPA_ROUNDS; ++i)
+                if (el[i] >= 0) slab[slab_at(i)] = pre[i];
+            if (r0 + 16 < P.nrhs) fetch(r0 + 16);                     // the next block's g is in flight while this one is multiplied
+            // LDS-only barrier (as in solve_op_mfma_kernel: __syncthreads() would wait out the loads just requested)
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            if (have) {
+                double* mine = slab + c16 * runp + wave * no;        // g of field r0 + c16 for this wave's case
+                double B[4];
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const int a = 4 * s + q;
+                    // DOFs >= no are 0.0, not a read past the row; DOFs the fit does not solve for take no part (their operator rows are
+                    // zero: masked here so that 0 * inf cannot reach grad_fk, as the geometric adjoint never reads them)
+                    B[s] = (a < no && ((unk >> a) & 1ull)) ? mine[a] : 0.0;
+                }
+                const bool fld = r0 + c16 < P.nrhs;
+                double* out = P.gfk + (r0 + c16) * P.sgfk_r + j * P.sgfk_j;
+#pragma unroll
+                for (int b = 0; b < NB; ++b) {
+                    od4_ acc = {0.0, 0.0, 0.0, 0.0};
+                    if (work) {
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[b][s], B[s], acc, 0, 0, 0);
+                    }
+                    const int k0 = 16 * b + 2 * q;
+                    if (fld && k0 < P.kst) __builtin_nontemporal_store(od2_{acc[0], acc[1]}, reinterpret_cast<od2_*>(out + k0));
+                    if (fld && k0 + 8 < P.kst) __builtin_nontemporal_store(od2_{acc[2], acc[3]}, reinterpret_cast<od2_*>(out + k0 + 8));
+                }
+                if (want_fi && work) {
+                    double gk = 0.0;
+                    od4_ acc = {0.0, 0.0, 0.0, 0.0};
+                    if (KNOWN && tk) {                                // wave-uniform
+                        if (kq >= 0) gk = mine[kq];
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Tl[KNOWN ? s : 0], B[s], acc, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        const int a = 4 * s + q;
+                        if (a < no && ((unk >> a) & 1ull)) mine[a] = 0.0;       // an unknown's incoming value is never read by the fit
+                    }
+                    if (KNOWN && kq >= 0) mine[kq] = gk - acc[0];
+                }
+            }
+            if (want_fi) {
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#pragma unroll
+                for (int i = 0; i < OPA_ROUNDS; ++i)
+                    if (ev[i] && r0 + (el[i] & 255) < P.nrhs) __builtin_nontemporal_store(slab[slab_at(i)], &P.gfi[oi[i] + r0 * P.sgfi_r]);
+            }
+            parity ^= 1;
+        }
+    }
+}
+
+// Eligibility: the forward's shape rule; 16-byte stores into grad_fk (base aligned, even strides, an even number of slots).  g and
+// grad_fi move 8 bytes per lane through the slab and carry no alignment condition.
+int launch_solve_op_adjoint(int dimension, int order, const KParams& geom, long long K, const double* op, const double* T, int any_known,
+                            long long nrhs, const double* g, long long sg_r, long long sg_j, double* gfk, long long sgfk_r,
+                            long long sgfk_j, long long gfk_slots, double* gfi, long long sgfi_r, long long sgfi_j, hipStream_t stream,
+                            bool* handled) {
+    *handled = false;
+    if (!solve_op_shape_ok(dimension, order, K) || !op) return WLSQM_OK;
+    if ((reinterpret_cast<uintptr_t>(gfk) & 15u) || (sgfk_r % 2) != 0 || (sgfk_j % 2) != 0 || (gfk_slots % 2) != 0) return WLSQM_OK;
+    const int no_ = ndofs(dimension, order);
+    const long long KP = (K + 7) / 8 * 8;
+    OpAdjParams P{op, T, geom.nk, geom.knowns, geom.ncases, (int)KP, (int)std::min(KP, gfk_slots), no_, nrhs,
+                  g, sg_r, sg_j, gfk, sgfk_r, sgfk_j, gfi, sgfi_r, sgfi_j};
+    int dev = 0;
+    WLSQM_HIP_CHECK(hipGetDevice(&dev));
+    static int cus[16] = {};
+    if (dev < 0 || dev >= 16) { set_error("device ordinal out of range"); return WLSQM_EVALUE; }
+    if (!cus[dev]) {
+        hipDeviceProp_t prop;
+        WLSQM_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+        cus[dev] = prop.multiProcessorCount;
+    }
+    const int ncu = cus[dev];
+    // 16 waves per workgroup up to 10 unknowns, 8 beyond and with the correction block (as the forward: its registers do not fit the
+    // 128 of a 16-wave workgroup without scratch); two slabs of 16 x (WPG no | 1) doubles: 41 KB for 10 unknowns at 16 waves
+#define OPA_LAUNCH(NB_, KN_, WPG_, NR_)                                                                                      \
+    {                                                                                                                    \
+        const size_t lds_bytes = sizeof(double) * 2 * 16 * ((WPG_ * no_) | 1);                                           \
+        const long long wgs = (geom.ncases + WPG_ - 1) / WPG_;                                                           \
+        long long grid = (long long)ncu * (16 / WPG_) * 4;                                                               \
+        if (grid > wgs) grid = wgs;                                                                                      \
+        if (grid < 1) grid = 1;                                                                                          \
+        hipLaunchKernelGGL((solve_op_adjoint_kernel<NB_, KN_, WPG_, NR_>), dim3((unsigned)grid), dim3(64 * WPG_), lds_bytes, stream, P); \
+    }
+#define OPA_CASE(NB_)                                                                                         \
+    if ((KP + 15) / 16 == NB_) {                                                                              \
+        const bool kn = any_known && gfi;      /* the correction block only enters grad_fi */                 \
+        if (no_ <= 8) { if (kn) OPA_LAUNCH(NB_, true, 8, 2) else OPA_LAUNCH(NB_, false, 16, 2) }               \
+        else if (no_ <= 10) { if (kn) OPA_LAUNCH(NB_, true, 8, 3) else OPA_LAUNCH(NB_, false, 16, 3) }        \
+        else { if (kn) OPA_LAUNCH(NB_, true, 8, 4) else OPA_LAUNCH(NB_, false, 8, 4) }                         \
+        WLSQM_HIP_CHECK(hipGetLastError());                                                                   \
+        *handled = true; note_kernel("solve-op-adjoint-mfma"); return WLSQM_OK;                               \
+    }
+    OPA_CASE(1) OPA_CASE(2) OPA_CASE(3) OPA_CASE(4)
+#undef OPA_CASE
+#undef OPA_LAUNCH
+    return WLSQM_OK;
+}
+
 }  // namespace wlsqm

@@ -61,6 +61,7 @@ namespace wlsqm {
 //   WLSQM_HIP_SOLVE_MANY             A/B   =f | =o           the stacked solve on the FMA kernel / on the stored-operator MFMA kernel (expert.hip)
 //   WLSQM_HIP_OP_WPG                 A/B   integer           waves per workgroup of the MFMA kernel (solve_op.hip)
 //   WLSQM_HIP_OP_DEBUG               A/B   integer           experiments of that kernel: 1 no stores, 2 only the first block of fields loaded (solve_op.hip)
+//   WLSQM_HIP_SOLVE_ADJOINT          A/B   =g | =o           the adjoint of the prepared solve: the geometric route (one fit adjoint per field) everywhere / the stored operator's transpose wherever it is eligible, whatever the stack size (expert.hip)
 //   WLSQM_HIP_ADJOINT_FORM           A/B   =l | =r           the adjoint of the fit: the lane form for every batch / the rows form wherever it is eligible, whatever measured faster for the shape (fit_adjoint.hip)
 
 // first character of the value; '\0' when the switch is unset or empty
@@ -194,6 +195,13 @@ int solve_op_build(int dimension, int order, const KParams& geom, long long K, c
 int launch_solve_op(int dimension, int order, const KParams& geom, long long K, const double* op, const double* T, int any_known,
                     long long nrhs, const double* fk, long long sfk_r, long long sfk_j, double* fi, long long sfi_r, long long sfi_j,
                     hipStream_t stream, bool* handled);                                                           // solve_op.hip
+bool solve_op_shape_ok(int dimension, int order, long long K);                                                     // solve_op.hip: shapes the stored operator covers
+// The adjoint of R stacked fields through the stored operator's transpose: grad_fk[r][j][k] for k < min(gfk_slots,
+// K rounded up to 8), grad_fi[r][j][a] for a < no (gfi nullable).  *handled = false with WLSQM_OK: not eligible, nothing was launched.
+int launch_solve_op_adjoint(int dimension, int order, const KParams& geom, long long K, const double* op, const double* T, int any_known,
+                            long long nrhs, const double* g, long long sg_r, long long sg_j, double* gfk, long long sgfk_r,
+                            long long sgfk_j, long long gfk_slots, double* gfi, long long sgfi_r, long long sgfi_j, hipStream_t stream,
+                            bool* handled);                                                                       // solve_op.hip
 long long cond_workspace_doubles(int no);                                                                         // conds.hip
 int launch_conds(int dimension, int order, const KParams& p, const int* order_arr, double* ws, long long CH,
                  long long case0, double* out, hipStream_t stream);                                               // conds.hip

@@ -124,6 +124,10 @@ def lib():
     L.wlsqm_hip_expert_prepare_operator.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.wlsqm_hip_expert_solve_many_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                                      C.c_void_p, C.c_int64, C.c_int64]
+    if hasattr(L, "wlsqm_hip_expert_solve_adjoint_device"):          # (older builds of the library, as above)
+        L.wlsqm_hip_expert_solve_adjoint_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                                            C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64]
+        L.wlsqm_hip_expert_solve_adjoint_device.restype = C.c_int
     L.wlsqm_hip_expert_solve_many.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                               C.c_void_p, C.c_int64, C.c_int64]
     L.wlsqm_hip_expert_memory_used.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]

@@ -370,6 +370,76 @@ class ExpertSolver:
             C.c_void_p(fk.data_ptr()), fk.stride(0), fk.stride(1), C.c_void_p(fi.data_ptr()), fi.stride(0), fi.stride(1)))
         return 0
 
+    # ---- the adjoint of the prepared solve (extension; csrc/solve_op.hip) ----
+
+    def _adjoint_arguments(self, g, grad_fk, grad_fi, rank):
+        """Checks (those of solve_device / solve_many_device, with their messages) and allocation of the outputs."""
+        if not self.ready:
+            raise RuntimeError("Solver is not in the ready state; prepare() must be called before solve()")
+        import torch
+        want_fi = grad_fi is not False
+        given = [(g, "g")] + ([(grad_fk, "grad_fk")] if grad_fk is not None else []) \
+            + ([(grad_fi, "grad_fi")] if want_fi and grad_fi is not None else [])
+        for t, name in given:
+            if t.dtype != torch.float64 or t.dim() != rank or not t.is_cuda or t.stride(rank - 1) != 1:
+                raise ValueError("%s must be a %d-D float64 device tensor with a contiguous last axis" % (name, rank))
+        lead = tuple(g.shape[:rank - 2])
+        if rank == 3 and (g.shape[0] < 1 or any(t.shape[0] != g.shape[0] for t, _ in given)):
+            raise ValueError("g, grad_fk and grad_fi must hold the same number (>= 1) of right-hand sides")
+        if any(t.shape[rank - 2] < self.ncases for t, _ in given) or (grad_fk is not None and grad_fk.shape[rank - 1] < self._max_nk):
+            raise ValueError("g/grad_fk/grad_fi are too small")
+        for t, name in given:
+            if name != "grad_fk" and t.shape[rank - 1] < self._max_no:
+                raise ValueError("%s has %d columns, need at least %d" % (name, t.shape[rank - 1], self._max_no))
+        for t, name in given:
+            if t.device.type != "cuda" or (t.device.index or 0) != self._device:
+                raise ValueError("%s must live on the solver's device (cuda:%d)" % (name, self._device))
+        if grad_fk is None:
+            grad_fk = torch.empty(lead + (self.ncases, self._max_nk), dtype=torch.float64, device=g.device)
+        if want_fi and grad_fi is None:
+            # mixed orders: the columns beyond a case's own number of DOFs are not written
+            uniform = bool((np.asarray(self.order) == np.asarray(self.order)[0]).all())
+            grad_fi = (torch.empty if uniform else torch.zeros)(lead + (self.ncases, self._max_no), dtype=torch.float64, device=g.device)
+        return grad_fk, (grad_fi if want_fi else None)
+
+    def solve_adjoint_device(self, g, grad_fk=None, grad_fi=None, stream=None):
+        """The vector-Jacobian product of solve_device (extension): given g (ncases, >= no) = dL/dfi_out, a float64 device tensor with
+        a contiguous last axis, returns (grad_fk (ncases, max_nk), grad_fi (ncases, no)) = (dL/dfk, dL/dfi_in).  See
+        solve_many_adjoint_device; this is its one-field form."""
+        grad_fk, grad_fi = self._adjoint_arguments(g, grad_fk, grad_fi, 2)
+        self._solve_adjoint(1, g, 0, g.stride(0), grad_fk, 0, grad_fk.stride(0), grad_fk.shape[1],
+                            grad_fi, 0, grad_fi.stride(0) if grad_fi is not None else 0, stream)
+        return grad_fk, grad_fi
+
+    def solve_many_adjoint_device(self, g, grad_fk=None, grad_fi=None, stream=None):
+        """The vector-Jacobian product of solve_many_device (extension): given g (nrhs, ncases, >= no) = dL/dfi_out, returns
+        (grad_fk (nrhs, ncases, max_nk), grad_fi (nrhs, ncases, no)).  The solve is linear in fk and in the known entries of fi, so
+        neither enters.  grad_fk[r, j, k] is exactly 0 for nk[j] <= k (every column of a wider grad_fk is written);
+        grad_fi[r, j, a] is 0 for an unknown, g for a DOF dropped by stray high mask bits, g minus the fit's dependence on the value
+        for a known DOF; a case with every DOF known has grad_fk = 0 and grad_fi = g.  The outputs are allocated when not given;
+        grad_fi=False: not wanted (returned as None).  g, grad_fk and grad_fi must not overlap.
+
+        Stacks on a shape with a stored solution operator (prepare_operator()) apply its transpose as one batched GEMM on the
+        matrix cores, from the stack size at which that measured faster (4 fields up to 6 unknowns, 64 beyond; WLSQM_HIP_SOLVE_ADJOINT=o:
+        always); everything else (and WLSQM_HIP_SOLVE_ADJOINT=g) runs one adjoint of the fit per field on the resident geometry.
+        With the operator present the call only enqueues kernels on `stream` (default: torch's current stream): it can be captured;
+        during a capture the operator is never built.  Always the fast arithmetic, whatever the numerics mode.  ALGO_BASIC only;
+        3D orders 3 and 4 are not covered (ValueError)."""
+        grad_fk, grad_fi = self._adjoint_arguments(g, grad_fk, grad_fi, 3)
+        self._solve_adjoint(g.shape[0], g, g.stride(0), g.stride(1), grad_fk, grad_fk.stride(0), grad_fk.stride(1), grad_fk.shape[2],
+                            grad_fi, grad_fi.stride(0) if grad_fi is not None else 0, grad_fi.stride(1) if grad_fi is not None else 0,
+                            stream)
+        return grad_fk, grad_fi
+
+    def _solve_adjoint(self, nrhs, g, sg_r, sg_j, gfk, sk_r, sk_j, slots, gfi, si_r, si_j, stream):
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(g.device).cuda_stream
+        B.check(B.lib().wlsqm_hip_expert_solve_adjoint_device(
+            self._handle, C.c_void_p(int(stream) if stream else 0), int(nrhs), C.c_void_p(g.data_ptr()), int(sg_r), int(sg_j),
+            C.c_void_p(gfk.data_ptr()), int(sk_r), int(sk_j), int(slots),
+            C.c_void_p(gfi.data_ptr()) if gfi is not None else None, int(si_r), int(si_j)))
+
     def solve_many(self, fk, fi):
         """Many fields on the prepared geometry, numpy in/out (extension): fk (nrhs, ncases, >= max_nk),
         fi (nrhs, ncases, >= no) in/out; same result as nrhs calls of solve() with ALGO_BASIC.  Returns 0."""

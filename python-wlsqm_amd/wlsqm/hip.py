@@ -14,6 +14,7 @@ import contextlib
 
 __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_cloud_device", "device_count", "knn", "ball", "nearest",
            "fit_many_adjoint_device", "fit_cloud_adjoint_device", "differentiable_fit_many", "differentiable_fit_cloud",
+           "differentiable_solve", "differentiable_solve_many",
            "InterpolationPlan",
            "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
            "getrf_batched", "getrs_batched", "gesv_batched", "sytrf_batched", "sytrs_batched", "sysv_batched", "symmetrize_batched"]
@@ -568,6 +569,83 @@ def differentiable_fit_cloud(dimension, order, S, F, hoods, fi, nk, knowns, weig
     _adjoint_order(dimension, order)
     _no_geometry_grad(S)
     return _autograd_functions()[1].apply(F, fi, dimension, int(order), S, hoods, nk, knowns, weighting_method, point_index, strict, stream)
+
+
+# ---- gradients through the prepared solver (ExpertSolver.solve_adjoint_device; csrc/solve_op.hip) ----
+
+_AUTOGRAD_SOLVE = None
+
+
+def _autograd_solve():
+    """The torch.autograd.Function behind differentiable_solve / differentiable_solve_many (made at first use)."""
+    global _AUTOGRAD_SOLVE
+    if _AUTOGRAD_SOLVE is not None:
+        return _AUTOGRAD_SOLVE
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class Solve(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, fk, fi, solver, stream, many):
+            out = fi.detach().clone()
+            (solver.solve_many_device if many else solver.solve_device)(fk.detach(), out, stream=stream)
+            ctx.call = (solver, stream, many, tuple(fk.shape), tuple(fi.shape))
+            return out
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gout):
+            solver, stream, many, fk_shape, fi_shape = ctx.call
+            need_fk, need_fi = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if not (need_fk or need_fi):
+                return (None,) * 5
+            g = gout.contiguous()
+            # rows beyond ncases receive no gradient (the columns beyond the solver's slots are zero-filled by the call itself)
+            gfk = (torch.zeros if fk_shape[-2] != solver.ncases else torch.empty)(fk_shape, dtype=torch.float64, device=g.device)
+            gfi = False
+            if need_fi:
+                # rows and columns of fi that the solve never touches leave as they came in: dL/dfi_in starts as a copy of g there
+                uniform = bool((solver.order == solver.order[0]).all())
+                exact = uniform and fi_shape[-2] == solver.ncases and fi_shape[-1] == solver._max_no
+                gfi = None if exact else g.clone()
+            adjoint = solver.solve_many_adjoint_device if many else solver.solve_adjoint_device
+            _, gfi = adjoint(g, grad_fk=gfk, grad_fi=gfi, stream=stream)
+            return (gfk if need_fk else None, gfi if need_fi else None, None, None, None)
+
+    _AUTOGRAD_SOLVE = Solve
+    return Solve
+
+
+def _differentiable_solve(solver, fk, fi, stream, many):
+    rank = 3 if many else 2
+    if not solver.ready:
+        raise RuntimeError("Solver is not in the ready state; prepare() must be called before solve()")
+    for t, name in ((fk, "fk"), (fi, "fi")):
+        if str(t.dtype).split(".")[-1] != "float64" or t.dim() != rank or not t.is_cuda or t.stride(rank - 1) != 1:
+            raise ValueError("%s must be a %d-D float64 device tensor with a contiguous last axis" % (name, rank))
+    if many and (fk.shape[0] != fi.shape[0] or fk.shape[0] < 1):
+        raise ValueError("fk and fi must hold the same number (>= 1) of right-hand sides")
+    if fk.shape[rank - 2] < solver.ncases or fi.shape[rank - 2] < solver.ncases or fk.shape[rank - 1] < solver._max_nk:
+        raise ValueError("fk/fi are too small")
+    if fi.shape[rank - 1] < solver._max_no:
+        raise ValueError("fi has %d columns, need at least %d" % (fi.shape[rank - 1], solver._max_no))
+    return _autograd_solve().apply(fk, fi, solver, stream, many)
+
+
+def differentiable_solve(solver, fk, fi, stream=None):
+    """ExpertSolver.solve_device as a differentiable function of fk (ncases, >= max_nk) and fi (ncases, >= no) on the prepared
+    geometry of `solver`: returns fi_out, a NEW tensor (fi is cloned and the in-place solve runs on the clone, so the solver's
+    "latest solve" that interpolate() evaluates is the returned tensor).  The backward pass is solver.solve_adjoint_device, computed
+    only for the inputs that require a gradient; dL/dfk has fk's full shape (zeros in rows and columns the solve never reads), rows
+    and columns of fi that the solve never touches pass the incoming gradient through.  ALGO_BASIC solvers only.  Once differentiable."""
+    return _differentiable_solve(solver, fk, fi, stream, False)
+
+
+def differentiable_solve_many(solver, fk, fi, stream=None):
+    """ExpertSolver.solve_many_device as a differentiable function of fk (nrhs, ncases, >= max_nk) and fi (nrhs, ncases, >= no): see
+    differentiable_solve.  The backward pass is solver.solve_many_adjoint_device: with the stored solution operator present
+    (solver.prepare_operator()) one batched GEMM with its transpose for the whole stack."""
+    return _differentiable_solve(solver, fk, fi, stream, True)
 
 
 def knn(S, k, stream=None, nquery=None):
