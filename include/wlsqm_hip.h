@@ -391,6 +391,38 @@ int wlsqm_hip_interp_plan_eval_expert(const wlsqm_interp_plan* plan, wlsqm_exper
                                       int ndiff, double* out_dev, int64_t out_stride_diff);
 int wlsqm_hip_interp_plan_destroy(wlsqm_interp_plan* plan);
 
+/* ---- the adjoint of the evaluation (extension) ----
+ * eval_* is linear in fi, so its adjoint takes g[f][d][m] = dL/d out[f][d][m] (at g_dev + f * g_stride_field + d * g_stride_diff + m)
+ * to grad_fi[f][i][a] = dL/d fi[f][i][a] (at grad_fi_dev + f * gfi_stride_field + i * gfi_stride_model + a):
+ *     nearest:     grad_fi[f][i][a] = sum over m with I_m == i, over d with P_a >= P_diffs[d]:  g[f][d][m] c_m[index(P_a - P_diffs[d])]
+ *     continuous:  the same over the list entries (m, e) with idx[e] == i, every term times w_{m,e} / W_m, W_m = sum_e w_{m,e}
+ * with c_m the scaled monomials of x_m - xi[i] and P the exponent table.  EVERY element of grad_fi[f][0 .. nmodels)[0 .. ncols) is
+ * written (exact zeros in the columns from the model's own number of DOFs on and in the rows of models that no point uses) and
+ * nothing else is; the caller pre-fills nothing.  ncols >= the number of DOFs of the plan's largest order, gfi_stride_model >= ncols.
+ * A point whose value does not depend on fi (model number outside 0 .. nmodels - 1, empty list, W_m == 0) and a diff that no model of
+ * the plan has contribute nothing and their g is never read; a diff given twice contributes twice.  With nx == 0 or ndiff == 0 the
+ * call still writes the zeros.  ndiff in 0 .. 35, nfields >= 0 (0: nothing happens).
+ * No atomics: the sum is a gather over the plan's inverted index (per model the points that use it, in ascending point number), one
+ * lane per model, one wavefront per model with more than `threshold` entries (wlsqm_hip_last_kernel(): "interp-plan-adjoint",
+ * "interp-plan-adjoint+wave" when the plan has such models).  The bits of grad_fi[f] are a function of the plan and of field f's g:
+ * the same run to run, eager or replayed from a graph, with the field alone or anywhere in a stack, with the diffs in any order (and
+ * g's diff axis permuted alike).
+ * prepare_adjoint builds the inverted index now (a stable sort; it allocates and synchronises `stream`; idempotent); *built
+ * (nullable) = 1 when the index exists afterwards.  Without it the first eval_adjoint_device builds the index on demand — unless
+ * `stream` is capturing: then it returns WLSQM_ERUNTIME (call prepare_adjoint before the capture) with nothing enqueued.  With the
+ * index present eval_adjoint_device only enqueues kernels.  WLSQM_EVALUE when the index would hold more than 2^31 - 1 entries.
+ * adjoint_info (every output nullable): entries of the index, the longest list of a model, the number of models that take the wave
+ * form (all three -1 while the index is absent) and the threshold.  export_transposed: toff_dev[nmodels + 1] and tpt_dev[nentries]
+ * (int64 device arrays; the points of model i are tpt[toff[i] .. toff[i + 1])), enqueued on `stream`; WLSQM_ERUNTIME without index. */
+int wlsqm_hip_interp_plan_prepare_adjoint(wlsqm_interp_plan* plan, void* stream, int* built);
+int wlsqm_hip_interp_plan_adjoint_info(const wlsqm_interp_plan* plan, int64_t* nentries, int64_t* max_len, int64_t* nlong,
+                                       int32_t* threshold);
+int wlsqm_hip_interp_plan_export_transposed(const wlsqm_interp_plan* plan, void* stream, int64_t* toff_dev, int64_t* tpt_dev);
+int wlsqm_hip_interp_plan_eval_adjoint_device(wlsqm_interp_plan* plan, void* stream, int64_t nfields,
+                                              const int32_t* diffs, int ndiff, const double* g_dev, int64_t g_stride_field,
+                                              int64_t g_stride_diff, double* grad_fi_dev, int64_t gfi_stride_field,
+                                              int64_t gfi_stride_model, int ncols);
+
 /* ---- batched dense solves: wlsqm.utils.lapackdrivers (lapackdrivers.pyx, the m* / *factor* families) ----
  * `count` independent problems in the reference's layout, Fortran order throughout: A is (n, n, nlhs) with element
  * (i, j, k) at A[i + n*j + n*n*k]; b is (n, count), ipiv (n, nlhs) int32 with LAPACK's 1-based entries, info one

@@ -152,6 +152,15 @@ def lib():
         L.wlsqm_hip_interp_plan_destroy.argtypes = [C.c_void_p]
         for name in ("create", "create_expert", "info", "export", "eval_device", "eval_expert", "destroy"):
             getattr(L, "wlsqm_hip_interp_plan_" + name).restype = C.c_int
+        # the adjoint of the evaluation (InterpolationPlan.evaluate_adjoint, wlsqm.hip.differentiable_evaluate)
+        L.wlsqm_hip_interp_plan_prepare_adjoint.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        L.wlsqm_hip_interp_plan_adjoint_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3 + [C.POINTER(C.c_int32)]
+        L.wlsqm_hip_interp_plan_export_transposed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.wlsqm_hip_interp_plan_eval_adjoint_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int,
+                                                                C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                                                C.c_int]
+        for name in ("prepare_adjoint", "adjoint_info", "export_transposed", "eval_adjoint_device"):
+            getattr(L, "wlsqm_hip_interp_plan_" + name).restype = C.c_int
     # batched dense solves (wlsqm.utils.lapackdrivers, wlsqm.hip.*_batched)
     for op in ("getrf", "gesv", "sytrf", "sysv"):
         solve = op in ("gesv", "sysv")

@@ -15,7 +15,7 @@ import contextlib
 __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_cloud_device", "device_count", "knn", "ball", "nearest",
            "fit_many_adjoint_device", "fit_cloud_adjoint_device", "differentiable_fit_many", "differentiable_fit_cloud",
            "differentiable_solve", "differentiable_solve_many",
-           "InterpolationPlan",
+           "InterpolationPlan", "differentiable_evaluate",
            "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
            "getrf_batched", "getrs_batched", "gesv_batched", "sytrf_batched", "sytrs_batched", "sysv_batched", "symmetrize_batched"]
 
@@ -746,6 +746,7 @@ class InterpolationPlan:
         if xi.dim() not in (1, 2) or (1 if xi.dim() == 1 else int(xi.shape[1])) != dim:
             raise ValueError("xi must be (nmodels,) or (nmodels, dim) with the coordinates of x; got %s" % (tuple(xi.shape),))
         _check(xi, "xi", "float64", xi.dim())
+        self._geometry_requires_grad = self._geometry_requires_grad or bool(getattr(xi, "requires_grad", False))
         if xi.dim() == 2 and xi.stride(1) != 1:
             raise ValueError("Buffer and memoryview are not contiguous in the same dimension. (argument xi)")
         nmodels = int(xi.shape[0])
@@ -815,6 +816,7 @@ class InterpolationPlan:
                 raise ValueError("I must be contiguous")
         self._mode_code = 0 if mode == 'nearest' else 1
         self.mode, self.r = mode, (float(r) if mode == 'continuous' else None)
+        self._geometry_requires_grad = bool(getattr(x, "requires_grad", False))      # differentiable_evaluate refuses such a plan
         return dim
 
     def _finish(self, h, x, dim, nmodels):
@@ -925,6 +927,146 @@ class InterpolationPlan:
             B.check(B.lib().wlsqm_hip_interp_plan_eval_device(h, s, R, _ptr(fi), int(fi.stride(0)) if stacked else 0,
                                                               int(fi.stride(-2)), arr, ndiff, _ptr(out), so_f, so_d))
         return out
+
+    # ---- the adjoint of evaluate (csrc/interp_plan.hip) ----
+
+    def prepare_adjoint(self, stream=None):
+        """Build the inverted index of the adjoint now (per model the points that use it, by a stable sort; continuous plans also
+        keep the forward's weight sums): without this call the first evaluate_adjoint builds it — which allocates and synchronises,
+        so it cannot happen inside a graph capture.  Synchronises `stream`.  Returns True when this call built the index (False: it
+        was there already)."""
+        h = self._live()
+        had = self.adjoint_info()["built"]
+        built = C.c_int(0)
+        B.check(B.lib().wlsqm_hip_interp_plan_prepare_adjoint(h, self._stream(stream), C.byref(built)))
+        return bool(built.value) and not had
+
+    def adjoint_info(self):
+        """dict(built, nentries, max_len, nlong, threshold): whether the inverted index exists, its number of (model, point) entries,
+        the longest list of a model, the number of models with more than `threshold` entries (they take the wave form of the adjoint
+        kernel) — the three counts are None while the index is absent — and the threshold, a constant of the library."""
+        n, longest, nlong, thr = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        B.check(B.lib().wlsqm_hip_interp_plan_adjoint_info(self._live(), C.byref(n), C.byref(longest), C.byref(nlong), C.byref(thr)))
+        built = n.value >= 0
+        return dict(built=built, nentries=int(n.value) if built else None, max_len=int(longest.value) if built else None,
+                    nlong=int(nlong.value) if built else None, threshold=int(thr.value))
+
+    def transposed_lists(self):
+        """(toff, tpt), int64 device tensors (nmodels + 1,) and (number of entries,): the points that use model i are
+        tpt[toff[i]:toff[i + 1]], in ascending point number.  Builds the index when it is absent (prepare_adjoint)."""
+        import torch
+        h = self._live()
+        if not self.adjoint_info()["built"]:
+            self.prepare_adjoint()
+        n = self.adjoint_info()["nentries"]
+        toff = torch.empty((self.nmodels + 1,), dtype=torch.int64, device=self._device)
+        tpt = torch.empty((n,), dtype=torch.int64, device=self._device)
+        B.check(B.lib().wlsqm_hip_interp_plan_export_transposed(h, self._stream(None), _ptr(toff), _ptr(tpt) if n else None))
+        return toff, tpt
+
+    def evaluate_adjoint(self, g, diff=0, grad_fi=None, ncols=None, stream=None):
+        """The adjoint of evaluate(diff, fi): from g = dL/d(evaluate's result) to grad_fi = dL/dfi.
+
+        g has exactly the shape evaluate returns for that `diff` — (nx,) for an int, (ndiff, nx) for a sequence, with a leading axis
+        R for a stack — float64 on the plan's device, contiguous last axis.  Returns grad_fi (nmodels, ncols) or (R, nmodels, ncols),
+        ncols >= the plan's largest number of DOFs (the default); a preallocated grad_fi may have more rows and columns: exactly
+        [:nmodels, :ncols] is written — every element of it, with exact zeros in the columns a model does not have and in the rows
+        of models that no point uses — and nothing else.  g at a point whose value does not depend on fi (NaN in the forward) is
+        never read; a diff given twice contributes twice.  No atomics: the bits of grad_fi of a field are a function of the plan and
+        of that field's g (the same run to run, eager or replayed, alone or in a stack, with the diffs in any order).
+        With the inverted index present (prepare_adjoint) the call only enqueues kernels on `stream`; without it the first call
+        builds the index, which synchronises — RuntimeError when that would happen inside a graph capture."""
+        import torch
+        diffs, single = _diff_list(diff)
+        ndiff = len(diffs)
+        if not hasattr(g, "data_ptr") or not hasattr(g, "is_cuda"):
+            raise ValueError("argument g must be a device (HIP) tensor")
+        _check(g, "g", "float64", g.dim())
+        h = self._live()
+        base = 1 if single else 2
+        if g.dim() not in (base, base + 1):
+            raise ValueError("g must have the shape evaluate() returns for this diff: %s, or with a leading axis for a stack; got %s"
+                             % ((() if single else (ndiff,)) + (self.nx,), tuple(g.shape)))
+        stacked = g.dim() == base + 1
+        R = int(g.shape[0]) if stacked else 1
+        shape = ((R,) if stacked else ()) + (() if single else (ndiff,)) + (self.nx,)
+        if tuple(g.shape) != shape or g.device != self._device or (self.nx > 1 and g.stride(-1) != 1):
+            raise ValueError("g must be a float64 device tensor of shape %s with a contiguous last axis; got %s" % (shape, tuple(g.shape)))
+        ncols = self._max_no if ncols is None else int(ncols)
+        if ncols < self._max_no:
+            raise ValueError("ncols = %d, need at least the plan's largest number of DOFs, %d" % (ncols, self._max_no))
+        if grad_fi is None:
+            grad_fi = torch.empty(((R,) if stacked else ()) + (self.nmodels, ncols), dtype=torch.float64, device=self._device)
+        else:
+            _check(grad_fi, "grad_fi", "float64", 3 if stacked else 2)
+            if (grad_fi.device != self._device or (stacked and grad_fi.shape[0] != R) or grad_fi.shape[-2] < self.nmodels
+                    or grad_fi.shape[-1] < ncols or (grad_fi.shape[-1] > 1 and grad_fi.stride(-1) != 1)):
+                raise ValueError("grad_fi must be %s(>= %d, >= %d) on the plan's device with a contiguous last axis; got %s"
+                                 % ("(%d, " % R if stacked else "", self.nmodels, ncols, tuple(grad_fi.shape)))
+        if R == 0:
+            return grad_fi
+        sg_f = int(g.stride(0)) if stacked else 0
+        sg_d = 0 if single else int(g.stride(1 if stacked else 0))
+        arr = (C.c_int32 * max(ndiff, 1))(*diffs)
+        B.check(B.lib().wlsqm_hip_interp_plan_eval_adjoint_device(h, self._stream(stream), R, arr, ndiff, _ptr(g), sg_f, sg_d,
+                                                                  _ptr(grad_fi), int(grad_fi.stride(0)) if stacked else 0,
+                                                                  int(grad_fi.stride(-2)), ncols))
+        return grad_fi
+
+
+# ---- gradients through the evaluation of a plan (InterpolationPlan.evaluate_adjoint; DESIGN.md section 14) ----
+
+_AUTOGRAD_EVALUATE = None
+
+
+def _autograd_evaluate():
+    """The torch.autograd.Function behind differentiable_evaluate (made at first use)."""
+    global _AUTOGRAD_EVALUATE
+    if _AUTOGRAD_EVALUATE is not None:
+        return _AUTOGRAD_EVALUATE
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class Evaluate(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, fi, plan, diff, stream):
+            ctx.call = (plan, diff, stream, tuple(fi.shape))
+            return plan.evaluate(diff, fi.detach(), stream=stream)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gout):
+            plan, diff, stream, fi_shape = ctx.call
+            if not ctx.needs_input_grad[0]:
+                return (None,) * 4
+            g = gout.contiguous()
+            # rows beyond nmodels and columns beyond the plan's DOFs are never read by the forward: zeros
+            exact = fi_shape[-2] == plan.nmodels and fi_shape[-1] == plan._max_no
+            gfi = (torch.empty if exact else torch.zeros)(fi_shape, dtype=torch.float64, device=g.device)
+            plan.evaluate_adjoint(g, diff, grad_fi=gfi, stream=stream)
+            return (gfi, None, None, None)
+
+    _AUTOGRAD_EVALUATE = Evaluate
+    return Evaluate
+
+
+def differentiable_evaluate(plan, fi, diff=0, stream=None):
+    """plan.evaluate(diff, fi) as a differentiable function of the coefficients fi (nmodels, >= no) or a stack (R, nmodels, >= no):
+    the same bits as evaluate, with a grad_fn.  The backward pass is plan.evaluate_adjoint (one deterministic gather, no atomics),
+    computed only when fi requires a gradient; dL/dfi has fi's full shape, zeros in the rows beyond nmodels and the columns beyond
+    the plan's DOFs.  fi must be given: "the latest solve of the solver" is not a tensor autograd can see — chain it behind
+    differentiable_solve.  The geometry (the x and xi the plan was made from) is not differentiable: ValueError when either
+    required a gradient.  Call plan.prepare_adjoint() first when the backward pass is to be captured into a graph.
+    Once differentiable."""
+    if fi is None:
+        raise ValueError("differentiable_evaluate needs the coefficients fi explicitly")
+    if getattr(plan, "_geometry_requires_grad", False):
+        raise ValueError("the geometry is not differentiable")
+    if hasattr(diff, "__len__") or hasattr(diff, "__iter__"):
+        diff = [int(d) for d in diff]
+    else:
+        diff = int(diff)
+    return _autograd_evaluate().apply(fi, plan, diff, stream)
 
 
 # ---- batched dense solves (the kernels behind wlsqm.utils.lapackdrivers), device-resident ----
