@@ -11,6 +11,7 @@ import numpy as np
 
 from . import defs
 from .. import _binding as B
+from .. import hip as whip
 
 __all__ = ["number_of_dofs", "ExpertSolver"]
 
@@ -193,9 +194,7 @@ class ExpertSolver:
             raise ValueError("xk (ncases, K) must have a contiguous neighbour axis")
         if xi.shape[0] < self.ncases or xk.shape[0] < self.ncases or xk.shape[1] < self._max_nk:
             raise ValueError("xi / xk are too small")
-        if stream is None:
-            stream = torch.cuda.current_stream(xk.device).cuda_stream
-        B.check(B.lib().wlsqm_hip_expert_prepare_device(self._handle, C.c_void_p(int(stream) if stream else 0),
+        B.check(B.lib().wlsqm_hip_expert_prepare_device(self._handle, whip._stream_ptr(xk, stream),
                                                         C.c_void_p(xi.data_ptr()), xi.stride(0), C.c_void_p(xk.data_ptr()),
                                                         xk.stride(0), self.dimension))
         self.xk, self.xi = xk, xi
@@ -290,7 +289,6 @@ class ExpertSolver:
         in one launch, legal inside a graph capture behind solve_device()."""
         if not self.ready:
             raise RuntimeError("Solver is not in the ready state; prepare() must be called before interpolation_plan()")
-        from .. import hip as whip
         if isinstance(x, np.ndarray) or (I is not None and not hasattr(I, "data_ptr")):
             import torch
             dev = torch.device("cuda", self._device)
@@ -306,20 +304,9 @@ class ExpertSolver:
         (float64, contiguous last axis); the fit is enqueued on `stream` (default: torch's current stream) with no
         host synchronisation and no PCIe traffic.  ALGO_BASIC, no sensitivities.  This is the time-stepping fast
         path: fi can feed the next step's fk without leaving HBM."""
-        if not self.ready:
-            raise RuntimeError("Solver is not in the ready state; prepare() must be called before solve()")
-        import torch
-        for t, name in ((fk, "fk"), (fi, "fi")):
-            if t.dtype != torch.float64 or t.dim() != 2 or not t.is_cuda or t.stride(1) != 1:
-                raise ValueError("%s must be a 2-D float64 device tensor with a contiguous last axis" % name)
-        if fk.shape[0] < self.ncases or fi.shape[0] < self.ncases or fk.shape[1] < self._max_nk:
-            raise ValueError("fk/fi are too small")
-        if fi.shape[1] < self._max_no:
-            raise ValueError("fi has %d columns, need at least %d" % (fi.shape[1], self._max_no))
-        if stream is None:
-            stream = torch.cuda.current_stream(fi.device).cuda_stream
+        self._check_tensors(2, ("fk", "fi"), ((fk, "fk"),), ((fi, "fi"),))
         self._fi_device = fi            # interpolate() evaluates the latest solve: keep its coefficients alive
-        B.check(B.lib().wlsqm_hip_expert_solve_device(self._handle, C.c_void_p(int(stream) if stream else 0),
+        B.check(B.lib().wlsqm_hip_expert_solve_device(self._handle, whip._stream_ptr(fi, stream),
                                                       C.c_void_p(fk.data_ptr()), fk.stride(0),
                                                       C.c_void_p(fi.data_ptr()), fi.stride(0)))
         return 0
@@ -332,13 +319,13 @@ class ExpertSolver:
         if not self.ready:
             raise RuntimeError("Solver is not in the ready state; prepare() must be called before solve()")
         built = C.c_int(0)
-        if stream is None:
-            try:
-                import torch
-                stream = torch.cuda.current_stream().cuda_stream
-            except Exception:
-                stream = 0
-        B.check(B.lib().wlsqm_hip_expert_prepare_operator(self._handle, C.c_void_p(int(stream) if stream else 0), C.byref(built)))
+        try:
+            s = whip._stream_ptr(None, stream)      # None: torch's current device, not the solver's (kept: callers may rely on it)
+        except Exception:
+            if stream is not None:
+                raise
+            s = C.c_void_p(0)                       # no torch, or no device at hand: the null stream
+        B.check(B.lib().wlsqm_hip_expert_prepare_operator(self._handle, s, C.byref(built)))
         return bool(built.value)
 
     def solve_many_device(self, fk, fi, stream=None):
@@ -350,56 +337,65 @@ class ExpertSolver:
         Stacks of 64 fields or more, and every stack on a shape with more than 6 unknowns or 32 neighbour slots, apply the stored
         solution operator (prepare_operator(); built by the first such call otherwise) as a batched GEMM on the matrix cores; short
         stacks on small shapes share the geometry work inside the launch instead."""
-        if not self.ready:
-            raise RuntimeError("Solver is not in the ready state; prepare() must be called before solve()")
-        import torch
-        for t, name in ((fk, "fk"), (fi, "fi")):
-            if t.dtype != torch.float64 or t.dim() != 3 or not t.is_cuda or t.stride(2) != 1:
-                raise ValueError("%s must be a 3-D float64 device tensor with a contiguous last axis" % name)
-        if fk.shape[0] != fi.shape[0] or fk.shape[0] < 1:
-            raise ValueError("fk and fi must hold the same number (>= 1) of right-hand sides")
-        if fk.shape[1] < self.ncases or fi.shape[1] < self.ncases or fk.shape[2] < self._max_nk:
-            raise ValueError("fk/fi are too small")
-        if fi.shape[2] < self._max_no:
-            raise ValueError("fi has %d columns, need at least %d" % (fi.shape[2], self._max_no))
+        self._check_tensors(3, ("fk", "fi"), ((fk, "fk"),), ((fi, "fi"),))
         self._fi_device = fi            # interpolate() evaluates the latest solve (here: the last field)
-        if stream is None:
-            stream = torch.cuda.current_stream(fi.device).cuda_stream
         B.check(B.lib().wlsqm_hip_expert_solve_many_device(
-            self._handle, C.c_void_p(int(stream) if stream else 0), fk.shape[0],
+            self._handle, whip._stream_ptr(fi, stream), fk.shape[0],
             C.c_void_p(fk.data_ptr()), fk.stride(0), fk.stride(1), C.c_void_p(fi.data_ptr()), fi.stride(0), fi.stride(1)))
         return 0
 
     # ---- the adjoint of the prepared solve (extension; csrc/solve_op.hip, DESIGN.md section 13) ----
 
-    def _adjoint_arguments(self, g, grad_fk, grad_fi, rank):
-        """Checks (those of solve_device / solve_many_device, with their messages) and allocation of the outputs."""
+    @property
+    def uniform_order(self):
+        """True when every case has the same polynomial order: the adjoint then writes every column of grad_fi (with mixed orders
+        the columns beyond a case's own number of DOFs are not written)."""
+        order = np.asarray(self.order)
+        return bool((order == order[0]).all())
+
+    def _check_tensors(self, rank, names, slots, dofs):
+        """What the device-resident solves (rank 2; rank 3: stacks of fields) and their adjoints ask of their tensors, given as
+        ((tensor, name), ...): float64 on the device with a contiguous last axis, at least ncases rows, at least max_nk columns for
+        `slots` (fk, grad_fk) and max_no for `dofs` (fi, g, grad_fi), the same number of fields in a stack.  `names` are all the
+        names of the call, for the messages that speak of them together."""
         if not self.ready:
             raise RuntimeError("Solver is not in the ready state; prepare() must be called before solve()")
         import torch
-        want_fi = grad_fi is not False
-        given = [(g, "g")] + ([(grad_fk, "grad_fk")] if grad_fk is not None else []) \
-            + ([(grad_fi, "grad_fi")] if want_fi and grad_fi is not None else [])
+        given = slots + dofs
         for t, name in given:
             if t.dtype != torch.float64 or t.dim() != rank or not t.is_cuda or t.stride(rank - 1) != 1:
                 raise ValueError("%s must be a %d-D float64 device tensor with a contiguous last axis" % (name, rank))
-        lead = tuple(g.shape[:rank - 2])
-        if rank == 3 and (g.shape[0] < 1 or any(t.shape[0] != g.shape[0] for t, _ in given)):
-            raise ValueError("g, grad_fk and grad_fi must hold the same number (>= 1) of right-hand sides")
-        if any(t.shape[rank - 2] < self.ncases for t, _ in given) or (grad_fk is not None and grad_fk.shape[rank - 1] < self._max_nk):
-            raise ValueError("g/grad_fk/grad_fi are too small")
-        for t, name in given:
-            if name != "grad_fk" and t.shape[rank - 1] < self._max_no:
+        if rank == 3:
+            nrhs = given[0][0].shape[0]
+            for t, _ in given:
+                if nrhs < 1 or t.shape[0] != nrhs:
+                    raise ValueError("%s and %s must hold the same number (>= 1) of right-hand sides" % (", ".join(names[:-1]), names[-1]))
+        for t, _ in given:
+            if t.shape[rank - 2] < self.ncases:
+                raise ValueError("%s are too small" % "/".join(names))
+        for t, _ in slots:
+            if t.shape[rank - 1] < self._max_nk:
+                raise ValueError("%s are too small" % "/".join(names))
+        for t, name in dofs:
+            if t.shape[rank - 1] < self._max_no:
                 raise ValueError("%s has %d columns, need at least %d" % (name, t.shape[rank - 1], self._max_no))
-        for t, name in given:
+
+    def _adjoint_arguments(self, g, grad_fk, grad_fi, rank):
+        """Checks (those of solve_device / solve_many_device, with their messages) and allocation of the outputs."""
+        import torch
+        want_fi = grad_fi is not False
+        slots = ((grad_fk, "grad_fk"),) if grad_fk is not None else ()
+        dofs = ((g, "g"), (grad_fi, "grad_fi")) if want_fi and grad_fi is not None else ((g, "g"),)
+        self._check_tensors(rank, ("g", "grad_fk", "grad_fi"), slots, dofs)
+        for t, name in dofs + slots:
             if t.device.type != "cuda" or (t.device.index or 0) != self._device:
                 raise ValueError("%s must live on the solver's device (cuda:%d)" % (name, self._device))
+        lead = tuple(g.shape[:rank - 2])
         if grad_fk is None:
             grad_fk = torch.empty(lead + (self.ncases, self._max_nk), dtype=torch.float64, device=g.device)
         if want_fi and grad_fi is None:
-            # mixed orders: the columns beyond a case's own number of DOFs are not written
-            uniform = bool((np.asarray(self.order) == np.asarray(self.order)[0]).all())
-            grad_fi = (torch.empty if uniform else torch.zeros)(lead + (self.ncases, self._max_no), dtype=torch.float64, device=g.device)
+            grad_fi = (torch.empty if self.uniform_order else torch.zeros)(lead + (self.ncases, self._max_no), dtype=torch.float64,
+                                                                           device=g.device)
         return grad_fk, (grad_fi if want_fi else None)
 
     def solve_adjoint_device(self, g, grad_fk=None, grad_fi=None, stream=None):
@@ -432,11 +428,8 @@ class ExpertSolver:
         return grad_fk, grad_fi
 
     def _solve_adjoint(self, nrhs, g, sg_r, sg_j, gfk, sk_r, sk_j, slots, gfi, si_r, si_j, stream):
-        import torch
-        if stream is None:
-            stream = torch.cuda.current_stream(g.device).cuda_stream
         B.check(B.lib().wlsqm_hip_expert_solve_adjoint_device(
-            self._handle, C.c_void_p(int(stream) if stream else 0), int(nrhs), C.c_void_p(g.data_ptr()), int(sg_r), int(sg_j),
+            self._handle, whip._stream_ptr(g, stream), int(nrhs), C.c_void_p(g.data_ptr()), int(sg_r), int(sg_j),
             C.c_void_p(gfk.data_ptr()), int(sk_r), int(sk_j), int(slots),
             C.c_void_p(gfi.data_ptr()) if gfi is not None else None, int(si_r), int(si_j)))
 

@@ -115,69 +115,113 @@ def _ndofs(dimension, order):
     return _NDOF[dimension][int(order)]
 
 
+_FEW_ROWS = "%s has %d rows, fewer than the %d cases of the batch"
+
+
 def _rows(n, **arrays):
     """Every per-case array must cover the n cases of the launch (simple.py's _run_many makes the same checks on the host)."""
     for name, t in arrays.items():
         if t.shape[0] < n:
-            raise ValueError("%s has %d rows, fewer than the %d cases of the batch" % (name, t.shape[0], n))
+            raise ValueError(_FEW_ROWS % (name, t.shape[0], n))
 
 
-def _batch(dimension, order, xk, fk, nk, xi, fi, knowns, weighting_method, sens, iterative, max_iter, order_dummy):
+def _double_rows(t, name, nrows, ncols, of=None, says=None):
+    """fi, g, grad_fi, slots: a float64 device tensor (>= nrows, >= ncols) with a contiguous last axis.  `of`: the (dimension, order)
+    that ncols is the number of DOFs of, for the callers whose message names them; `says` is a caller's own sentence for a wrong
+    layout or extent, raised in place of the three below."""
+    _check(t, name, "float64", 2)
+    if says is not None:
+        if t.shape[0] < nrows or t.shape[1] < ncols or t.stride(1) != 1:
+            raise ValueError(says)
+        return
+    if t.stride(1) != 1:
+        raise ValueError("Buffer and memoryview are not contiguous in the same dimension. (argument %s)" % name)
+    if t.shape[0] < nrows:
+        raise ValueError(_FEW_ROWS % (name, t.shape[0], nrows))
+    if t.shape[1] < ncols:
+        raise ValueError("%s has %d columns, need at least number_of_dofs%s = %d" % (name, t.shape[1], "(%d, %d)" % of if of else "", ncols))
+
+
+def _dense_geometry(dimension, xk, nk, xi, knowns, weighting_method):
+    """The geometry of a dense batch, checked and put into a B.Batch (the forward adds fk, fi and sens, the adjoint g and its outputs):
+    xk (n, K, dim) [1D: (n, K)], nk (n,) int32, xi (n, dim) [1D: (n,)], knowns (n,) int64, weighting_method (n,) int32."""
     ncases = nk.shape[0]
-    no = _ndofs(dimension, order)
     _check(nk, "nk", "int32", 1); _check(knowns, "knowns", "int64", 1); _check(weighting_method, "weighting_method", "int32", 1)
-    _check(fk, "fk", "float64", 2); _check(fi, "fi", "float64", 2)
     if dimension == 1:
         _check(xk, "xk", "float64", 2); _check(xi, "xi", "float64", 1)
     else:
         _check(xk, "xk", "float64", 3); _check(xi, "xi", "float64", 2)
         if xk.stride(2) != 1 or xi.stride(1) != 1:
             raise ValueError("Buffer and memoryview are not contiguous in the same dimension.")
-    if fi.stride(1) != 1:
-        raise ValueError("Buffer and memoryview are not contiguous in the same dimension. (argument fi)")
+        if xk.shape[2] < dimension or xi.shape[1] < dimension:
+            raise ValueError("xk / xi must have %d coordinates on the last axis" % dimension)
+    _rows(ncases, xk=xk, xi=xi, knowns=knowns, weighting_method=weighting_method)
+    b = B.Batch()
+    b.dimension, b.ncases = dimension, ncases
+    b.xk, b.xk_stride_case, b.xk_stride_k = xk.data_ptr(), xk.stride(0), xk.stride(1)
+    b.nk, b.nk_stride = nk.data_ptr(), nk.stride(0)
+    b.xi, b.xi_stride_case = xi.data_ptr(), xi.stride(0)
+    b.knowns, b.knowns_stride = knowns.data_ptr(), knowns.stride(0)
+    b.weighting_method, b.wm_stride = weighting_method.data_ptr(), weighting_method.stride(0)
+    return b
+
+
+def _batch(dimension, order, xk, fk, nk, xi, fi, knowns, weighting_method, sens, iterative, max_iter, order_dummy):
+    no = _ndofs(dimension, order)
+    b = _dense_geometry(dimension, xk, nk, xi, knowns, weighting_method)
+    ncases = b.ncases
     # extents: the kernels write `no` doubles per fi row at the row pitch and read K neighbour slots per xk / fk row
-    _rows(ncases, xk=xk, fk=fk, xi=xi, fi=fi, knowns=knowns, weighting_method=weighting_method)
+    _check(fk, "fk", "float64", 2)
+    if fk.shape[0] < ncases:
+        raise ValueError(_FEW_ROWS % ("fk", fk.shape[0], ncases))
     K = int(fk.shape[1])
     if xk.shape[1] < K:
         raise ValueError("xk has %d neighbour slots per case, fk has %d" % (xk.shape[1], K))
-    if dimension > 1 and (xk.shape[2] < dimension or xi.shape[1] < dimension):
-        raise ValueError("xk / xi must have %d coordinates on the last axis" % dimension)
-    if fi.shape[1] < no:
-        raise ValueError("fi has %d columns, need at least number_of_dofs(%d, %d) = %d" % (fi.shape[1], dimension, order, no))
+    _double_rows(fi, "fi", ncases, no, (dimension, order))
     if sens is not None:
         _check(sens, "sens", "float64", 3)
         if sens.stride(2) != 1:
             raise ValueError("Buffer and memoryview are not contiguous in the same dimension. (argument sens)")
         if sens.shape[0] < ncases or sens.shape[1] < K or sens.shape[2] < no:
             raise ValueError("sens must be at least (ncases, %d, %d); got %s" % (K, no, tuple(sens.shape)))
-    b = B.Batch()
-    b.dimension, b.ncases = dimension, ncases
-    b.xk, b.xk_stride_case, b.xk_stride_k = xk.data_ptr(), xk.stride(0), xk.stride(1)
-    b.fk, b.fk_stride_case, b.fk_stride_k = fk.data_ptr(), fk.stride(0), fk.stride(1)
-    b.nk, b.nk_stride = nk.data_ptr(), nk.stride(0)
-    b.xi, b.xi_stride_case = xi.data_ptr(), xi.stride(0)
-    b.fi, b.fi_stride_case = fi.data_ptr(), fi.stride(0)
-    if sens is not None:
         b.do_sens = 1
         b.sens, b.sens_stride_case, b.sens_stride_k = sens.data_ptr(), sens.stride(0), sens.stride(1)
+    b.fk, b.fk_stride_case, b.fk_stride_k = fk.data_ptr(), fk.stride(0), fk.stride(1)
+    b.fi, b.fi_stride_case = fi.data_ptr(), fi.stride(0)
     # the per-case order array is not read on this path (order_uniform is); point it somewhere valid
     b.order, b.order_stride = order_dummy.data_ptr(), 0
-    b.knowns, b.knowns_stride = knowns.data_ptr(), knowns.stride(0)
-    b.weighting_method, b.wm_stride = weighting_method.data_ptr(), weighting_method.stride(0)
-    b.iterative, b.max_iter, b.max_nk = (1 if iterative else 0), int(max_iter), int(fk.shape[1])
+    b.iterative, b.max_iter, b.max_nk = (1 if iterative else 0), int(max_iter), K
     return b
 
 
+def _case_index(case_index):
+    """(pointer, count) of the cases a launch is restricted to (an int64 device tensor), (None, 0) without one."""
+    if case_index is None:
+        return None, 0
+    _check(case_index, "case_index", "int64", 1)
+    return C.c_void_p(case_index.data_ptr()), int(case_index.shape[0])
+
+
 def _strict_ctx(flag):
+    # the entry points below take a `strict=` parameter, which hides the context manager of that name inside them
     return strict(flag)
 
 
-def _stream_and_device(t, stream):
-    import torch
-    dev = t.device.index if t.device.index is not None else torch.cuda.current_device()
+def _stream_ptr(where, stream):
+    """The HIP stream of a launch as a c_void_p: `stream`, or (None) torch's current stream on the device of `where`, a tensor, a
+    torch device or a device number (None: torch's current device)."""
     if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    return C.c_void_p(int(stream) if stream else 0), dev
+        import torch
+        stream = torch.cuda.current_stream(getattr(where, "device", where)).cuda_stream
+    return C.c_void_p(int(stream) if stream else 0)
+
+
+def _stream_and_device(t, stream):
+    dev = t.device.index
+    if dev is None:
+        import torch
+        dev = torch.cuda.current_device()
+    return _stream_ptr(dev, stream), dev
 
 
 class row_hint:
@@ -237,11 +281,7 @@ def fit_many_device(dimension, order, xk, fk, nk, xi, fi, knowns, weighting_meth
     b = _batch(dimension, order, xk, fk, nk, xi, fi, knowns, weighting_method, sens, iterative, max_iter, nk)
     s, dev = _stream_and_device(fi, stream)
     its = C.c_int32(0)
-    nsel = 0
-    ci = None
-    if case_index is not None:
-        _check(case_index, "case_index", "int64", 1)
-        ci, nsel = C.c_void_p(case_index.data_ptr()), int(case_index.shape[0])
+    ci, nsel = _case_index(case_index)
     with _strict_ctx(strict):
         B.check(B.lib().wlsqm_hip_fit_many_device(C.byref(b), dev, s, int(order), ci, nsel,
                                                   C.byref(its) if want_iterations else None))
@@ -273,30 +313,41 @@ def time_fit_device(dimension, order, xk, fk, nk, xi, fi, knowns, weighting_meth
     return float(ms.value)
 
 
-def _cloud_args(dimension, order, S, F, hoods, fi, nk, knowns, weighting_method, point_index):
-    _check(F, "F", "float64", 1); _check(hoods, "hoods", "int32", 2); _check(fi, "fi", "float64", 2)
+def _cloud_geometry(dimension, S, hoods, nk, knowns, weighting_method, point_index, layout):
+    """The geometry of an index-based batch, checked (the forward adds F, fi and sens, the adjoint g and its outputs): S (npoints, dim)
+    [1D: (npoints,)] contiguous, hoods (ncases, K) int32, nk / knowns / weighting_method per case with unit stride, point_index
+    (ncases,) int32 or None.  `layout` is the caller's sentence about contiguity, which also names its own arrays.  Returns
+    (ncases, K)."""
+    _check(hoods, "hoods", "int32", 2)
     _check(S, "S", "float64", 1 if dimension == 1 else 2)
     _check(nk, "nk", "int32", 1); _check(knowns, "knowns", "int64", 1); _check(weighting_method, "weighting_method", "int32", 1)
-    if not S.is_contiguous() or not F.is_contiguous() or hoods.stride(1) != 1 or fi.stride(1) != 1:
-        raise ValueError("S, F must be contiguous; hoods and fi must have a contiguous last axis")
+    if not S.is_contiguous() or hoods.stride(1) != 1:
+        raise ValueError(layout)
     for t in (nk, knowns, weighting_method):
         if t.stride(0) != 1:
             raise ValueError("nk, knowns, weighting_method must have unit stride")
+    ncases, K = int(hoods.shape[0]), int(hoods.shape[1])
+    _rows(ncases, nk=nk, knowns=knowns, weighting_method=weighting_method)
     if point_index is not None:
         _check(point_index, "point_index", "int32", 1)
-    ncases, K = int(hoods.shape[0]), int(hoods.shape[1])
-    no = _ndofs(dimension, order)
-    _rows(ncases, fi=fi, nk=nk, knowns=knowns, weighting_method=weighting_method)
-    if point_index is not None:
         _rows(ncases, point_index=point_index)
     elif S.shape[0] < ncases:
         raise ValueError("S has %d points but there are %d cases (xi of case j is S[j] without point_index)" % (S.shape[0], ncases))
     if dimension > 1 and S.shape[1] != dimension:
         raise ValueError("S must be (npoints, %d)" % dimension)
+    return ncases, K
+
+
+def _cloud_args(dimension, order, S, F, hoods, fi, nk, knowns, weighting_method, point_index):
+    no = _ndofs(dimension, order)
+    layout = "S, F must be contiguous; hoods and fi must have a contiguous last axis"
+    _check(F, "F", "float64", 1); _check(fi, "fi", "float64", 2)
+    if not F.is_contiguous() or fi.stride(1) != 1:
+        raise ValueError(layout)
+    ncases, K = _cloud_geometry(dimension, S, hoods, nk, knowns, weighting_method, point_index, layout)
     if F.shape[0] < S.shape[0]:
         raise ValueError("F has fewer entries than S has points")
-    if fi.shape[1] < no:
-        raise ValueError("fi has %d columns, need at least number_of_dofs(%d, %d) = %d" % (fi.shape[1], dimension, order, no))
+    _double_rows(fi, "fi", ncases, no, (dimension, order))
     return [int(dimension), int(order), ncases, K, _ptr(S), _ptr(F), _ptr(hoods), int(hoods.stride(0)), _ptr(point_index),
             _ptr(nk), _ptr(knowns), _ptr(weighting_method), _ptr(fi), int(fi.stride(0))]
 
@@ -348,16 +399,6 @@ def _adjoint_order(dimension, order):
     return no
 
 
-def _adjoint_rows(t, name, ncases, no):
-    """g / grad_fi: float64 device tensor (>= ncases, >= no), contiguous last axis."""
-    _check(t, name, "float64", 2)
-    if t.stride(1) != 1:
-        raise ValueError("Buffer and memoryview are not contiguous in the same dimension. (argument %s)" % name)
-    _rows(ncases, **{name: t})
-    if t.shape[1] < no:
-        raise ValueError("%s has %d columns, need at least number_of_dofs = %d" % (name, t.shape[1], no))
-
-
 def fit_many_adjoint_device(dimension, order, xk, nk, xi, knowns, weighting_method, g, grad_fk=None, grad_fi=None, case_index=None,
                             stream=None):
     """The vector-Jacobian product of fit_many_device (basic fit, integer `order`): given g (n, >= no) = dL/dfi_out, returns
@@ -373,19 +414,10 @@ def fit_many_adjoint_device(dimension, order, xk, nk, xi, knowns, weighting_meth
     same linear map differently.  3D orders 3 and 4 are not covered (ValueError)."""
     import torch
     no = _adjoint_order(dimension, order)
-    ncases = nk.shape[0]
-    _check(nk, "nk", "int32", 1); _check(knowns, "knowns", "int64", 1); _check(weighting_method, "weighting_method", "int32", 1)
-    if dimension == 1:
-        _check(xk, "xk", "float64", 2); _check(xi, "xi", "float64", 1)
-    else:
-        _check(xk, "xk", "float64", 3); _check(xi, "xi", "float64", 2)
-        if xk.stride(2) != 1 or xi.stride(1) != 1:
-            raise ValueError("Buffer and memoryview are not contiguous in the same dimension.")
-        if xk.shape[2] < dimension or xi.shape[1] < dimension:
-            raise ValueError("xk / xi must have %d coordinates on the last axis" % dimension)
-    _rows(ncases, xk=xk, xi=xi, knowns=knowns, weighting_method=weighting_method)
-    _adjoint_rows(g, "g", ncases, no)
-    K = int(xk.shape[1])
+    b = _dense_geometry(dimension, xk, nk, xi, knowns, weighting_method)
+    ncases, K = b.ncases, int(xk.shape[1])
+    b.max_nk = K
+    _double_rows(g, "g", ncases, no)
     new = torch.zeros if case_index is not None else torch.empty
     if grad_fk is None:
         grad_fk = new((ncases, K), dtype=torch.float64, device=g.device)
@@ -398,21 +430,10 @@ def fit_many_adjoint_device(dimension, order, xk, nk, xi, knowns, weighting_meth
     elif grad_fi is False:
         grad_fi = None
     if grad_fi is not None:
-        _adjoint_rows(grad_fi, "grad_fi", ncases, no)
+        _double_rows(grad_fi, "grad_fi", ncases, no)
     _same_device(g, xk, nk, xi, knowns, weighting_method, grad_fk, grad_fi, case_index)
-    b = B.Batch()
-    b.dimension, b.ncases = dimension, ncases
-    b.xk, b.xk_stride_case, b.xk_stride_k = xk.data_ptr(), xk.stride(0), xk.stride(1)
-    b.nk, b.nk_stride = nk.data_ptr(), nk.stride(0)
-    b.xi, b.xi_stride_case = xi.data_ptr(), xi.stride(0)
-    b.knowns, b.knowns_stride = knowns.data_ptr(), knowns.stride(0)
-    b.weighting_method, b.wm_stride = weighting_method.data_ptr(), weighting_method.stride(0)
-    b.max_nk = K
     s, dev = _stream_and_device(g, stream)
-    ci, nsel = None, 0
-    if case_index is not None:
-        _check(case_index, "case_index", "int64", 1)
-        ci, nsel = C.c_void_p(case_index.data_ptr()), int(case_index.shape[0])
+    ci, nsel = _case_index(case_index)
     B.check(B.lib().wlsqm_hip_fit_adjoint_device(C.byref(b), dev, s, int(order), _ptr(g), int(g.stride(0)),
                                                  _ptr(grad_fk), int(grad_fk.stride(0)), int(grad_fk.stride(1)),
                                                  _ptr(grad_fi), int(grad_fi.stride(0)) if grad_fi is not None else 0, ci, nsel))
@@ -429,36 +450,19 @@ def fit_cloud_adjoint_device(dimension, order, S, hoods, nk, knowns, weighting_m
     (ncases, K) that receives the per-slot gradients (allocated otherwise).  Asynchronous on `stream`."""
     import torch
     no = _adjoint_order(dimension, order)
-    _check(hoods, "hoods", "int32", 2)
-    _check(S, "S", "float64", 1 if dimension == 1 else 2)
-    _check(nk, "nk", "int32", 1); _check(knowns, "knowns", "int64", 1); _check(weighting_method, "weighting_method", "int32", 1)
-    if not S.is_contiguous() or hoods.stride(1) != 1:
-        raise ValueError("S must be contiguous; hoods must have a contiguous last axis")
-    for t in (nk, knowns, weighting_method):
-        if t.stride(0) != 1:
-            raise ValueError("nk, knowns, weighting_method must have unit stride")
-    ncases, K = int(hoods.shape[0]), int(hoods.shape[1])
+    ncases, K = _cloud_geometry(dimension, S, hoods, nk, knowns, weighting_method, point_index,
+                                "S must be contiguous; hoods must have a contiguous last axis")
     npoints = int(S.shape[0])
-    _rows(ncases, nk=nk, knowns=knowns, weighting_method=weighting_method)
-    if point_index is not None:
-        _check(point_index, "point_index", "int32", 1)
-        _rows(ncases, point_index=point_index)
-    elif npoints < ncases:
-        raise ValueError("S has %d points but there are %d cases (xi of case j is S[j] without point_index)" % (npoints, ncases))
-    if dimension > 1 and S.shape[1] != dimension:
-        raise ValueError("S must be (npoints, %d)" % dimension)
-    _adjoint_rows(g, "g", ncases, no)
+    _double_rows(g, "g", ncases, no)
     if slots is None:
         slots = torch.empty((ncases, K), dtype=torch.float64, device=g.device)
-    _check(slots, "slots", "float64", 2)
-    if slots.shape[0] < ncases or slots.shape[1] < K or slots.stride(1) != 1:
-        raise ValueError("slots must be at least (ncases, %d) with a contiguous last axis; got %s" % (K, tuple(slots.shape)))
+    _double_rows(slots, "slots", ncases, K, says="slots must be at least (ncases, %d) with a contiguous last axis; got %s" % (K, tuple(slots.shape)))
     if grad_fi is None:
         grad_fi = torch.empty((ncases, no), dtype=torch.float64, device=g.device)
     elif grad_fi is False:
         grad_fi = None
     if grad_fi is not None:
-        _adjoint_rows(grad_fi, "grad_fi", ncases, no)
+        _double_rows(grad_fi, "grad_fi", ncases, no)
     if grad_F is None:
         grad_F = torch.zeros((npoints,), dtype=torch.float64, device=g.device)
     else:
@@ -481,20 +485,43 @@ def fit_cloud_adjoint_device(dimension, order, S, hoods, nk, knowns, weighting_m
     return grad_F, grad_fi
 
 
+# ---- autograd: gradients through the fits, the prepared solver (ExpertSolver.solve_adjoint_device; csrc/solve_op.hip, DESIGN.md
+# section 13) and the evaluation of a plan (InterpolationPlan.evaluate_adjoint) ----
+
 _AUTOGRAD = None
 
 
-def _autograd_functions():
-    """The two torch.autograd.Function classes (made at first use: the module does not import torch)."""
+def _autograd():
+    """The torch.autograd.Function classes behind the differentiable_* functions, as a namespace with FitMany, FitCloud, Solve and
+    Evaluate (made at first use: the module does not import torch).  Every forward takes its tensor inputs first."""
     global _AUTOGRAD
     if _AUTOGRAD is not None:
         return _AUTOGRAD
+    import types
     import torch
     from torch.autograd.function import once_differentiable
 
-    def pass_through(g, ncases, no):
-        """dL/dfi_in starts as a copy of g where fi has rows or columns the fit never touches (they leave as they came in)."""
-        return g.clone() if (g.shape[0] != ncases or g.shape[1] != no) else None
+    def gradients(ctx, gout, ntensors, adjoint):
+        """The frame of every backward pass: one entry per input of the forward, None for all of them when no tensor input wants
+        a gradient (nothing is launched), else what adjoint(g, *wanted) returns for the tensor inputs that want theirs."""
+        wanted = ctx.needs_input_grad[:ntensors]
+        out = [None] * len(ctx.needs_input_grad)
+        if any(wanted):
+            for i, grad in enumerate(adjoint(gout.contiguous(), *wanted)):
+                if wanted[i]:
+                    out[i] = grad
+        return tuple(out)
+
+    def buffer(shape, g, covered):
+        """A gradient the adjoint kernel writes into: uninitialised when the kernel covers every element of it, zeros otherwise."""
+        return (torch.empty if covered else torch.zeros)(shape, dtype=torch.float64, device=g.device)
+
+    def grad_fi_start(g, wanted, covered):
+        """The grad_fi argument of an in-place fit's adjoint: False when not wanted; a copy of g when fi has rows or columns the
+        forward never touches (they leave as they came in, so dL/dfi_in is g there); None (the adjoint allocates) otherwise."""
+        if not wanted:
+            return False
+        return None if covered else g.clone()
 
     class FitMany(torch.autograd.Function):
         @staticmethod
@@ -507,17 +534,14 @@ def _autograd_functions():
         @staticmethod
         @once_differentiable
         def backward(ctx, gout):
-            dimension, order, xk, nk, xi, knowns, weighting_method, stream, fk_shape = ctx.geometry
-            need_fk, need_fi = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-            if not (need_fk or need_fi):
-                return (None,) * 11
-            g = gout.contiguous()
-            ncases, K, no = int(nk.shape[0]), int(fk_shape[1]), _ndofs(dimension, order)
-            gfk = (torch.zeros if fk_shape[0] != ncases else torch.empty)(fk_shape, dtype=torch.float64, device=g.device)
-            gfi = pass_through(g, ncases, no) if need_fi else False
-            _, gfi = fit_many_adjoint_device(dimension, order, xk[:, :K], nk, xi, knowns, weighting_method, g, grad_fk=gfk,
-                                             grad_fi=gfi, stream=stream)
-            return (gfk if need_fk else None, gfi if need_fi else None) + (None,) * 9
+            def adjoint(g, need_fk, need_fi):
+                dimension, order, xk, nk, xi, knowns, weighting_method, stream, fk_shape = ctx.geometry
+                ncases, K, no = int(nk.shape[0]), int(fk_shape[1]), _ndofs(dimension, order)
+                gfk = buffer(fk_shape, g, fk_shape[0] == ncases)
+                gfi = grad_fi_start(g, need_fi, g.shape[0] == ncases and g.shape[1] == no)
+                return fit_many_adjoint_device(dimension, order, xk[:, :K], nk, xi, knowns, weighting_method, g, grad_fk=gfk,
+                                               grad_fi=gfi, stream=stream)
+            return gradients(ctx, gout, 2, adjoint)
 
     class FitCloud(torch.autograd.Function):
         @staticmethod
@@ -531,58 +555,13 @@ def _autograd_functions():
         @staticmethod
         @once_differentiable
         def backward(ctx, gout):
-            dimension, order, S, hoods, nk, knowns, weighting_method, point_index, stream, F_shape = ctx.geometry
-            need_F, need_fi = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-            if not (need_F or need_fi):
-                return (None,) * 12
-            g = gout.contiguous()
-            gF = torch.empty(F_shape, dtype=torch.float64, device=g.device)
-            gfi = pass_through(g, int(hoods.shape[0]), _ndofs(dimension, order)) if need_fi else False
-            _, gfi = fit_cloud_adjoint_device(dimension, order, S, hoods, nk, knowns, weighting_method, g, point_index=point_index,
-                                              grad_F=gF, grad_fi=gfi, stream=stream)
-            return (gF if need_F else None, gfi if need_fi else None) + (None,) * 10
-
-    _AUTOGRAD = (FitMany, FitCloud)
-    return _AUTOGRAD
-
-
-def _no_geometry_grad(*tensors):
-    for t in tensors:
-        if t is not None and getattr(t, "requires_grad", False):
-            raise ValueError("the geometry is not differentiable")
-
-
-def differentiable_fit_many(dimension, order, xk, fk, nk, xi, fi, knowns, weighting_method, strict=None, stream=None):
-    """fit_many_device as a differentiable function of fk and fi: returns fi_out, a NEW tensor (fi is cloned, the fit runs in place on
-    the clone), through which autograd reaches fk and fi (the basic fit, integer `order`; refinement is not offered: its stop test
-    is data-dependent).  The backward pass is fit_many_adjoint_device: one kernel, computed only for the inputs that require a gradient;
-    it always runs the fast arithmetic, whatever `strict` the forward used.  The geometry (xk, xi) is not differentiable:
-    ValueError when it requires a gradient.  Once differentiable."""
-    _adjoint_order(dimension, order)
-    _no_geometry_grad(xk, xi)
-    return _autograd_functions()[0].apply(fk, fi, dimension, int(order), xk, nk, xi, knowns, weighting_method, strict, stream)
-
-
-def differentiable_fit_cloud(dimension, order, S, F, hoods, fi, nk, knowns, weighting_method, point_index=None, strict=None, stream=None):
-    """fit_cloud_device as a differentiable function of the field F (npoints,) and of fi: returns fi_out, a new tensor.  The backward
-    pass is fit_cloud_adjoint_device (index-based kernel + one index_add_ into dL/dF).  S is not differentiable (ValueError)."""
-    _adjoint_order(dimension, order)
-    _no_geometry_grad(S)
-    return _autograd_functions()[1].apply(F, fi, dimension, int(order), S, hoods, nk, knowns, weighting_method, point_index, strict, stream)
-
-
-# ---- gradients through the prepared solver (ExpertSolver.solve_adjoint_device; csrc/solve_op.hip, DESIGN.md section 13) ----
-
-_AUTOGRAD_SOLVE = None
-
-
-def _autograd_solve():
-    """The torch.autograd.Function behind differentiable_solve / differentiable_solve_many (made at first use)."""
-    global _AUTOGRAD_SOLVE
-    if _AUTOGRAD_SOLVE is not None:
-        return _AUTOGRAD_SOLVE
-    import torch
-    from torch.autograd.function import once_differentiable
+            def adjoint(g, need_F, need_fi):
+                dimension, order, S, hoods, nk, knowns, weighting_method, point_index, stream, F_shape = ctx.geometry
+                gF = buffer(F_shape, g, True)
+                gfi = grad_fi_start(g, need_fi, g.shape[0] == int(hoods.shape[0]) and g.shape[1] == _ndofs(dimension, order))
+                return fit_cloud_adjoint_device(dimension, order, S, hoods, nk, knowns, weighting_method, g, point_index=point_index,
+                                                grad_F=gF, grad_fi=gfi, stream=stream)
+            return gradients(ctx, gout, 2, adjoint)
 
     class Solve(torch.autograd.Function):
         @staticmethod
@@ -595,41 +574,65 @@ def _autograd_solve():
         @staticmethod
         @once_differentiable
         def backward(ctx, gout):
-            solver, stream, many, fk_shape, fi_shape = ctx.call
-            need_fk, need_fi = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-            if not (need_fk or need_fi):
-                return (None,) * 5
-            g = gout.contiguous()
-            # rows beyond ncases receive no gradient (the columns beyond the solver's slots are zero-filled by the call itself)
-            gfk = (torch.zeros if fk_shape[-2] != solver.ncases else torch.empty)(fk_shape, dtype=torch.float64, device=g.device)
-            gfi = False
-            if need_fi:
-                # rows and columns of fi that the solve never touches leave as they came in: dL/dfi_in starts as a copy of g there
-                uniform = bool((solver.order == solver.order[0]).all())
-                exact = uniform and fi_shape[-2] == solver.ncases and fi_shape[-1] == solver._max_no
-                gfi = None if exact else g.clone()
-            adjoint = solver.solve_many_adjoint_device if many else solver.solve_adjoint_device
-            _, gfi = adjoint(g, grad_fk=gfk, grad_fi=gfi, stream=stream)
-            return (gfk if need_fk else None, gfi if need_fi else None, None, None, None)
+            def adjoint(g, need_fk, need_fi):
+                solver, stream, many, fk_shape, fi_shape = ctx.call
+                # rows beyond ncases receive no gradient (the columns beyond the solver's slots are zero-filled by the call itself)
+                gfk = buffer(fk_shape, g, fk_shape[-2] == solver.ncases)
+                gfi = grad_fi_start(g, need_fi, need_fi and fi_shape[-2] == solver.ncases and fi_shape[-1] == solver._max_no
+                                    and solver.uniform_order)
+                return (solver.solve_many_adjoint_device if many else solver.solve_adjoint_device)(g, grad_fk=gfk, grad_fi=gfi,
+                                                                                                   stream=stream)
+            return gradients(ctx, gout, 2, adjoint)
 
-    _AUTOGRAD_SOLVE = Solve
-    return Solve
+    class Evaluate(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, fi, plan, diff, stream):
+            ctx.call = (plan, diff, stream, tuple(fi.shape))
+            return plan.evaluate(diff, fi.detach(), stream=stream)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gout):
+            def adjoint(g, need_fi):
+                plan, diff, stream, fi_shape = ctx.call
+                # rows beyond nmodels and columns beyond the plan's DOFs are never read by the forward: zeros
+                gfi = buffer(fi_shape, g, fi_shape[-2] == plan.nmodels and fi_shape[-1] == plan._max_no)
+                return (plan.evaluate_adjoint(g, diff, grad_fi=gfi, stream=stream),)
+            return gradients(ctx, gout, 1, adjoint)
+
+    _AUTOGRAD = types.SimpleNamespace(FitMany=FitMany, FitCloud=FitCloud, Solve=Solve, Evaluate=Evaluate)
+    return _AUTOGRAD
+
+
+def _no_geometry_grad(*geometry):
+    """The tensors a fit's geometry is made of, or a plan (which remembers whether the tensors it was made from required one)."""
+    for t in geometry:
+        if t is not None and (getattr(t, "requires_grad", False) or getattr(t, "_geometry_requires_grad", False)):
+            raise ValueError("the geometry is not differentiable")
+
+
+def differentiable_fit_many(dimension, order, xk, fk, nk, xi, fi, knowns, weighting_method, strict=None, stream=None):
+    """fit_many_device as a differentiable function of fk and fi: returns fi_out, a NEW tensor (fi is cloned, the fit runs in place on
+    the clone), through which autograd reaches fk and fi (the basic fit, integer `order`; refinement is not offered: its stop test
+    is data-dependent).  The backward pass is fit_many_adjoint_device: one kernel, computed only for the inputs that require a gradient;
+    it always runs the fast arithmetic, whatever `strict` the forward used.  The geometry (xk, xi) is not differentiable:
+    ValueError when it requires a gradient.  Once differentiable."""
+    _adjoint_order(dimension, order)
+    _no_geometry_grad(xk, xi)
+    return _autograd().FitMany.apply(fk, fi, dimension, int(order), xk, nk, xi, knowns, weighting_method, strict, stream)
+
+
+def differentiable_fit_cloud(dimension, order, S, F, hoods, fi, nk, knowns, weighting_method, point_index=None, strict=None, stream=None):
+    """fit_cloud_device as a differentiable function of the field F (npoints,) and of fi: returns fi_out, a new tensor.  The backward
+    pass is fit_cloud_adjoint_device (index-based kernel + one index_add_ into dL/dF).  S is not differentiable (ValueError)."""
+    _adjoint_order(dimension, order)
+    _no_geometry_grad(S)
+    return _autograd().FitCloud.apply(F, fi, dimension, int(order), S, hoods, nk, knowns, weighting_method, point_index, strict, stream)
 
 
 def _differentiable_solve(solver, fk, fi, stream, many):
-    rank = 3 if many else 2
-    if not solver.ready:
-        raise RuntimeError("Solver is not in the ready state; prepare() must be called before solve()")
-    for t, name in ((fk, "fk"), (fi, "fi")):
-        if str(t.dtype).split(".")[-1] != "float64" or t.dim() != rank or not t.is_cuda or t.stride(rank - 1) != 1:
-            raise ValueError("%s must be a %d-D float64 device tensor with a contiguous last axis" % (name, rank))
-    if many and (fk.shape[0] != fi.shape[0] or fk.shape[0] < 1):
-        raise ValueError("fk and fi must hold the same number (>= 1) of right-hand sides")
-    if fk.shape[rank - 2] < solver.ncases or fi.shape[rank - 2] < solver.ncases or fk.shape[rank - 1] < solver._max_nk:
-        raise ValueError("fk/fi are too small")
-    if fi.shape[rank - 1] < solver._max_no:
-        raise ValueError("fi has %d columns, need at least %d" % (fi.shape[rank - 1], solver._max_no))
-    return _autograd_solve().apply(fk, fi, solver, stream, many)
+    solver._check_tensors(3 if many else 2, ("fk", "fi"), ((fk, "fk"),), ((fi, "fi"),))      # before anything is cloned
+    return _autograd().Solve.apply(fk, fi, solver, stream, many)
 
 
 def differentiable_solve(solver, fk, fi, stream=None):
@@ -842,11 +845,14 @@ class InterpolationPlan:
             raise RuntimeError("the interpolation plan has been closed")
         return self._handle
 
-    def _stream(self, stream):
-        import torch
-        if stream is None:
-            stream = torch.cuda.current_stream(self._device).cuda_stream
-        return C.c_void_p(int(stream) if stream else 0)
+    def _result(self, single, ndiff, stacked, R, t=None):
+        """(shape, field stride, diff stride) of what evaluate returns for an int diff (single) or ndiff of them, for one field or a
+        stack of R: the strides are those of `t`, a tensor of that shape (0 for an axis the result does not have, and both 0 without
+        a tensor or for one of another rank, which the caller rejects)."""
+        shape = ((R,) if stacked else ()) + (() if single else (ndiff,)) + (self.nx,)
+        if t is None or t.dim() != len(shape):
+            return shape, 0, 0
+        return shape, (int(t.stride(0)) if stacked else 0), (0 if single else int(t.stride(1 if stacked else 0)))
 
     def memory_used(self):
         """Bytes of device memory the plan holds."""
@@ -863,7 +869,7 @@ class InterpolationPlan:
             import torch
             out = torch.empty((self.nx,), dtype=torch.int64, device=self._device)
             if self.nx > 0:
-                B.check(B.lib().wlsqm_hip_interp_plan_export(self._live(), self._stream(None), _ptr(out), None))
+                B.check(B.lib().wlsqm_hip_interp_plan_export(self._live(), _stream_ptr(self._device, None), _ptr(out), None))
             self._I = out
         return self._I
 
@@ -877,7 +883,7 @@ class InterpolationPlan:
         B.check(B.lib().wlsqm_hip_interp_plan_info(self._live(), None, C.byref(n), None, None))
         off = torch.empty((self.nx + 1,), dtype=torch.int64, device=self._device)
         idx = torch.empty((int(n.value),), dtype=torch.int64, device=self._device)
-        B.check(B.lib().wlsqm_hip_interp_plan_export(self._handle, self._stream(None), _ptr(off), _ptr(idx) if n.value else None))
+        B.check(B.lib().wlsqm_hip_interp_plan_export(self._handle, _stream_ptr(self._device, None), _ptr(off), _ptr(idx) if n.value else None))
         return off, idx
 
     def evaluate(self, diff=0, fi=None, out=None, stream=None):
@@ -908,19 +914,18 @@ class InterpolationPlan:
             if fi.shape[-2] < self.nmodels or fi.shape[-1] < self._max_no or (fi.shape[-1] > 1 and fi.stride(-1) != 1):
                 raise ValueError("fi must be (nmodels, >= no) = (%d, >= %d), or a stack of those, with a contiguous last axis; got %s"
                                  % (self.nmodels, self._max_no, tuple(fi.shape)))
-        shape = ((R,) if stacked else ()) + (() if single else (ndiff,)) + (self.nx,)
+        shape, so_f, so_d = self._result(single, ndiff, stacked, R, out)
         if out is None:
             out = torch.empty(shape, dtype=torch.float64, device=self._device)
+            _, so_f, so_d = self._result(single, ndiff, stacked, R, out)
         else:
             _check(out, "out", "float64", len(shape))
             if tuple(out.shape) != shape or out.device != self._device or (self.nx > 1 and out.stride(-1) != 1):
                 raise ValueError("out must be a float64 device tensor of shape %s with a contiguous last axis" % (shape,))
         if self.nx == 0 or ndiff == 0 or R == 0:
             return out
-        so_f = int(out.stride(0)) if stacked else 0
-        so_d = 0 if single else int(out.stride(1 if stacked else 0))
         arr = (C.c_int32 * ndiff)(*diffs)
-        s = self._stream(stream)
+        s = _stream_ptr(self._device, stream)
         if fi is None:
             B.check(B.lib().wlsqm_hip_interp_plan_eval_expert(h, solver._handle, s, arr, ndiff, _ptr(out), so_d))
         else:
@@ -938,7 +943,7 @@ class InterpolationPlan:
         h = self._live()
         had = self.adjoint_info()["built"]
         built = C.c_int(0)
-        B.check(B.lib().wlsqm_hip_interp_plan_prepare_adjoint(h, self._stream(stream), C.byref(built)))
+        B.check(B.lib().wlsqm_hip_interp_plan_prepare_adjoint(h, _stream_ptr(self._device, stream), C.byref(built)))
         return bool(built.value) and not had
 
     def adjoint_info(self):
@@ -961,7 +966,7 @@ class InterpolationPlan:
         n = self.adjoint_info()["nentries"]
         toff = torch.empty((self.nmodels + 1,), dtype=torch.int64, device=self._device)
         tpt = torch.empty((n,), dtype=torch.int64, device=self._device)
-        B.check(B.lib().wlsqm_hip_interp_plan_export_transposed(h, self._stream(None), _ptr(toff), _ptr(tpt) if n else None))
+        B.check(B.lib().wlsqm_hip_interp_plan_export_transposed(h, _stream_ptr(self._device, None), _ptr(toff), _ptr(tpt) if n else None))
         return toff, tpt
 
     def evaluate_adjoint(self, g, diff=0, grad_fi=None, ncols=None, stream=None):
@@ -986,10 +991,10 @@ class InterpolationPlan:
         base = 1 if single else 2
         if g.dim() not in (base, base + 1):
             raise ValueError("g must have the shape evaluate() returns for this diff: %s, or with a leading axis for a stack; got %s"
-                             % ((() if single else (ndiff,)) + (self.nx,), tuple(g.shape)))
+                             % (self._result(single, ndiff, False, 1)[0], tuple(g.shape)))
         stacked = g.dim() == base + 1
         R = int(g.shape[0]) if stacked else 1
-        shape = ((R,) if stacked else ()) + (() if single else (ndiff,)) + (self.nx,)
+        shape, sg_f, sg_d = self._result(single, ndiff, stacked, R, g)
         if tuple(g.shape) != shape or g.device != self._device or (self.nx > 1 and g.stride(-1) != 1):
             raise ValueError("g must be a float64 device tensor of shape %s with a contiguous last axis; got %s" % (shape, tuple(g.shape)))
         ncols = self._max_no if ncols is None else int(ncols)
@@ -1005,49 +1010,11 @@ class InterpolationPlan:
                                  % ("(%d, " % R if stacked else "", self.nmodels, ncols, tuple(grad_fi.shape)))
         if R == 0:
             return grad_fi
-        sg_f = int(g.stride(0)) if stacked else 0
-        sg_d = 0 if single else int(g.stride(1 if stacked else 0))
         arr = (C.c_int32 * max(ndiff, 1))(*diffs)
-        B.check(B.lib().wlsqm_hip_interp_plan_eval_adjoint_device(h, self._stream(stream), R, arr, ndiff, _ptr(g), sg_f, sg_d,
+        B.check(B.lib().wlsqm_hip_interp_plan_eval_adjoint_device(h, _stream_ptr(self._device, stream), R, arr, ndiff, _ptr(g), sg_f, sg_d,
                                                                   _ptr(grad_fi), int(grad_fi.stride(0)) if stacked else 0,
                                                                   int(grad_fi.stride(-2)), ncols))
         return grad_fi
-
-
-# ---- gradients through the evaluation of a plan (InterpolationPlan.evaluate_adjoint) ----
-
-_AUTOGRAD_EVALUATE = None
-
-
-def _autograd_evaluate():
-    """The torch.autograd.Function behind differentiable_evaluate (made at first use)."""
-    global _AUTOGRAD_EVALUATE
-    if _AUTOGRAD_EVALUATE is not None:
-        return _AUTOGRAD_EVALUATE
-    import torch
-    from torch.autograd.function import once_differentiable
-
-    class Evaluate(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, fi, plan, diff, stream):
-            ctx.call = (plan, diff, stream, tuple(fi.shape))
-            return plan.evaluate(diff, fi.detach(), stream=stream)
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, gout):
-            plan, diff, stream, fi_shape = ctx.call
-            if not ctx.needs_input_grad[0]:
-                return (None,) * 4
-            g = gout.contiguous()
-            # rows beyond nmodels and columns beyond the plan's DOFs are never read by the forward: zeros
-            exact = fi_shape[-2] == plan.nmodels and fi_shape[-1] == plan._max_no
-            gfi = (torch.empty if exact else torch.zeros)(fi_shape, dtype=torch.float64, device=g.device)
-            plan.evaluate_adjoint(g, diff, grad_fi=gfi, stream=stream)
-            return (gfi, None, None, None)
-
-    _AUTOGRAD_EVALUATE = Evaluate
-    return Evaluate
 
 
 def differentiable_evaluate(plan, fi, diff=0, stream=None):
@@ -1060,13 +1027,9 @@ def differentiable_evaluate(plan, fi, diff=0, stream=None):
     Once differentiable."""
     if fi is None:
         raise ValueError("differentiable_evaluate needs the coefficients fi explicitly")
-    if getattr(plan, "_geometry_requires_grad", False):
-        raise ValueError("the geometry is not differentiable")
-    if hasattr(diff, "__len__") or hasattr(diff, "__iter__"):
-        diff = [int(d) for d in diff]
-    else:
-        diff = int(diff)
-    return _autograd_evaluate().apply(fi, plan, diff, stream)
+    _no_geometry_grad(plan)
+    diffs, single = _diff_list(diff)
+    return _autograd().Evaluate.apply(fi, plan, diffs[0] if single else diffs, stream)
 
 
 # ---- batched dense solves (the kernels behind wlsqm.utils.lapackdrivers), device-resident ----

@@ -10,6 +10,7 @@ import pytest
 import _adjoint_ref as R
 import _cases as K
 import _parity as P
+from _device_helpers import OnDevice as _OnDevice
 
 ROOT = K.ROOT
 
@@ -73,17 +74,6 @@ def test_the_four_names_exist():
     for name in ("fit_many_adjoint_device", "fit_cloud_adjoint_device", "differentiable_fit_many", "differentiable_fit_cloud"):
         assert callable(getattr(h, name)) and name in h.__all__
         assert not hasattr(wlsqm, name)
-
-
-class _OnDevice:
-    """A host tensor that says it lives on the device: the argument checks run before anything touches the GPU."""
-    is_cuda = True
-
-    def __init__(self, t):
-        self._t = t
-
-    def __getattr__(self, name):
-        return getattr(self._t, name)
 
 
 def _args(n=4, K_=7, dim=2, no=6):

@@ -11,6 +11,7 @@ import pytest
 import _adjoint_ref as R
 import _cases as K
 import _parity as P
+from _device_helpers import bits as _bits, dev as _dev, nan as _nan
 
 pytestmark = pytest.mark.gpu
 
@@ -54,21 +55,6 @@ class _form:
         else:
             os.environ[SWITCH] = self.prev
         return False
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _nan(*shape):
-    import torch
-    return torch.full(shape, float("nan"), dtype=torch.float64, device="cuda")
-
-
-def _bits(t):
-    import torch
-    return t.contiguous().view(torch.int64)
 
 
 def _err(cand, ref, s):

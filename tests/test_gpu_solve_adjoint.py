@@ -11,6 +11,7 @@ import _adjoint_ref as R
 import _cases as K
 import _parity as P
 import _solve_adjoint_cases as SA
+from _device_helpers import bits as _bits, dev as _dev, nan as _nan
 
 pytestmark = pytest.mark.gpu
 
@@ -41,21 +42,6 @@ def floors():
 
 def _bar(floors, dim):
     return P.TOL + P.NOISE_MULT * floors[dim]
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _nan(*shape):
-    import torch
-    return torch.full(shape, float("nan"), dtype=torch.float64, device="cuda")
-
-
-def _bits(t):
-    import torch
-    return t.contiguous().view(torch.int64)
 
 
 def _solver(wlsqm, c, **kw):

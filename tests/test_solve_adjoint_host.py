@@ -14,6 +14,7 @@ import _adjoint_ref as R
 import _cases as K
 import _parity as P
 import _solve_adjoint_cases as SA
+from _device_helpers import OnDevice as _OnDevice
 
 ROOT = K.ROOT
 NAME = "wlsqm_hip_expert_solve_adjoint_device"
@@ -46,17 +47,6 @@ def test_the_four_python_names_exist():
         sig = inspect.signature(getattr(h, name))
         assert list(sig.parameters) == ["solver", "fk", "fi", "stream"] and sig.parameters["stream"].default is None
         assert name in h.__all__ and not hasattr(wlsqm, name)
-
-
-class _OnDevice:
-    """A host tensor that says it lives on the device: the argument checks run before anything touches the GPU."""
-    is_cuda = True
-
-    def __init__(self, t):
-        self._t = t
-
-    def __getattr__(self, name):
-        return getattr(self._t, name)
 
 
 def _solver(ready=True, n=4, max_nk=8, no=6):
