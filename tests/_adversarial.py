@@ -282,14 +282,71 @@ def truth_job(job):
     return P.truth_fit_mp(dim, b["xk"][s], b["fk"][s], b["nk"][s], b["xi"][s], b["fi0"][s], b["order_a"][s], kn[s], wm[s])
 
 
-def truths(jobs, workers=1):
-    """[truth_job(j) for j in jobs], over `workers` freshly started processes when workers > 1."""
+def _map(fn, jobs, workers):
     if workers <= 1:
-        return [truth_job(j) for j in jobs]
+        return [fn(j) for j in jobs]
     import multiprocessing as mp
     from concurrent.futures import ProcessPoolExecutor
     with ProcessPoolExecutor(max_workers=workers, mp_context=mp.get_context("spawn")) as ex:
-        return list(ex.map(truth_job, jobs))
+        return list(ex.map(fn, jobs))
+
+
+def truths(jobs, workers=1):
+    """[truth_job(j) for j in jobs], over `workers` freshly started processes when workers > 1."""
+    return _map(truth_job, jobs, workers)
+
+
+# ---- the fit's linear operator: sensitivities and adjoints -----------------------------------------------------------------------------
+
+# The families whose GEOMETRY differs (the operator does not see the data: fk* and exactpoly* share `plain`'s geometry), plus the real
+# lattice with self-including rows.  EDGE_EXP and COLLINEAR_EPS apply unchanged (tests/test_adversarial_cpu.py rehearses that the oracle's
+# sensitivities and the adjoint built from them stay finite and a reference on every one of them).
+OP_FAMILIES = ("plain", "grid", "grid_sorted", "sortedguess", "far", "aniso", "onesided", "self", "collinear", "tiny", "huge", "tiny_edge",
+               "huge_edge", "lattice")
+# One full wave and one half-filled one; combos(96) puts its four blocks of 24 across them, so that a wave holds several knowns /
+# weighting kinds (the fit suite's blocks are whole waves of one kind: this is the complementary arrangement).
+N_OP = 96
+OP_FIELDS = (0, 2)            # the seeds of g that have a truth; field 1 of a stack is field 0 times -1/2 (exact, truth included)
+
+
+def op_batch(family, dim, order, K, n=N_OP):
+    """The batch of `family` with its knowns / weighting (combos(n)) under the keys kn, wm."""
+    b = lattice_batch(dim, order, K, n) if family == "lattice" else make(family, dim, order, K, n)
+    b["kn"], b["wm"] = combos(n)
+    return b
+
+
+def op_g(family, dim, order, K, n=N_OP, field=0):
+    """g = dL/dfi_out of a family and shape: uniform in [-1, 1], seeded by family, shape and field."""
+    return _rng("g%d/%s" % (field, family), dim, order, K, n).uniform(-1.0, 1.0, (n, NDOF[dim][order]))
+
+
+def operator_job(job):
+    """(family, dim, order, K, n, lo, hi[, fields]) -> dict(S, J, kappa, live, kind, adjoint={field: (grad_fk, grad_fi, s)}) of cases
+    lo..hi by `_parity.truth_operator_mp` and, contracted in mpmath before anything is rounded, `_parity.truth_adjoint_mp` of
+    op_g(..., field) for `fields` (default OP_FIELDS; (): the operator alone).  A plain function of plain arguments, as truth_job is."""
+    import _parity as P
+    family, dim, order, K, n, lo, hi = job[:7]
+    fields = tuple(job[7]) if len(job) > 7 else OP_FIELDS
+    b = op_batch(family, dim, order, K, n)
+    s = slice(lo, hi)
+    op = P.truth_operator_mp(dim, b["xk"][s], b["nk"][s], b["xi"][s], b["order_a"][s], b["kn"][s], b["wm"][s], as_mp=True)
+    adj = {f: P.truth_adjoint_mp(op, op_g(family, dim, order, K, n, f)[s]) for f in fields}
+    return dict(S=op.S.astype(np.float64), J=op.J.astype(np.float64), kappa=op.kappa, live=op.live, kind=op.kind, adjoint=adj)
+
+
+def operators(jobs, workers=1):
+    """[operator_job(j) for j in jobs], over `workers` freshly started processes when workers > 1."""
+    return _map(operator_job, jobs, workers)
+
+
+def operator_truth(family, dim, order, K, n=N_OP, results=None):
+    """The pieces of operator_job over consecutive slices of one family joined into one dict (results: the jobs' outputs in order;
+    None: computed here in one piece)."""
+    results = [operator_job((family, dim, order, K, n, 0, n))] if results is None else results
+    out = {k: np.concatenate([r[k] for r in results]) for k in ("S", "J", "kappa", "live", "kind")}
+    out["adjoint"] = {f: tuple(np.concatenate([r["adjoint"][f][i] for r in results]) for i in range(3)) for f in results[0]["adjoint"]}
+    return out
 
 
 def lattice_batch(dim, order, K, n):

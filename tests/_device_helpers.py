@@ -1,6 +1,8 @@
 """What the tests of the device-resident API share: a host tensor that passes for a device tensor (the argument checks run before
-anything touches the GPU), and the three one-liners of the GPU tests that compare bits."""
+anything touches the GPU), the one-liners of the GPU tests that move arrays and compare bits, and the module-scoped fixtures of the
+adversarial GPU modules (imported by name into the module that uses them)."""
 import numpy as np
+import pytest
 
 
 class OnDevice:
@@ -27,3 +29,24 @@ def nan(*shape):
 def bits(t):
     import torch
     return t.contiguous().view(torch.int64)
+
+
+def same_bits(a, b):
+    """numpy arrays bit for bit, any NaN standing for any NaN."""
+    a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
+    na, nb = np.isnan(a), np.isnan(b)
+    return np.array_equal(na, nb) and np.array_equal(a.view(np.uint64)[~na], b.view(np.uint64)[~nb])
+
+
+@pytest.fixture(scope="module")
+def wlsqm():
+    import wlsqm as W
+    from wlsqm import _binding
+    assert _binding.lib().wlsqm_hip_device_count() >= 1, "no HIP device: the GPU tests need a real MI355X"
+    return W
+
+
+@pytest.fixture(scope="module")
+def oracle():
+    from oracle import oracle as O
+    return O

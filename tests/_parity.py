@@ -13,6 +13,8 @@ each other's roundoff, so the asserted bound is  E_m <= 1e-10 + NOISE_MULT * N_m
 additionally requires the candidate to be no further from the truth than the reference is (same
 multiplier).  Known DOFs must be bit-identical to the input.
 """
+from typing import NamedTuple
+
 import numpy as np
 
 TOL = 1e-10
@@ -90,6 +92,74 @@ def truth_fit(dim, xk, fk, nk, xi, fi_in, order, knowns, wm):
     return out
 
 
+def _unknown_set(dim, o, kn):
+    """(no, unknown, known, dropped) of one case: the DOFs the fit solves for, the true knowns and the unknowns that stray high mask bits
+    drop (infra.pyx:119-121)."""
+    no = len(exponents(dim, o))
+    unknown = [a for a in range(no) if not (kn >> a) & 1]
+    extra = bin(kn >> no).count("1")                          # infra.pyx:119-121 quirk: stray high bits drop unknowns
+    kept = unknown[:max(len(unknown) - extra, 0)] if extra else unknown
+    return no, kept, [a for a in range(no) if (kn >> a) & 1], unknown[len(kept):]
+
+
+def _system_mp(dim, xk, nk, xi, order, knowns, wm, j):
+    """Case j of a batch in mpmath (inside mp.workdps): None when it has nothing to solve, else a dict with
+      no, unknown, known, dropped   the DOF classes,
+      C[k][a]                       the design matrix (scaled monomials of the offsets), all `no` columns,
+      w[k]                          the weights,
+      s[i]                          the column equilibration of the unknowns (sqrt of sum_k w c^2; 1 for a zero column),
+      cols[i][k], wc[i][k]          the equilibrated columns of the unknowns and the same times w,
+      A                             the equilibrated normal matrix  cols^T W cols,
+      kappa                         the 2-norm condition number of sqrt(W) cols (fp64 numpy).
+    The one statement of the fit's matrix that truth_fit_mp and truth_operator_mp share."""
+    from mpmath import mp, mpf
+    one, w0 = mpf(1), mpf(1e-4)
+    fact = [mpf(v) for v in _FACT]
+    o, nkj, kn = int(order[j]), int(nk[j]), int(knowns[j])
+    ex = exponents(dim, o)
+    no, unknown, known, dropped = _unknown_set(dim, o, kn)
+    if not unknown:
+        return None
+    if dim == 1:
+        d = [[mpf(float(xk[j, k])) - mpf(float(xi[j]))] for k in range(nkj)]
+    else:
+        d = [[mpf(float(xk[j, k, m])) - mpf(float(xi[j, m])) for m in range(dim)] for k in range(nkj)]
+    C = []
+    for k in range(nkj):
+        pw = [[one, dk, dk * dk, dk ** 3, dk ** 4] for dk in d[k]]
+        row = []
+        for e in ex:
+            v = one
+            for m, p in enumerate(e):
+                if p:
+                    v = v * pw[m][p] / fact[p]
+            row.append(v)
+        C.append(row)
+    if int(wm[j]) == 1:
+        w = [one] * nkj
+    else:
+        d2 = [mp.fsum(x * x for x in dk) for dk in d]
+        dmax = max(d2)
+        w = []
+        for v in d2:
+            t = one - mp.sqrt(v / dmax)
+            w.append(w0 + (one - w0) * t * t)
+    nu = len(unknown)
+    cols = [[C[k][a] for k in range(nkj)] for a in unknown]
+    s = [mp.sqrt(mp.fsum(w[k] * c[k] * c[k] for k in range(nkj))) for c in cols]
+    s = [v if v != 0 else one for v in s]
+    cols = [[c[k] / s[i] for k in range(nkj)] for i, c in enumerate(cols)]
+    wc = [[w[k] * c[k] for k in range(nkj)] for c in cols]
+    A = [[None] * nu for _ in range(nu)]
+    for a in range(nu):
+        for b in range(a, nu):
+            A[a][b] = A[b][a] = mp.fdot(wc[a], cols[b])
+    B = np.array([[float(mp.sqrt(w[k]) * cols[i][k]) for i in range(nu)] for k in range(nkj)])
+    sv = np.linalg.svd(B, compute_uv=False)
+    kappa = sv[0] / sv[-1] if sv[-1] > 0 else np.inf
+    return dict(no=no, nk=nkj, unknown=unknown, known=known, dropped=dropped, C=C, w=w, s=s, cols=cols, wc=wc, A=A, kappa=kappa)
+
+
 def truth_fit_mp(dim, xk, fk, nk, xi, fi_in, order, knowns, wm, dps=60, as_mp=False):
     """The WLSQM fit of a batch in mpmath at `dps` (>= 60) digits: same arguments and meaning as `truth_fit` (knowns masks, the stray-bit
     quirk, both weightings, per-case orders, the 1D layout), without its limit (x87 long double on the normal equations stops being a
@@ -98,7 +168,6 @@ def truth_fit_mp(dim, xk, fk, nk, xi, fi_in, order, knowns, wm, dps=60, as_mp=Fa
     kappa_j, the 2-norm condition number of the column-equilibrated design matrix of the unknowns weighted by sqrt(w) (fp64 numpy; 1.0 for
     a case with nothing to solve).  The columns are equilibrated and the right-hand side scaled before the solve, so that the elimination
     sees entries of order one whatever the length scale and the magnitude of the data are."""
-    import mpmath
     from mpmath import mp, mpf
     assert dps >= 60
     n = len(nk)
@@ -106,96 +175,145 @@ def truth_fit_mp(dim, xk, fk, nk, xi, fi_in, order, knowns, wm, dps=60, as_mp=Fa
     full = np.array([[mpf(float(v)) for v in row] for row in np.asarray(fi_in, np.float64)], dtype=object).reshape(out.shape) if as_mp else None
     kappa = np.ones(n)
     with mp.workdps(dps):
-        one, w0 = mpf(1), mpf(1e-4)
-        fact = [mpf(v) for v in _FACT]
+        one = mpf(1)
         for j in range(n):
-            o, nkj, kn = int(order[j]), int(nk[j]), int(knowns[j])
-            ex = exponents(dim, o)
-            no = len(ex)
-            unknown = [a for a in range(no) if not (kn >> a) & 1]
-            extra = bin(kn >> no).count("1")                  # infra.pyx:119-121 quirk: stray high bits drop unknowns
-            if extra:
-                unknown = unknown[:max(len(unknown) - extra, 0)]
-            if not unknown:
+            m = _system_mp(dim, xk, nk, xi, order, knowns, wm, j)
+            if m is None:
                 continue
-            if dim == 1:
-                d = [[mpf(float(xk[j, k])) - mpf(float(xi[j]))] for k in range(nkj)]
-            else:
-                d = [[mpf(float(xk[j, k, m])) - mpf(float(xi[j, m])) for m in range(dim)] for k in range(nkj)]
-            C = []
-            for k in range(nkj):
-                pw = [[one, dk, dk * dk, dk ** 3, dk ** 4] for dk in d[k]]
-                row = []
-                for e in ex:
-                    v = one
-                    for m, p in enumerate(e):
-                        if p:
-                            v = v * pw[m][p] / fact[p]
-                    row.append(v)
-                C.append(row)
-            if int(wm[j]) == 1:
-                w = [one] * nkj
-            else:
-                d2 = [mp.fsum(x * x for x in dk) for dk in d]
-                dmax = max(d2)
-                w = []
-                for v in d2:
-                    t = one - mp.sqrt(v / dmax)
-                    w.append(w0 + (one - w0) * t * t)
+            nkj, C = m["nk"], m["C"]
             f = [mpf(float(fk[j, k])) for k in range(nkj)]
-            for a in range(no):
-                if (kn >> a) & 1:                             # known DOFs move to the right-hand side
-                    va = mpf(float(fi_in[j, a]))
-                    f = [f[k] - C[k][a] * va for k in range(nkj)]
-            nu = len(unknown)
-            cols = [[C[k][a] for k in range(nkj)] for a in unknown]
-            s = [mp.sqrt(mp.fsum(w[k] * c[k] * c[k] for k in range(nkj))) for c in cols]
-            s = [v if v != 0 else one for v in s]
+            for a in m["known"]:                              # known DOFs move to the right-hand side
+                va = mpf(float(fi_in[j, a]))
+                f = [f[k] - C[k][a] * va for k in range(nkj)]
             fs = max(abs(v) for v in f)
             fs = fs if fs != 0 else one
-            cols = [[c[k] / s[i] for k in range(nkj)] for i, c in enumerate(cols)]
-            wc = [[w[k] * c[k] for k in range(nkj)] for c in cols]
             fsc = [v / fs for v in f]
-            A = [[None] * nu for _ in range(nu)]
-            for a in range(nu):
-                for b in range(a, nu):
-                    A[a][b] = A[b][a] = mp.fdot(wc[a], cols[b])
-            rhs = [mp.fdot(wc[a], fsc) for a in range(nu)]
-            x = _solve_mp(A, rhs)
-            for i, a in enumerate(unknown):
-                v = x[i] * fs / s[i]
+            x = _solve_mp(m["A"], [[mp.fdot(wca, fsc)] for wca in m["wc"]])
+            for i, a in enumerate(m["unknown"]):
+                v = x[i][0] * fs / m["s"][i]
                 out[j, a] = float(v)
                 if as_mp:
                     full[j, a] = v
-            B = np.array([[float(mp.sqrt(w[k]) * cols[i][k]) for i in range(nu)] for k in range(nkj)])
-            sv = np.linalg.svd(B, compute_uv=False)
-            kappa[j] = sv[0] / sv[-1] if sv[-1] > 0 else np.inf
+            kappa[j] = m["kappa"]
     return (full if as_mp else out), kappa
 
 
-def _solve_mp(A, b):
-    """Gaussian elimination with partial pivoting on lists of mpf (in place)."""
-    n = len(b)
+# classes of a DOF of one case (Operator.kind)
+DOF_UNKNOWN, DOF_KNOWN, DOF_DROPPED, DOF_BEYOND = 0, 1, 2, 3
+
+
+class Operator(NamedTuple):
+    """What truth_operator_mp returns: (S, J, kappa) and, beside them, `live` (n, K, max_no) bool, the entries of S that the fit defines,
+    and `kind` (n, max_no) int8, the class of every DOF: DOF_UNKNOWN, DOF_KNOWN, DOF_DROPPED (by stray high mask bits), DOF_BEYOND (the
+    case's order).  `S, J, kappa = op[:3]` unpacks the operator alone."""
+    S: np.ndarray
+    J: np.ndarray
+    kappa: np.ndarray
+    live: np.ndarray
+    kind: np.ndarray
+
+
+def truth_operator_mp(dim, xk, nk, xi, order, knowns, wm, dps=60, as_mp=False):
+    """The fit's linear operator in mpmath, with the conventions of truth_fit_mp (same arguments but fk / fi, which the operator does not
+    see): fi_out[a] = sum_k S[k, a] fk[k] + sum_b J[a, b] fi_in[b] for every unknown a.  Returns an Operator (S, J, kappa, live, kind):
+      S (n, K, max_no)       S[j, k, a] = (A_UU^-1 C_U^T W)[a, k] = d fi_a / d fk_k for a in the unknown set U and k < nk[j], 0 elsewhere
+                             (`.live` marks the defined entries),
+      J (n, max_no, max_no)  J[j, a, b] = -(A_UU^-1 A_U,Kn)[a, b] = d fi_a / d fi_in_b for a in U and b a true known, 0 elsewhere,
+      kappa (n,)             truth_fit_mp's, from the same statement of the matrix (`_system_mp`).
+    float64 arrays, or object arrays of mpf with as_mp=True (what truth_adjoint_mp takes).  One elimination per case, with nk + |Kn|
+    right-hand sides: the columns of W C_U (unit data at neighbour k) and of -A_U,Kn (a unit known value moved to the right-hand side)."""
+    from mpmath import mp, mpf
+    assert dps >= 60
+    n = len(nk)
+    K = int(np.asarray(xk).shape[1])
+    no_max = max(len(exponents(dim, int(o))) for o in order)
+    S = np.zeros((n, K, no_max), object if as_mp else np.float64)
+    J = np.zeros((n, no_max, no_max), object if as_mp else np.float64)
+    live = np.zeros((n, K, no_max), bool)
+    kind = np.full((n, no_max), DOF_BEYOND, np.int8)
+    kappa = np.ones(n)
+    with mp.workdps(dps):
+        if as_mp:
+            S[...] = mpf(0); J[...] = mpf(0)
+        for j in range(n):
+            no, unknown, known, dropped = _unknown_set(dim, int(order[j]), int(knowns[j]))
+            kind[j, unknown], kind[j, known], kind[j, dropped] = DOF_UNKNOWN, DOF_KNOWN, DOF_DROPPED
+            m = _system_mp(dim, xk, nk, xi, order, knowns, wm, j)
+            if m is None:
+                continue
+            nkj, C, wc = m["nk"], m["C"], m["wc"]
+            rhs = [list(wca) + [-mp.fdot(wca, [C[k][b] for k in range(nkj)]) for b in known] for wca in wc]
+            x = _solve_mp(m["A"], rhs)
+            for i, a in enumerate(unknown):
+                xs = [v / m["s"][i] for v in x[i]]
+                for k in range(nkj):
+                    S[j, k, a] = xs[k] if as_mp else float(xs[k])
+                for t, b in enumerate(known):
+                    J[j, a, b] = xs[nkj + t] if as_mp else float(xs[nkj + t])
+                live[j, :nkj, a] = True
+            kappa[j] = m["kappa"]
+    return Operator(S, J, kappa, live, kind)
+
+
+def truth_adjoint_mp(op, g, dps=60):
+    """The transpose of the fit's operator applied to g (n, >= max_no) = dL/dfi_out, contracted in mpmath from `op` =
+    truth_operator_mp(..., as_mp=True) and rounded once: no fp64 cancellation in the truth.  Returns float64 (grad_fk, grad_fi, s):
+      grad_fk[j, k] = sum_{a in U} S[j, k, a] g[j, a]                        (0 for k >= nk[j]),
+      grad_fi[j, b] = g[j, b] + sum_{a in U} g[j, a] J[j, a, b]  for a known b,  g[j, b] for a dropped DOF,  0 for an unknown (and beyond
+                      the case's order),
+      s[j]          = max_k sum_{a in U} |S[j, k, a] g[j, a]|, the case's scale as tests/_adjoint_ref.contract defines it (1 where that is 0)."""
+    from mpmath import mp, mpf
+    S, J, kind = op.S, op.J, op.kind
+    assert S.dtype == object, "truth_adjoint_mp contracts before it rounds: it takes truth_operator_mp(..., as_mp=True)"
+    n, K, no_max = S.shape
+    gfk, gfi, s = np.zeros((n, K)), np.zeros((n, no_max)), np.ones(n)
+    with mp.workdps(dps):
+        for j in range(n):
+            gm = [mpf(float(g[j, a])) for a in range(no_max)]
+            U = [a for a in range(no_max) if kind[j, a] == DOF_UNKNOWN]
+            top = mpf(0)
+            for k in range(K):
+                terms = [S[j, k, a] * gm[a] for a in U]
+                gfk[j, k] = float(mp.fsum(terms))
+                top = max(top, mp.fsum(abs(t) for t in terms))
+            if top > 0:
+                s[j] = float(top)
+            for b in range(no_max):
+                if kind[j, b] == DOF_KNOWN:
+                    gfi[j, b] = float(gm[b] + mp.fsum(gm[a] * J[j, a, b] for a in U))
+                elif kind[j, b] == DOF_DROPPED:
+                    gfi[j, b] = float(gm[b])
+    return gfk, gfi, s
+
+
+def _solve_mp(A, B):
+    """Gaussian elimination with partial pivoting on lists of mpf: A (n x n; overwritten), B (n rows of m right-hand-side entries;
+    overwritten).  Returns X as n rows of m."""
+    n = len(B)
+    m = len(B[0]) if n else 0
     for c in range(n):
         p = max(range(c, n), key=lambda r: abs(A[r][c]))
         if p != c:
-            A[c], A[p] = A[p], A[c]; b[c], b[p] = b[p], b[c]
+            A[c], A[p] = A[p], A[c]; B[c], B[p] = B[p], B[c]
         piv = A[c][c]
-        rc = A[c]
+        rc, bc = A[c], B[c]
         for r in range(c + 1, n):
-            m = A[r][c] / piv
-            if m != 0:
-                rr = A[r]
+            f = A[r][c] / piv
+            if f != 0:
+                rr, br = A[r], B[r]
                 for t in range(c + 1, n):
-                    rr[t] -= m * rc[t]
-                b[r] -= m * b[c]
-    x = [None] * n
+                    rr[t] -= f * rc[t]
+                for t in range(m):
+                    br[t] -= f * bc[t]
+    X = [None] * n
     for r in range(n - 1, -1, -1):
-        acc = b[r]
+        acc = list(B[r])
         for t in range(r + 1, n):
-            acc -= A[r][t] * x[t]
-        x[r] = acc / A[r][r]
-    return x
+            art, xt = A[r][t], X[t]
+            for q in range(m):
+                acc[q] -= art * xt[q]
+        X[r] = [v / A[r][r] for v in acc]
+    return X
 
 
 def _solve_ld(A, b):
@@ -272,6 +390,51 @@ def assert_per_case(cand, ref, truth, kappa, what="", noise_mult=NOISE_MULT, flo
         "%s: per-case error q = %.3g at case %d (kappa %.3g) exceeds %g * %.3g + %g (the reference's worst case)"
         % (what, qc.max(), j, np.asarray(kappa)[j], noise_mult, qr.max(), floor))
     return float(qc.max()), float(qr.max())
+
+
+def sens_q(x, S, live, kappa):
+    """case_q for sensitivities (n, K, no) against truth_operator_mp's S: q_j = max over the case's live entries of |x - S| / (s_a eps
+    kappa_j^2), s_a the scale of DOF column a over the batch's live entries (1 for a column without any).  A live entry that is NaN / inf
+    gives q = inf; a case without live entries has q = 0."""
+    x = np.asarray(x, np.float64)[:, :, :S.shape[2]]
+    scale = np.where(live, np.abs(S), 0.0).max(axis=(0, 1))
+    scale = np.where(scale > 0, scale, 1.0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        e = np.abs(x - S) / scale
+    e = np.where(live, np.where(np.isfinite(e), e, np.inf), 0.0)
+    return e.max(axis=(1, 2)) / (np.finfo(np.float64).eps * np.asarray(kappa, np.float64) ** 2)
+
+
+def grad_err(x, truth, s):
+    """Per case ||x_j - truth_j||_inf / s_j (s: the case's scale, truth_adjoint_mp's); NaN / inf give inf."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        e = np.abs(np.asarray(x, np.float64) - truth).max(axis=1) / s
+    return np.where(np.isfinite(e), e, np.inf)
+
+
+def grad_q(x, truth, s, kappa):
+    """case_q for a gradient of the adjoint: q_j = ||x_j - truth_j||_inf / (s_j eps kappa_j^2)."""
+    return grad_err(x, truth, s) / (np.finfo(np.float64).eps * np.asarray(kappa, np.float64) ** 2)
+
+
+def assert_q(qc, qr, kappa, what="", noise_mult=NOISE_MULT, floor=None):
+    """Criterion (b) on per-case q already computed (sens_q, grad_q): max_j q_j(candidate) <= noise_mult * max_j q_j(reference) + floor."""
+    floor = Q_FLOOR if floor is None else floor
+    j = int(np.argmax(qc))
+    assert qc.max() <= noise_mult * qr.max() + floor, (
+        "%s: per-case error q = %.3g at case %d (kappa %.3g) exceeds %g * %.3g + %g (the reference's worst case)"
+        % (what, qc.max(), j, np.asarray(kappa)[j], noise_mult, qr.max(), floor))
+    return float(qc.max()), float(qr.max())
+
+
+def assert_scaled(e_cand_ref, e_cand_truth, e_ref_truth, what="", tol=TOL, noise_mult=NOISE_MULT):
+    """Criterion (a) for quantities with a per-case scale (the adjoint's gradients; grad_err): over the batch, the candidate's distance
+    to the reference and to the truth are both within tol + noise_mult * N, N = max_j e_j(reference against truth)."""
+    N = float(np.max(e_ref_truth))
+    assert np.max(e_cand_truth) <= tol + noise_mult * N, "%s: %.3g from the truth at case %d, reference %.3g" % (
+        what, np.max(e_cand_truth), int(np.argmax(e_cand_truth)), N)
+    assert np.max(e_cand_ref) <= tol + noise_mult * N, "%s: %.3g from the reference at case %d, bound %.3g" % (
+        what, np.max(e_cand_ref), int(np.argmax(e_cand_ref)), tol + noise_mult * N)
 
 
 COND_EDGES = (1.0, 1e1, 1e2, 1e3, 1e4, 1e5)     # six bins: [1, 10), [10, 1e2), ..., [1e5, inf)

@@ -15,6 +15,7 @@ import pytest
 
 import _adversarial as A
 import _parity as P
+from _device_helpers import oracle, wlsqm  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,20 +28,6 @@ DENSE_KERNEL = {(2, 2, 32): "stage", (2, 3, 30): "stage", (2, 4, 64): "stage", (
                 (1, 2, 8): "tile", (1, 4, 12): "tile"}
 GATHER_KERNEL = {(2, 2, 32): "stage-gather", (2, 4, 64): "stage-gather", (3, 2, 40): "stage-gather", (1, 2, 8): "tile-gather"}
 WORKERS = 12
-
-
-@pytest.fixture(scope="module")
-def wlsqm():
-    import wlsqm as W
-    from wlsqm import _binding
-    assert _binding.lib().wlsqm_hip_device_count() >= 1, "no HIP device: the GPU tests need a real MI355X"
-    return W
-
-
-@pytest.fixture(scope="module")
-def oracle():
-    from oracle import oracle as O
-    return O
 
 
 def _t(a, dev="cuda:0"):
@@ -80,6 +67,23 @@ def _shape_data(oracle, shape):
         out[f] = b
     _CACHE[shape] = out
     return out
+
+
+_OP_CACHE = {}
+
+
+def _operator_truths(shape):
+    """family -> truth of the fit's operator (A.operator_job, the operator alone: no adjoint is contracted) on the first A.N_OP cases of
+    the family's batch of N, for the families of A.OP_FAMILIES: the operator does not see the data, and the data families (fk*, exactpoly*)
+    are further draws of `plain`'s kind of geometry (every family seeds its own generator, so none of them IS plain's).  Once per module."""
+    if shape not in _OP_CACHE:
+        dim, order, K = shape
+        step = 32
+        per = A.N_OP // step
+        fams = [f for f in A.FAMILIES if f in A.OP_FAMILIES]
+        res = A.operators([(f, dim, order, K, N, lo, lo + step, ()) for f in fams for lo in range(0, A.N_OP, step)], WORKERS)
+        _OP_CACHE[shape] = {f: A.operator_truth(f, dim, order, K, N, res[i * per:(i + 1) * per]) for i, f in enumerate(fams)}
+    return _OP_CACHE[shape]
 
 
 def _dense(whip, b, mode=None):
@@ -169,10 +173,12 @@ def test_index_based_fit(wlsqm, oracle, shape):
 @pytest.mark.parametrize("shape", SIDE_SHAPES, ids=lambda s: "%dD-o%d-K%d" % s)
 def test_reference_signatures_with_sensitivities(wlsqm, oracle, shape, iterative):
     """`fit_*D_many_parallel(do_sens=1)` and `fit_*D_iterative_many_parallel` (numpy in / out): fi under (a) and (b) against the oracle's
-    run of the same algorithm, sens against the oracle's under the column criterion.  There is no mpmath truth of sens; its noise floor is
-    taken as the larger of the oracle's floor N_m of the fi column and eps kappa^2 of the batch's worst case — the forward error bound of a
-    solve through the normal equations, which the sensitivities (columns of the inverse applied to unit data) see in full whereas a smooth
-    field does not."""
+    run of the same algorithm, sens against the oracle's under the column criterion, with a noise floor taken as the larger of the
+    oracle's floor N_m of the fi column and eps kappa^2 of the batch's worst case — the forward error bound of a solve through the normal
+    equations, which the sensitivities (columns of the inverse applied to unit data) see in full whereas a smooth field does not.  That
+    bound is batch-wide: on the first A.N_OP cases of every family whose geometry differs (A.OP_FAMILIES) the basic fit's sens is also held to the per-case criterion (b)
+    against the mpmath truth of the operator (`_parity.truth_operator_mp`), so that one wrong lane cannot hide behind the
+    worst-conditioned case of its batch.  (The refinement's sensitivities are left at the column criterion.)"""
     import wlsqm.hip as whip
     dim, order, K = shape
     data = _shape_data(oracle, shape)
@@ -195,6 +201,13 @@ def test_reference_signatures_with_sensitivities(wlsqm, oracle, shape, iterative
         Nm = np.maximum(P.column_metric(ref, b["truth"]), np.finfo(np.float64).eps * b["kappa"].max() ** 2)
         E = P.column_metric(sens[live], sens_o[live])
         assert np.all(E <= P.TOL + P.NOISE_MULT * Nm), "%s %s: sens column metric %s, bound %s" % (name, f, E, P.TOL + P.NOISE_MULT * Nm)
+        if not iterative and f in A.OP_FAMILIES:
+            T = _operator_truths(shape)[f]
+            m = A.N_OP
+            assert np.array_equal(T["kappa"], b["kappa"][:m])
+            qc, qo = (P.sens_q(x[:m], T["S"], T["live"], T["kappa"]) for x in (sens, sens_o))
+            print("%-60s max q: gpu %.3g oracle %.3g" % ("%s sens [%s], %s" % (name, kern, f), qc.max(), qo.max()))
+            P.assert_q(qc, qo, T["kappa"], "%s sens, %s %s" % (name, f, shape))
 
 
 @pytest.mark.parametrize("shape", [(2, 2, 32), (3, 2, 40)], ids=lambda s: "%dD-o%d-K%d" % s)

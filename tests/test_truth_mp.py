@@ -57,3 +57,100 @@ def test_truth_fit_mp_recovers_a_dyadic_polynomial(dim, order, K, wm):
     with mpmath.mp.workdps(60):
         err = max(abs(got[j, a] - mpmath.mpf(float(b["coef"][j, a]))) for j in range(n) for a in range(b["no"]))
         assert err <= mpmath.mpf(10) ** -40, err
+
+
+# ---- the fit's linear operator: truth_operator_mp / truth_adjoint_mp ----
+
+def _operator_batch(dim):
+    """_benign plus one case that mixes a known derivative with a stray high bit (a known, a dropped DOF and unknowns in one case)."""
+    b = _benign(dim, n=14)
+    no = b["no"]
+    b["kn"][12] = 2 | (1 << (no + 1))
+    b["order_a"][12] = 2
+    op = P.truth_operator_mp(dim, b["xk"], b["nk"], b["xi"], b["order_a"], b["kn"], b["wm"], as_mp=True)
+    return b, op
+
+
+@pytest.mark.parametrize("dim", [1, 2, 3])
+def test_truth_operator_mp_is_the_fit(dim):
+    """(i) linearity: S fk + J fi_known is truth_fit_mp's solution to 1e-50; (iii) kappa is truth_fit_mp's; the masks say what the fit
+    defines; the float64 form is the rounded mpf form."""
+    import mpmath
+    b, op = _operator_batch(dim)
+    S, J, kappa = op[:3]
+    args = (dim, b["xk"], b["fk"], b["nk"], b["xi"], b["fi0"], b["order_a"], b["kn"], b["wm"])
+    fit, kappa_fit = P.truth_fit_mp(*args, as_mp=True)
+    assert np.array_equal(kappa, kappa_fit)
+    seen = set()
+    with mpmath.mp.workdps(60):
+        for j in range(b["n"]):
+            nkj = int(b["nk"][j])
+            kind = op.kind[j]
+            seen |= set(kind.tolist())
+            for a in range(b["no"]):
+                if kind[a] != P.DOF_UNKNOWN:
+                    assert not op.live[j, :, a].any() and all(S[j, k, a] == 0 for k in range(S.shape[1]))
+                    assert all(J[j, a, c] == 0 for c in range(b["no"]))
+                    continue
+                assert op.live[j, :nkj, a].all() and not op.live[j, nkj:, a].any()
+                assert all(J[j, a, c] == 0 for c in range(b["no"]) if kind[c] != P.DOF_KNOWN)
+                got = mpmath.fsum(S[j, k, a] * mpmath.mpf(float(b["fk"][j, k])) for k in range(nkj))
+                got += mpmath.fsum(J[j, a, c] * mpmath.mpf(float(b["fi0"][j, c])) for c in range(b["no"]))
+                assert abs(got - fit[j, a]) <= mpmath.mpf(10) ** -50 * abs(fit[j, a]), (j, a, got, fit[j, a])
+    assert seen == {P.DOF_UNKNOWN, P.DOF_KNOWN, P.DOF_DROPPED, P.DOF_BEYOND}
+    as64 = P.truth_operator_mp(dim, b["xk"][:3], b["nk"][:3], b["xi"][:3], b["order_a"][:3], b["kn"][:3], b["wm"][:3])
+    assert np.array_equal(as64.S, S[:3].astype(np.float64)) and np.array_equal(as64.J, J[:3].astype(np.float64))
+
+
+@pytest.mark.parametrize("dim", [1, 2, 3])
+def test_truth_operator_mp_reproduces_the_monomials(dim):
+    """(ii) sum_k S[k, a] c_k[b] = delta_ab over the unknowns, to 1e-50, with the monomials c_k built here from the coordinates: the one
+    identity that does not go through the elimination whose result it checks."""
+    import mpmath
+    from mpmath import mpf
+    b, op = _operator_batch(dim)
+    fact = [1, 1, 2, 6, 24]
+    checked = 0
+    with mpmath.mp.workdps(60):
+        for j in range(b["n"]):
+            ex = P.exponents(dim, int(b["order_a"][j]))
+            U = [a for a in range(len(ex)) if op.kind[j, a] == P.DOF_UNKNOWN]
+            nkj = int(b["nk"][j])
+            c = []
+            for k in range(nkj):
+                xkj = [b["xk"][j, k]] if dim == 1 else b["xk"][j, k]
+                xij = [b["xi"][j]] if dim == 1 else b["xi"][j]
+                d = [mpf(float(p)) - mpf(float(q)) for p, q in zip(xkj, xij)]
+                c.append([mpmath.fprod(d[m] ** p / fact[p] for m, p in enumerate(e)) for e in ex])
+            for a in U:
+                for bb in U:
+                    got = mpmath.fsum(op.S[j, k, a] * c[k][bb] for k in range(nkj))
+                    assert abs(got - (1 if a == bb else 0)) <= mpf(10) ** -50, (j, a, bb, got)
+                    checked += 1
+    assert checked >= 100 if dim > 1 else checked >= 30
+
+
+@pytest.mark.parametrize("dim", [1, 2, 3])
+def test_truth_adjoint_mp_is_the_transpose(dim):
+    """<g, fit(fk, fi)> over the unknowns plus the pass-through of every other DOF = <grad_fk, fk> + <grad_fi, fi>, to fp64 rounding of
+    the rounded gradients; padding, unknowns and columns beyond the order are exact zeros; dropped DOFs pass g through; s is the scale
+    of tests/_adjoint_ref.contract evaluated on the rounded sensitivities."""
+    b, op = _operator_batch(dim)
+    n, no = b["n"], b["no"]
+    g = np.random.default_rng(40 + dim).uniform(-1, 1, (n, no))
+    gfk, gfi, s = P.truth_adjoint_mp(op, g)
+    fit, _ = P.truth_fit_mp(dim, b["xk"], b["fk"], b["nk"], b["xi"], b["fi0"], b["order_a"], b["kn"], b["wm"])
+    S64 = op.S.astype(np.float64)
+    for j in range(n):
+        kind = op.kind[j]
+        nkj = int(b["nk"][j])
+        assert np.all(gfk[j, nkj:] == 0.0)
+        assert np.all(gfi[j, (kind == P.DOF_UNKNOWN) | (kind == P.DOF_BEYOND)] == 0.0)
+        assert np.array_equal(gfi[j, kind == P.DOF_DROPPED], g[j, kind == P.DOF_DROPPED])
+        defined = kind != P.DOF_BEYOND
+        lhs = float(np.dot(g[j, defined], fit[j, defined]))
+        terms = np.concatenate([gfk[j] * b["fk"][j], gfi[j] * b["fi0"][j]])
+        assert abs(lhs - terms.sum()) <= 64 * np.finfo(float).eps * np.abs(terms).sum(), (j, lhs, terms.sum())
+        U = kind == P.DOF_UNKNOWN
+        want_s = np.abs(S64[j][:, U] * g[j, U]).sum(axis=1).max() if U.any() else 0.0
+        assert abs(s[j] - (want_s if want_s > 0 else 1.0)) <= 1e-14 * s[j]
