@@ -70,35 +70,32 @@
 #include <atomic>
 #include <type_traits>
 
+#include "wlsqm_chunk.hpp"
 #include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_strict.hpp"
 
 #pragma clang fp contract(off)      // the reference is gcc -O2 on x86-64: no contraction; every fma() below is spelled out
 
+// ---- compile-time switches (tools/ab_unit.sh rebuilds this unit with -DNAME=value; the table of all of them: DESIGN section 8)
 #ifndef WLSQM_ACC_MINW6
 #define WLSQM_ACC_MINW6 2           // waves per SIMD the kernel of the systems up to 6 unknowns is compiled for
 #endif
 #ifndef WLSQM_ACC_MINW10
 #define WLSQM_ACC_MINW10 1          // ... of the 10-unknown systems
 #endif
+#ifndef WLSQM_ACC_W1
+#define WLSQM_ACC_W1 2              // chunks in flight in pass 1 of the two-pass form, 2D (a chunk's few instructions do not cover the next one's loads; 3D: always 2)
+#endif
+#ifndef WLSQM_ACC_GRP
+#define WLSQM_ACC_GRP 2             // neighbours per straight-line group of the accumulation, systems up to 6 unknowns (the size measured flat, profiles/r04b_ab_accurate.txt; the 10-unknown systems take the whole chunk)
+#endif
 
 namespace wlsqm {
 
 namespace acc {
 
-typedef double d2_ __attribute__((ext_vector_type(2)));
-
-#ifndef WLSQM_ACC_CH
-#define WLSQM_ACC_CH 8
-#endif
-constexpr int CH = WLSQM_ACC_CH;                                     // neighbours per staged chunk
-#ifndef WLSQM_ACC_W1
-#define WLSQM_ACC_W1 2
-#endif
-#ifndef WLSQM_ACC_GRP
-#define WLSQM_ACC_GRP 2
-#endif
+constexpr int CH = 8;                                                // neighbours per staged chunk
 constexpr int GRP = WLSQM_ACC_GRP < CH ? WLSQM_ACC_GRP : CH;                                   // neighbours per straight-line group of the accumulation
 
 template <int N> __host__ __device__ constexpr int utri(int i, int m) { return i * N - i * (i - 1) / 2 + (m - i); }   // i <= m < N
@@ -147,9 +144,6 @@ __device__ __forceinline__ bool entries_in_range(const double (&U)[N * (N + 1) /
 // the other N (N - 1) / 2 quotients of the sweep need not be computed — the same doubles come out, not an approximation.  c_max^2 is
 // computed once per case (raw v_rcp_f64: 2^-23, covered by the 2^-16 margin below); the test is wave-uniform (every lane of the
 // wave must pass: otherwise the full sweep runs, which is always right).  On BASELINE configs[1] the sweeps from the third on pass.
-#ifndef WLSQM_ACC_RUIZ_DIAG
-#define WLSQM_ACC_RUIZ_DIAG 1
-#endif
 template <int N, class OPS, bool DIAG = false>
 __device__ __forceinline__ bool ruiz_sym(const double (&U)[N * (N + 1) / 2], double (&rs)[N]) {
     using strict::ruiz_epsilon;
@@ -313,7 +307,8 @@ __device__ __forceinline__ bool accurate_group(const KParams& p, const long long
     static_assert(!SPEC || DENSE, "the speculative single pass stages dense rows");
     constexpr int N = ndofs(DIM, ORDER), NE = N * (N + 1) / 2;
     constexpr unsigned FULL = (N >= 32) ? ~0u : ((1u << N) - 1u);
-    constexpr int XPC = CH * DIM * 8 / 16, FPC = CH * 8 / 16;        // 16-byte pieces of one case's chunk: coordinates, values
+    using Pieces = ChunkPieces<DIM, CH>;                             // (wlsqm_chunk.hpp: which lane moves which 16-byte piece)
+    constexpr int XPC = Pieces::XPC, FPC = Pieces::FPC, XCPI = Pieces::XCPI, XNI = Pieces::XNI, FCPI = Pieces::FCPI, FNI = Pieces::FNI;
     constexpr int XPITCH = CH * DIM + 2, FPITCH = CH + 2;            // doubles per staged row (+ 16 bytes: conflict-free b128 reads)
     double* const xs = lds;
     double* const fs = lds + 64 * XPITCH;
@@ -334,9 +329,6 @@ __device__ __forceinline__ bool accurate_group(const KParams& p, const long long
     const int K = (int)p.max_nk;
     const int Q = (K + CH - 1) / CH;
     const int nvalid = (ncases - t0 < 64) ? (int)(ncases - t0) : 64;
-    constexpr int XCPI = 64 / XPC, XNI = (64 + XCPI - 1) / XCPI;      // 2D: 8 cases x 8 instructions; 3D: 5 x 13 (lanes 60..63 idle)
-    constexpr int FCPI = 64 / FPC, FNI = 64 / FCPI;                   // 16 cases x 4 instructions
-    static_assert(64 % FCPI == 0, "value rows: whole instructions");
     const int xsub = lane % XPC, xc0 = lane / XPC, fsub = lane % FPC, fc0 = lane / FPC;
     const unsigned xrowb = (unsigned)K * DIM * 8, frowb = (unsigned)K * 8;
     const unsigned xg0 = (unsigned)xc0 * xrowb + (unsigned)xsub * 16u, fg0 = (unsigned)fc0 * frowb + (unsigned)fsub * 16u;
@@ -695,7 +687,7 @@ __device__ __forceinline__ bool accurate_group(const KParams& p, const long long
         double rs[N];
 #pragma unroll
         for (int i = 0; i < N; ++i) rs[i] = 1.;
-        if (__all(sure)) sure = !active || ruiz_sym<N, FastOps, WLSQM_ACC_RUIZ_DIAG != 0>(U, rs);
+        if (__all(sure)) sure = !active || ruiz_sym<N, FastOps, true>(U, rs);
         if (!__all(sure)) return true;                                // wave-uniform: the whole group again, with the IEEE sequences
         eliminate(rs, weight_of);
         solve_store(rs);
@@ -825,12 +817,8 @@ int launch_fit_accurate(int dimension, int order, const KParams& p, hipStream_t 
     *handled = false;
     if (p.do_sens || p.iterative) return WLSQM_OK;
 #define CASE(D, O) if (dimension == D && order == O) { *handled = true; return launch_accurate<D, O, FMA>(p, stream); }
-#ifdef WLSQM_ACC_DEV_ONLY22      // (development: one shape, for quick looks at the ISA)
-    CASE(2, 2)
-#else
     CASE(2, 0) CASE(2, 1) CASE(2, 2) CASE(2, 3)
     CASE(3, 0) CASE(3, 1) CASE(3, 2)
-#endif
 #undef CASE
     return WLSQM_OK;
 }

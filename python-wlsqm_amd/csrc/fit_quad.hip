@@ -24,6 +24,14 @@
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_moments.hpp"
 
+// ---- compile-time switches (tools/ab_unit.sh rebuilds this unit with -DNAME=value; the table of all of them: DESIGN section 8)
+#ifndef WLSQM_QUAD_LROWS
+#define WLSQM_QUAD_LROWS 2              // slots of every lane's rows kept in LDS during the solve (68 of the 180 doubles; 0, all in registers: 120 doubles in scratch, 0.83 ms per 200k cases)
+#endif
+#ifndef WLSQM_QUAD_LOAD_UNROLL
+#define WLSQM_QUAD_LOAD_UNROLL 50       // moments of a lane requested at once: all 50 (10 at a time: 3Do4@400k 1.14 against 1.09 ms)
+#endif
+
 namespace wlsqm {
 
 namespace quad {
@@ -77,9 +85,6 @@ __global__ __launch_bounds__(64, 1) void quad_solve_kernel(const KParams p) {
     // lane's rows (68 of the 180 doubles: entry e of lane t at lds[64 e + t]) — the rows that are finished first and then only read
     // again by the back substitution.  All 180 in registers were 360 of the lane's 512 and the compiler put 120 doubles of them in
     // scratch (0.83 ms per 200k cases: a lone wave waits out every scratch access).
-#ifndef WLSQM_QUAD_LROWS
-#define WLSQM_QUAD_LROWS 2
-#endif
     constexpr int LROWS = WLSQM_QUAD_LROWS, NL = off(LROWS);
     __shared__ __attribute__((aligned(16))) double mom[(16 * PITCH > 64 * NL) ? 16 * PITCH : 64 * NL];
     __shared__ unsigned int s_idx32[NP * NP / 4];
@@ -91,9 +96,6 @@ __global__ __launch_bounds__(64, 1) void quad_solve_kernel(const KParams p) {
         // the 16 cases of this wave are 16 consecutive lanes of one 64-case group of the moment kernels: 128 contiguous bytes per entry
         const double* src = p.ws + (case0 >> 6) * (long long)(NW * 64) + (case0 & 63);
         const int cc = lane & 15, e0 = lane >> 4;
-#ifndef WLSQM_QUAD_LOAD_UNROLL
-#define WLSQM_QUAD_LOAD_UNROLL 50       // all of a lane's 50 moments requested at once (10 at a time: 3Do4@400k 1.14 against 1.09 ms)
-#endif
 #pragma unroll WLSQM_QUAD_LOAD_UNROLL
         for (int it = 0; it < NW / 4; ++it) mom[cc * PITCH + it * 4 + e0] = src[(it * 4 + e0) * 64 + cc];
         if (lane < 16) mom[lane * PITCH + NW] = 0.0;

@@ -38,57 +38,57 @@
 #include <atomic>
 #include <type_traits>
 
+#include "wlsqm_chunk.hpp"
 #include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_moments.hpp"
 
-#ifndef WLSQM_STAGE_NT_LOADS
-#define WLSQM_STAGE_NT_LOADS 0      // 1: the once-read rows by non-temporal loads — slower: configs[1] 0.175 against 0.152 ms, configs[2] 0.407 against 0.398, configs[4] 0.317 against 0.286 (profiles/r04zb_ab_stage_nt_loads.txt)
+// ---- compile-time switches (tools/ab_unit.sh rebuilds this unit with -DNAME=value; the table of all of them: DESIGN section 8)
+#ifndef WLSQM_STAGE_MINW6
+#define WLSQM_STAGE_MINW6 2         // waves per SIMD the dense systems up to 6 unknowns are compiled for (the LDS-DMA form compiled for 2 / 3 / 4: configs[1] 0.132-0.134 ms all three, profiles/stage_c2_dma_occupancy.txt)
 #endif
-#ifndef WLSQM_STAGE_GRP
-#define WLSQM_STAGE_GRP 4           // neighbours the scheduler may interleave in the moment pass (with WLSQM_STAGE_SCHED_BARRIER)
+#ifndef WLSQM_STAGE_MINW10
+#define WLSQM_STAGE_MINW10 2        // ... the dense systems with 7..10 unknowns (one wave: configs[4] 0.290 against 0.275 ms, profiles/r05g_ab_stage_dma.txt; the gathering form keeps its SIMD)
 #endif
-#ifndef WLSQM_STAGE_SCHED_BARRIER
-#define WLSQM_STAGE_SCHED_BARRIER 0
+#ifndef WLSQM_STAGE_CH10
+#define WLSQM_STAGE_CH10 8          // neighbours per staged chunk of the systems with 7..10 unknowns (4: 96-byte pieces straddle 64-byte sectors — by LDS-DMA at two waves per SIMD 0.30 against 0.275 ms and 1.83 GB fetched per 1M configs[4] cases, profiles/r05g_ab_stage_dma.txt; register-staged the loops spilled, r04z_ab_c5_two_waves.txt)
+#endif
+#ifndef WLSQM_STAGE_GRP15
+#define WLSQM_STAGE_GRP15 8         // neighbours the scheduler may interleave in the moment pass of the 15-unknown systems (below the chunk size: a scheduling barrier per group)
+#endif
+#ifndef WLSQM_STAGE_GRP20
+#define WLSQM_STAGE_GRP20 8         // ... of the 20-unknown systems (1 / 2 / 4 / 8: 0.608 / 0.594 / 0.594 / 0.569 ms per 1M cases of 32 neighbours, profiles/r04t_ab_stage33.txt)
+#endif
+#ifndef WLSQM_STAGE_DMA
+#define WLSQM_STAGE_DMA 18          // which systems take their chunks by LDS-DMA — bit 0: up to 6 unknowns, 1: 7..10, 2: 11..15, 3: 20, 4: 35 (bit 0 stays off, see DMA in the kernel; profiles/r05g_ab_stage_dma.txt)
+#endif
+#ifndef WLSQM_STAGE_DMA_SLOTS
+#define WLSQM_STAGE_DMA_SLOTS 2     // slots of the LDS-DMA ring (1: no chunk in flight while one is consumed — the second wave of the SIMD covers the wait)
+#endif
+#ifndef WLSQM_STAGE_DMA_SLOTS10
+#define WLSQM_STAGE_DMA_SLOTS10 1   // ... of the systems with 7..10 unknowns (two waves per SIMD: 17 KB each)
+#endif
+#ifndef WLSQM_STAGE_DMA_SLOTS35
+#define WLSQM_STAGE_DMA_SLOTS35 2   // ... of the 35-unknown systems' two moment passes
+#endif
+#ifndef WLSQM_STAGE_DMA_SKEW
+#define WLSQM_STAGE_DMA_SKEW 16     // bytes by which a load instruction's KiB of the LDS-DMA image is shifted (0: 6- to 8-way bank conflicts of the b128 reads, see SKEW in the kernel)
 #endif
 
 namespace wlsqm {
 
 namespace stage {
-typedef double d2_ __attribute__((ext_vector_type(2)));
 constexpr int CH = 8;               // neighbours per staged chunk
+// Settled (switches until the compile-time clean-up; the arms are out of the source, the measurements stay):
+//   the once-read rows by non-temporal loads — measured slower, removed: configs[1] 0.175 against 0.152 ms, configs[2] 0.407 against 0.398,
+//   configs[4] 0.317 against 0.286 (profiles/r04zb_ab_stage_nt_loads.txt);
+//   every LDS-DMA transfer non-temporal — measured slower, removed: configs[1] 0.182-0.184 / 0.157-0.159 against 0.132-0.134 ms
+//   (profiles/stage_c2_dma_occupancy.txt);
+//   one group size of the moment pass for every system (a scheduling barrier every 4 neighbours) — removed: the sizes are per system (GRP
+//   in the kernel).
+constexpr int LDS_ROWS20 = 4;       // rows of a 20 x 20 normal matrix kept in LDS during the solve (74 of its 210 entries: 37 KB per wave)
 }
 
-#ifndef WLSQM_STAGE_GRP20
-#define WLSQM_STAGE_GRP20 8         // ... of the 20-unknown systems (1 / 2 / 4 / 8: 0.608 / 0.594 / 0.594 / 0.569 ms per 1M cases of 32 neighbours, profiles/r04t_ab_stage33.txt)
-#endif
-#ifndef WLSQM_STAGE_SOLVE_BARRIERS
-#define WLSQM_STAGE_SOLVE_BARRIERS 1
-#endif
-#ifndef WLSQM_STAGE_LDS_ROWS
-#define WLSQM_STAGE_LDS_ROWS 4      // rows of a 20 x 20 normal matrix kept in LDS during the solve (74 of its 210 entries: 37 KB per wave)
-#endif
-#ifndef WLSQM_STAGE_MINW6
-#define WLSQM_STAGE_MINW6 2         // waves per SIMD the systems up to 6 unknowns are compiled for
-#endif
-#ifndef WLSQM_STAGE_MINW6G
-#define WLSQM_STAGE_MINW6G 2        // ... their gathering form
-#endif
-#ifndef WLSQM_STAGE_MINW35
-#define WLSQM_STAGE_MINW35 1        // ... the two moment passes of the 35-unknown systems (dense input; two: ~100 sums per lane leave no room, 1 898 / 49 spilled registers)
-#endif
-#ifndef WLSQM_STAGE_MINW10
-#define WLSQM_STAGE_MINW10 2        // waves per SIMD the systems with 7..10 unknowns are compiled for (dense input; the gathering form keeps its SIMD)
-#endif
-#ifndef WLSQM_STAGE_MINW10G
-#define WLSQM_STAGE_MINW10G 1       // ... their gathering form (two: 3D order 2 spills)
-#endif
-#ifndef WLSQM_STAGE_MINW15
-#define WLSQM_STAGE_MINW15 1        // ... the 15-unknown systems
-#endif
-#ifndef WLSQM_STAGE_GRP15
-#define WLSQM_STAGE_GRP15 8         // neighbours the scheduler may interleave in their moment pass
-#endif
 // PART = 4 (round 5, 2D order 4): the whole fit, and the INVERSE of every case's knowns-eliminated normal matrix at p.ws for the
 // sensitivities (fit_sens.hip) — layout and meaning of moment_solve_kernel<.., INV> (fit_moment.hip): inv[group of 64][column][case][row].
 // PART = 0: the whole fit.  PART = 1 / 2 (3D order 4, 35 unknowns): the kernel stops after the moment pass and leaves HALF of the case's
@@ -110,56 +110,33 @@ __device__ __forceinline__ void stage_group(const KParams& p, const unsigned grp
     constexpr bool RAGGED = RAG == 2;
     using namespace stage;
     constexpr int NO = ndofs(DIM, ORDER), NE = NO * (NO + 1) / 2, NM = mom_count<DIM>(2 * ORDER);
-#ifndef WLSQM_STAGE_CH10
-#define WLSQM_STAGE_CH10 8          // neighbours per staged chunk of the systems with 7 .. 10 unknowns (4: 96-byte pieces straddle 64-byte sectors — by LDS-DMA at two waves per SIMD 0.30 against 0.275 ms and 1.83 GB fetched per 1M configs[4] cases, profiles/r05g_ab_stage_dma.txt; register-staged the loops spilled, r04z_ab_c5_two_waves.txt)
-#endif
     constexpr int CH = (NO > 6 && NO <= 10) ? WLSQM_STAGE_CH10 : stage::CH;
     static_assert(mom_count<DIM>(ORDER) == NO, "one right-hand-side moment per DOF");
-    constexpr int XPC = CH * DIM * 8 / 16, FPC = CH * 8 / 16;        // 16-byte pieces of one case's chunk: coordinates, values
+    using Pieces = ChunkPieces<DIM, CH>;                             // (wlsqm_chunk.hpp: which lane moves which 16-byte piece)
+    constexpr int XPC = Pieces::XPC, FPC = Pieces::FPC, XCPI = Pieces::XCPI, XNI = Pieces::XNI, FCPI = Pieces::FCPI, FNI = Pieces::FNI;
     constexpr int XPITCH = CH * DIM + 2, FPITCH = CH + 2;            // doubles per staged row (+ 16 bytes: conflict-free b128 reads)
-    constexpr int XCPI = 64 / XPC, XNI = (64 + XCPI - 1) / XCPI;      // whole cases per load instruction; instructions per chunk
-    constexpr int FCPI = 64 / FPC, FNI = 64 / FCPI;
     // neighbours the scheduler may interleave: the 6-unknown systems run two waves per SIMD and fit their 256 registers only with
     // two at a time (no scratch; four: 44 B, eight: 76 B); the larger systems own their SIMD and take the whole chunk
-    constexpr bool SCHED_BARRIER = WLSQM_STAGE_SCHED_BARRIER || NO <= 6 || NO >= 20 || (NO > 10 && WLSQM_STAGE_GRP15 < CH);
-    constexpr int GRP = WLSQM_STAGE_SCHED_BARRIER ? (WLSQM_STAGE_GRP < CH ? WLSQM_STAGE_GRP : CH) : (NO <= 6 ? 2 : NO >= 20 ? WLSQM_STAGE_GRP20 : NO > 10 ? (WLSQM_STAGE_GRP15 < CH ? WLSQM_STAGE_GRP15 : CH) : CH);
+    constexpr bool SCHED_BARRIER = NO <= 6 || NO >= 20 || (NO > 10 && WLSQM_STAGE_GRP15 < CH);
+    constexpr int GRP = NO <= 6 ? 2 : NO >= 20 ? WLSQM_STAGE_GRP20 : NO > 10 ? (WLSQM_STAGE_GRP15 < CH ? WLSQM_STAGE_GRP15 : CH) : CH;
     // the staging rows; behind them (reusing the same bytes after the last chunk) the 64 result rows of the wave
     // (and, for the 20-unknown systems, the top R0 rows of every lane's normal matrix during the solve: see below)
-    constexpr int R0 = NO == 20 ? WLSQM_STAGE_LDS_ROWS : 0, TOP_D = 64 * tri<NO>(R0, R0);
+    constexpr int R0 = NO == 20 ? LDS_ROWS20 : 0, TOP_D = 64 * tri<NO>(R0, R0);
     // DMA (round 5): the chunks go from memory STRAIGHT into LDS (global_load_lds_dwordx4: no vector register holds a chunk in flight), into
     // a ring of NSLOT slots with NSLOT - 1 chunks in flight while one is consumed.  A wave instruction's 64 pieces land lane-linear —
     // piece of lane l at 16 l of the instruction's KiB — so the image of a slot is [instruction][case in instruction][piece] and case c reads
     // its CH neighbours at KiB c / XCPI, offset (c % XCPI) XPC 16 (contiguous, as in the padded rows of the register-staged form; the idle
     // lanes of an instruction land in the tail of its KiB, which nobody reads).  The wave waits for its OWN transfers with a counted
     // s_waitcnt vmcnt — all that orders a ds_read behind an LDS-DMA of the same wave (MI355X_MICROARCH.md, co-residence item 7).
-#ifndef WLSQM_STAGE_DMA
-#define WLSQM_STAGE_DMA 18           // bit 0: the systems up to 6 unknowns, 1: 7..10, 2: 11..15, 3: 20, 4: 35
-// (bit 0 stays off: the dense 2D systems up to 6 unknowns get the DMA form as a kernel of its own, PART 6, for the launches it was measured
-// on — rows of whole lines on line-aligned bases, see launch_stage.  With the skewed image one slot is enough there: BASELINE configs[1]
-// 0.1524 ms register-staged, 0.132-0.134 with one slot at 2 / 3 / 4 waves per SIMD compiled for, 0.149-0.151 with two slots (25 KB per wave:
-// six waves per CU); every transfer non-temporal 0.182-0.184 / 0.157-0.159: profiles/stage_c2_dma_occupancy.txt.)
-#endif
-#ifndef WLSQM_STAGE_DMA_NT
-#define WLSQM_STAGE_DMA_NT 0        // the transfers with the non-temporal policy
-#endif
-#if WLSQM_STAGE_DMA_NT
-#define WLSQM_STAGE_DMA_POLICY " nt"
-#else
-#define WLSQM_STAGE_DMA_POLICY ""
-#endif
-#ifndef WLSQM_STAGE_DMA_SLOTS
-#define WLSQM_STAGE_DMA_SLOTS 2      // slots of the ring (1: no chunk in flight while one is consumed — the second wave of the SIMD covers the wait)
-#endif
-#ifndef WLSQM_STAGE_DMA_SLOTS10
-#define WLSQM_STAGE_DMA_SLOTS10 1    // ... of the systems with 7..10 unknowns (two waves per SIMD: 17 KB each)
-#endif
+    // Which systems: the bits of WLSQM_STAGE_DMA.  Bit 0 stays off: the dense 2D systems up to 6 unknowns get the DMA form as a kernel of its
+    // own, PART 6, for the launches it was measured on — rows of whole lines on line-aligned bases, see launch_stage.  With the skewed image one
+    // slot is enough there: BASELINE configs[1] 0.1524 ms register-staged, 0.132-0.134 with one slot at 2 / 3 / 4 waves per SIMD compiled for,
+    // 0.149-0.151 with two slots (25 KB per wave: six waves per CU); every transfer non-temporal measured slower, removed: 0.182-0.184 /
+    // 0.157-0.159 (profiles/stage_c2_dma_occupancy.txt).
     // PART = 6 (2D systems up to 6 unknowns; launch_stage): PART 0 with its chunks by LDS-DMA into ONE slot, whatever the mask says
     constexpr bool DMA6 = PART == 6;
     static_assert(!DMA6 || (DIM == 2 && NO <= 6 && !GATHER && RAG != 2), "PART 6: the dense 2D systems up to 6 unknowns");
     constexpr bool DMA = DMA6 || (!GATHER && PART != 5 && (((WLSQM_STAGE_DMA) >> (NO <= 6 ? 0 : NO <= 10 ? 1 : NO <= 15 ? 2 : NO <= 20 ? 3 : 4)) & 1));
-#ifndef WLSQM_STAGE_DMA_SLOTS35
-#define WLSQM_STAGE_DMA_SLOTS35 2
-#endif
     constexpr int NSLOT = DMA6 ? 1 : DMA ? ((NO > 6 && NO <= 10) ? WLSQM_STAGE_DMA_SLOTS10 : NO == 35 ? WLSQM_STAGE_DMA_SLOTS35 : WLSQM_STAGE_DMA_SLOTS) : 1, PF = NSLOT - 1;
     // SKEW (round 6): instruction i lands at i (1 KiB + 16 B), not at i KiB.  A lane reads ITS case's neighbours with
     // ds_read_b128, and the 16 lanes of a read group (MI355X_MICROARCH.md: {0-3, 12-15, 20-27}, ...) must hit 16 different 16-byte slots of the
@@ -167,9 +144,6 @@ __device__ __forceinline__ void stage_group(const KParams& p, const unsigned grp
     // slots for sixteen lanes, 6-way conflicts (`SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE` 0.80 on configs[4], profiles/r05_C5_pmc_summary.json)
     // — or (8 (c mod 8)) mod 16 (2D order 3: 8-way).  With the instruction's KiB shifted by one slot the worst group is 2-3-way (brute force
     // over the four lane groups: 25 -> 9 of an ideal 4 cycles per read in 3D, 32 -> 8 in 2D, 16 -> 8 for the values).
-#ifndef WLSQM_STAGE_DMA_SKEW
-#define WLSQM_STAGE_DMA_SKEW 16
-#endif
     constexpr int KIB_B = 1024 + WLSQM_STAGE_DMA_SKEW, KIB_D = KIB_B / 8;      // bytes / doubles from one instruction's image to the next
     constexpr int SLOT_D = (XNI + FNI) * KIB_D;                        // doubles of one slot
     static_assert(!DMA || (NSLOT >= 1 && PF * (XNI + FNI) <= 63), "the chunks in flight must fit the vmcnt counter");
@@ -206,22 +180,14 @@ __device__ __forceinline__ void stage_group(const KParams& p, const unsigned grp
         for (int i = 0; i < XNI; ++i) {
             int cc = xc0 + i * XCPI;
             cc = cc < nvalid ? cc : nvalid - 1;                       // tail group / idle lanes of the last instruction: replay a valid row
-#if WLSQM_STAGE_NT_LOADS
-            if (xlane) xr[i] = __builtin_nontemporal_load(reinterpret_cast<const d2_*>(xb + (size_t)(unsigned)cc * xrowb));
-#else
             if (xlane) xr[i] = *reinterpret_cast<const d2_*>(xb + (size_t)(unsigned)cc * xrowb);
-#endif
         }
         if (want_f) {
 #pragma unroll
             for (int i = 0; i < FNI; ++i) {
                 int cc = fc0 + i * FCPI;
                 cc = cc < nvalid ? cc : nvalid - 1;
-#if WLSQM_STAGE_NT_LOADS
-                fr[i] = __builtin_nontemporal_load(reinterpret_cast<const d2_*>(fb + (size_t)(unsigned)cc * frowb));
-#else
                 fr[i] = *reinterpret_cast<const d2_*>(fb + (size_t)(unsigned)cc * frowb);
-#endif
             }
         }
     };
@@ -233,17 +199,16 @@ __device__ __forceinline__ void stage_group(const KParams& p, const unsigned grp
             unsigned xo = (unsigned)q * (CH * DIM * 8) + (unsigned)xsub * 16u, fo = (unsigned)q * (CH * 8) + (unsigned)fsub * 16u;
             xo = xo < xrowb ? xo : xrowb - 16u; fo = fo < frowb ? fo : frowb - 16u;
             const unsigned slot = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(uintptr_t)lds + (unsigned)(q % NSLOT) * (unsigned)(SLOT_D * 8)));
-#ifndef WLSQM_STAGE_DMA_SPLIT
-#define WLSQM_STAGE_DMA_SPLIT 1      // (configs[4]: same 0.275 ms, FETCH_SIZE 1.80 -> 1.64 GB per launch; its shuffled form 0.427 -> 0.406 ms: profiles/r05g_ab_stage_dma.txt)
-#endif
-            constexpr bool SPLIT = WLSQM_STAGE_DMA_SPLIT && PF == 0;      // (two masked instructions per transfer: only where every wait is vmcnt(0))
+            // SPLIT cache policy of the coordinates' transfers (two masked instructions per transfer: only where every wait is vmcnt(0)).  Against one
+            // policy for all pieces, configs[4]: same 0.275 ms, FETCH_SIZE 1.80 -> 1.64 GB per launch; its shuffled form 0.427 -> 0.406 ms
+            // (profiles/r05g_ab_stage_dma.txt; the unsplit form of these kernels is removed)
+            constexpr bool SPLIT = PF == 0;      // (two masked instructions per transfer: only where every wait is vmcnt(0))
             const unsigned xt_lo = (unsigned)(uintptr_t)xt & 127u;
             (void)xt_lo;
 #pragma unroll
             for (int i = 0; i < XNI; ++i) {
                 int cc = xc0 + i * XCPI;
                 cc = cc < nvalid ? cc : nvalid - 1;                   // (idle lanes and tail groups replay a valid row)
-                unsigned keep;
                 if constexpr (SPLIT) {
                     // a piece whose 128-byte line lies wholly inside this chunk's run of the row is read once: non-temporal; a line shared
                     // with the neighbouring chunk (or row) keeps the default policy, so that L2 holds the halves that WILL be read again
@@ -251,22 +216,19 @@ __device__ __forceinline__ void stage_group(const KParams& p, const unsigned grp
                     const unsigned r0 = xt_lo + (unsigned)cc * xrowb + (unsigned)q * (CH * DIM * 8);
                     const unsigned rend = xt_lo + (unsigned)(cc + 1) * xrowb, r1 = r0 + CH * DIM * 8 < rend ? r0 + CH * DIM * 8 : rend;
                     const unsigned long long inner = __ballot(line >= r0 && line + 128u <= r1);
+                    unsigned keep;
                     unsigned long long keepx;
                     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_mov_b64 %1, exec\n\ts_and_b64 exec, %1, %5\n\tglobal_load_lds_dwordx4 %2, %3 nt\n\t"
                                  "s_andn2_b64 exec, %1, %5\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
                                  : "=&s"(keep), "=&s"(keepx) : "v"(xo + (unsigned)cc * xrowb), "s"(xt), "s"(slot + (unsigned)i * (unsigned)KIB_B), "s"(inner) : "memory", "scc");      // (s_and_b64 / s_andn2_b64 write SCC: ADVICE r5)
-                } else
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" WLSQM_STAGE_DMA_POLICY "\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(xo + (unsigned)cc * xrowb), "s"(xt), "s"(slot + (unsigned)i * (unsigned)KIB_B) : "memory");
+                } else lds_dma_b128(xo + (unsigned)cc * xrowb, xt, slot + (unsigned)i * (unsigned)KIB_B);
             }
             if (want_f) {
 #pragma unroll
                 for (int i = 0; i < FNI; ++i) {
                     int cc = fc0 + i * FCPI;
                     cc = cc < nvalid ? cc : nvalid - 1;
-                    unsigned keep;
-                    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" WLSQM_STAGE_DMA_POLICY "\n\ts_mov_b32 m0, %0"
-                                 : "=&s"(keep) : "v"(fo + (unsigned)cc * frowb), "s"(ft), "s"(slot + (unsigned)(XNI + i) * (unsigned)KIB_B) : "memory");
+                    lds_dma_b128(fo + (unsigned)cc * frowb, ft, slot + (unsigned)(XNI + i) * (unsigned)KIB_B);
                 }
             }
         }
@@ -296,11 +258,8 @@ __device__ __forceinline__ void stage_group(const KParams& p, const unsigned grp
     // neighbour (a second), then the chunk (a third) were three memory latencies in a row at the head of every 64-case group, ~3.5 us of a
     // lone wave's 18-26 us per group (ISA: s_waitcnt vmcnt(1) / vmcnt(0) in front of the chunk's first load); now they overlap.
     // Measured (tools/ab_unit.sh, one box, profiles/r05f_ab_early_fetch.txt): configs[2] 0.392 -> 0.3876 ms (+1.2 %); configs[1] and configs[4]
-    // within +-0.5 % either way (on for the 15-unknown systems and up: 2).  The head of a group is not where a lone wave loses its time.
-#ifndef WLSQM_STAGE_EARLY_FETCH
-#define WLSQM_STAGE_EARLY_FETCH 2
-#endif
-    constexpr bool EARLY = (WLSQM_STAGE_EARLY_FETCH != 0) && !GATHER && !RAGGED && (WLSQM_STAGE_EARLY_FETCH == 1 || NO > 10);      // (2: the 15-unknown systems and up only)
+    // within +-0.5 % either way, so it is on for the 15-unknown systems and up only.  The head of a group is not where a lone wave loses its time.
+    constexpr bool EARLY = !GATHER && !RAGGED && NO > 10;      // (2: the 15-unknown systems and up only)
     if constexpr (EARLY && DMA) { dma_prime(QK); if constexpr (PF == 0) dma_fetch(QK - 1); }      // (a ring of one slot: its only chunk)
     else if constexpr (EARLY) fetch_into(xr, fr, QK - 1);
     // (every scalar of the case is requested before the first of them is looked at: the mask arithmetic below waits for its own)
@@ -435,13 +394,7 @@ __device__ __forceinline__ void stage_group(const KParams& p, const unsigned grp
                         double w = weight(d2, inv_max, uniform);
                         double f = GATHER ? cf[ks] : frow[ks];
                         if (MASKED) { w = live ? w : 0.0; f = live ? f : 0.0; }
-#ifndef WLSQM_STAGE_OUTER3D
-#define WLSQM_STAGE_OUTER3D 1
-#endif
-#ifndef WLSQM_STAGE_OUTER3D_FROM
-#define WLSQM_STAGE_OUTER3D_FROM 3
-#endif
-                        if constexpr (DIM == 3 && ORDER >= WLSQM_STAGE_OUTER3D_FROM && WLSQM_STAGE_OUTER3D) accumulate_moments_outer3d<ORDER, (PART == 1 || PART == 2) ? PART : 0>(mu, nu, d, w, f);
+                        if constexpr (DIM == 3 && ORDER >= 3) accumulate_moments_outer3d<ORDER, (PART == 1 || PART == 2) ? PART : 0>(mu, nu, d, w, f);
                         else accumulate_moments_best<DIM, ORDER>(mu, nu, d, w, f);
                     }
                 }
@@ -662,7 +615,7 @@ __device__ __forceinline__ void stage_group(const KParams& p, const unsigned grp
 #pragma unroll
             for (int i = j + 1; i < NO; ++i) L[tri<NO>(j, i) * 64] = t[i];
             L[tri<NO>(j, j) * 64] = inv;
-            if (WLSQM_STAGE_SOLVE_BARRIERS) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
         }
         // (ldlt_factor<N2>, one elimination step at a time: steps interleaved by the scheduler keep more of the matrix in flight
         // than the lane has registers for)
@@ -677,7 +630,7 @@ __device__ __forceinline__ void stage_group(const KParams& p, const unsigned grp
                 R[tri<N2>(j, i)] = t;
             }
             R[tri<N2>(j, j)] = inv;
-            if (WLSQM_STAGE_SOLVE_BARRIERS) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
         }
         // substitution: forward through the LDS rows, both directions in the register block, backward through the LDS rows
 #pragma unroll
@@ -685,12 +638,12 @@ __device__ __forceinline__ void stage_group(const KParams& p, const unsigned grp
 #pragma unroll
             for (int i = j + 1; i < NO; ++i) sol[i] = fma(-L[tri<NO>(j, i) * 64], sol[j], sol[i]);
         }
-        if (WLSQM_STAGE_SOLVE_BARRIERS) __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int j = 0; j < N2; ++j) {
 #pragma unroll
             for (int i = j + 1; i < N2; ++i) sol[R0 + i] -= R[tri<N2>(j, i)] * sol[R0 + j];
-            if (WLSQM_STAGE_SOLVE_BARRIERS) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int j = N2 - 1; j >= 0; --j) {
@@ -698,7 +651,7 @@ __device__ __forceinline__ void stage_group(const KParams& p, const unsigned grp
 #pragma unroll
             for (int i = j + 1; i < N2; ++i) v -= R[tri<N2>(j, i)] * sol[R0 + i];
             sol[R0 + j] = v;
-            if (WLSQM_STAGE_SOLVE_BARRIERS) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int j = R0 - 1; j >= 0; --j) {
@@ -794,8 +747,9 @@ __device__ __forceinline__ void stage_group(const KParams& p, const unsigned grp
 }
 
 __host__ __device__ constexpr int stage_minw(int NO, int PART, bool GATHER) {
-    return PART == 5 ? 1 : NO <= 6 ? (GATHER ? WLSQM_STAGE_MINW6G : WLSQM_STAGE_MINW6) : NO <= 10 ? (GATHER ? WLSQM_STAGE_MINW10G : WLSQM_STAGE_MINW10) :
-           NO <= 15 ? WLSQM_STAGE_MINW15 : (NO == 35 && !GATHER) ? WLSQM_STAGE_MINW35 : 1;
+    // (the gathering form of the systems with 7..10 unknowns keeps its SIMD: at two waves 3D order 2 spills; the 15-unknown systems and the
+    // two moment passes of the 35-unknown ones too: two waves leave ~100 sums per lane no room, 1 898 / 49 spilled registers)
+    return PART == 5 ? 1 : NO <= 6 ? (GATHER ? 2 : WLSQM_STAGE_MINW6) : NO <= 10 ? (GATHER ? 1 : WLSQM_STAGE_MINW10) : 1;
 }
 
 template <int DIM, int ORDER, int PART = 0, bool GATHER = false, int RAG = 0>

@@ -29,39 +29,35 @@
 // Round 5: the 15-unknown re-staging forms take their chunks by LDS-DMA (DMA at the kernel: 168 -> 40 registers in scratch, C3+iter@400k
 // 1.33 -> 1.10 ms; profiles/r05j_refine_dma.txt).
 //
-// Measured and left off (switches at the top; records under profiles/r04zb_*): two chunks in flight, the next pass's first chunk behind
-// the current pass's last, two waves per SIMD for the 10-unknown systems, partial sums of the model evaluation, the caches at three
-// waves per CU, and the SENS form (sensitivities on this mapping: correct, 1.2-1.9x slower than the inverse + matrix-core path).
+// Measured slower or flat and removed (the figures stand where the code was; records under profiles/r04zb_*): two chunks in flight,
+// partial sums of the model evaluation.  Measured and left off: the next pass's first chunk behind the current pass's last
+// (WLSQM_SITER_WARM below), two waves per SIMD for the 10-unknown systems (WLSQM_SITER_TWO_WAVES_UPTO), the caches at three waves per CU,
+// and the SENS form (sensitivities on this mapping: correct, 1.2-1.9x slower than the inverse + matrix-core path).
 #include <atomic>
 #include <type_traits>
 
+#include "wlsqm_chunk.hpp"
 #include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 #include "wlsqm_moments.hpp"
 
+// ---- compile-time switches (tools/ab_unit.sh rebuilds this unit with -DNAME=value; the table of all of them: DESIGN section 8)
 #ifndef WLSQM_SITER_GRP
-#define WLSQM_SITER_GRP 4           // neighbours of a lane in flight in the moment pass and in a sweep
-#endif
-#ifndef WLSQM_SITER_MODEL_CHAINS
-#define WLSQM_SITER_MODEL_CHAINS 1  // partial sums of the model evaluation in a sweep (3, also with -amdgpu-sched-strategy=max-ilp: flat, profiles/r04zb_ab_siter_chains.txt)
-#endif
-#ifndef WLSQM_SITER_REDUCED
-#define WLSQM_SITER_REDUCED 1       // 15-unknown systems: a case with exactly F known keeps the factor of its 14 x 14 system
-#endif
-#ifndef WLSQM_SITER_WARM
-#define WLSQM_SITER_WARM 0          // 1: the first chunk of the next pass is requested behind the last chunk of the current one (measured slower, off: see the kernel)
+#define WLSQM_SITER_GRP 4           // neighbours of a lane in flight in the moment pass and in a sweep (2 / 4 / 8: flat, profiles/r04zb_ab_siter_grp.txt)
 #endif
 #ifndef WLSQM_SITER_TWO_WAVES_UPTO
-#define WLSQM_SITER_TWO_WAVES_UPTO 6    // systems up to this many unknowns are compiled for two waves per SIMD (re-staging form)
+#define WLSQM_SITER_TWO_WAVES_UPTO 6    // systems up to this many unknowns are compiled for two waves per SIMD, re-staging form (10: measured slower, profiles/r04zb_ab_siter_two_waves.txt)
 #endif
-#ifndef WLSQM_SITER_DEEP
-#define WLSQM_SITER_DEEP 0          // 1: two chunks in flight for the systems with 7 .. 10 unknowns (see the kernel: measured slower, off)
+#ifndef WLSQM_SITER_WARM
+#define WLSQM_SITER_WARM 0          // 1: the first chunk of the next pass is requested behind the last chunk of the current one (measured slower, see the kernel; the switch stays because the unit compiles to other code without its `inflight` flag)
+#endif
+#ifndef WLSQM_SITER_DMA_SKEW
+#define WLSQM_SITER_DMA_SKEW 1      // 16-byte units by which a load instruction's KiB of the LDS-DMA image is shifted (0: 8-way bank conflicts of the b128 reads, see KIB2 in the kernel)
 #endif
 
 namespace wlsqm {
 
 namespace siter {
-typedef double d2_ __attribute__((ext_vector_type(2)));
 constexpr int CH = 8;               // neighbours per staged chunk
 __host__ __device__ constexpr int sens_group(int no) { return no <= 6 ? 4 : 2; }       // neighbours per sens tile: at most 16 pieces of 16 bytes per case
 __host__ __device__ constexpr int pitch2(int doubles) {               // row pitch in 16-byte units: odd, so that 16 lanes' b128 reads hit 16 different slots
@@ -84,29 +80,22 @@ __host__ __device__ constexpr int pitch2(int doubles) {               // row pit
 // DMA (round 5): the re-staging forms of the 15-unknown systems take their chunks by global_load_lds_dwordx4 into a ring of two slots
 // (lane-linear image and hand-counted waits: fit_stage.hip) — at the same one wave per SIMD: the point is the ~50 registers the staging
 // sets, their addresses and the hoisted LDS reads occupied in a kernel that spilled into scratch next to its 105-entry factor.
-#ifndef WLSQM_SITER_DMA
-#define WLSQM_SITER_DMA 1
-#endif
 template <int DIM, int ORDER, bool RESIDENT, bool SENS, int CACHE = 0>
 __global__ __launch_bounds__(64, (!RESIDENT && !SENS && CACHE == 0 && ndofs(DIM, ORDER) <= WLSQM_SITER_TWO_WAVES_UPTO) ? 2 : 1) void fit_stage_refine_kernel(const KParams p, const int XP2r, const int FP2r) {
     static_assert(CACHE == 0 || (!RESIDENT && !SENS), "the caches belong to the re-staging refinement form");
     constexpr bool WCACHE = CACHE == 1, FCACHE = CACHE == 2;
     using namespace siter;
     constexpr int NO = ndofs(DIM, ORDER), NE = NO * (NO + 1) / 2, NM = mom_count<DIM>(2 * ORDER);
-    constexpr bool DMA = (WLSQM_SITER_DMA != 0) && !RESIDENT && !SENS && NO == 15;
+    constexpr bool DMA = !RESIDENT && !SENS && NO == 15;
     constexpr int SG = sens_group(NO), SR = SG * NO / 2, TP2 = pitch2(SG * NO);      // neighbours per sens tile; 16-byte pieces of a case's tile; tile pitch
     constexpr int TILE2 = SENS ? 64 * TP2 : 0;
-    constexpr int XPC = CH * DIM * 8 / 16, FPC = CH * 8 / 16;        // 16-byte pieces of one case's chunk: coordinates, values
-    constexpr int XCPI = 64 / XPC, XNI = (64 + XCPI - 1) / XCPI;      // whole cases per load instruction; instructions per chunk
-    constexpr int FCPI = 64 / FPC, FNI = 64 / FCPI;
+    using Pieces = ChunkPieces<DIM, CH>;                             // (wlsqm_chunk.hpp: which lane moves which 16-byte piece)
+    constexpr int XPC = Pieces::XPC, FPC = Pieces::FPC, XCPI = Pieces::XCPI, XNI = Pieces::XNI, FCPI = Pieces::FCPI, FNI = Pieces::FNI;
     constexpr int GRP = WLSQM_SITER_GRP < CH ? WLSQM_SITER_GRP : CH;
     constexpr int XP2s = pitch2(CH * DIM), FP2s = pitch2(CH);         // chunk staging pitches (not RESIDENT)
     // (DMA) 16-byte units from one load instruction's image to the next: a KiB + ONE slot (round 6, as in fit_stage.hip: dense KiB blocks put the
     // 16 lanes of a ds_read_b128 group on two to four slots of the bank row — `SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE` 0.84 on configs[2]
     // with refinement, profiles/r05_pmc_refine.txt; 2D: slot (8 (c mod 8)) mod 16 unskewed)
-#ifndef WLSQM_SITER_DMA_SKEW
-#define WLSQM_SITER_DMA_SKEW 1
-#endif
     constexpr int KIB2 = 64 + WLSQM_SITER_DMA_SKEW;
     constexpr int SLOT2 = (XNI + FNI) * KIB2;                         // 16-byte units of a slot
     constexpr int STAGE2 = DMA ? 2 * SLOT2 : 64 * XP2s + 64 * FP2s, OUT2 = 64 * NO / 2;
@@ -147,14 +136,13 @@ __global__ __launch_bounds__(64, (!RESIDENT && !SENS && CACHE == 0 && ndofs(DIM,
     const bool xlane = lane < XCPI * XPC;
     const char* const xtile = reinterpret_cast<const char*>(p.xk + t0 * (long long)K * DIM);
     const char* const ftile = reinterpret_cast<const char*>(p.fk + t0 * (long long)K);
-    // DEEP: TWO chunks in flight (two register sets) — an experiment, OFF.  The idea: a lone wave waits out every exposed load, and with
+    // TWO chunks in flight (two register sets) — measured slower, removed.  The idea: a lone wave waits out every exposed load, and with
     // one chunk in flight a sweep of configs[4]'s shape computes ~1.3 us per chunk while 1 024 waves x 18 KB in flight at the measured
     // 7.5 TB/s say ~2.5 us for a chunk to come back from L2 / the Infinity Cache.  Measured (profiles/r04zb_ab_siter_deep.txt, max_iter
-    // 10): 3D order 2 at 40 neighbours, 1M cases, 3.51 against 2.03 ms, at 124 neighbours 3.83 against 2.92 — the second set costs 118
+    // 10): 3D order 2 at 40 neighbours, 1M cases, 3.51 against 2.03 ms, at 124 neighbours 3.83 against 2.92 — the second set cost 118
     // spilled registers and 13 scratch reloads of load addresses per chunk; 2D order 3 at 80 neighbours (no spill): 1.252 against
     // 1.240 ms, i.e. the latency is NOT what bounds the sweeps there.
-    constexpr bool DEEP = (WLSQM_SITER_DEEP != 0) && !RESIDENT && NO > 6 && NO <= 10;      // (the 6-unknown systems run two waves per SIMD)
-    d2_ xr[XNI], fr[FNI], xr2[DEEP ? XNI : 1], fr2[DEEP ? FNI : 1];
+    d2_ xr[XNI], fr[FNI];
     auto fetch_into = [&](d2_ (&xr)[XNI], d2_ (&fr)[FNI], int q, auto nof_tag) __attribute__((always_inline)) {
         constexpr bool NOF = decltype(nof_tag)::value;                // (FCACHE, sweeps) the values are in LDS already: coordinates only
         unsigned xo = (unsigned)q * (CH * DIM * 8) + (unsigned)xsub * 16u, fo = (unsigned)q * (CH * 8) + (unsigned)fsub * 16u;
@@ -188,7 +176,7 @@ __global__ __launch_bounds__(64, (!RESIDENT && !SENS && CACHE == 0 && ndofs(DIM,
             for (int i = 0; i < FNI; ++i) fl[i * FCPI * FP2] = fr[i];
         }
     };
-    constexpr bool WARM = (WLSQM_SITER_WARM != 0) && !RESIDENT && !DEEP;
+    constexpr bool WARM = (WLSQM_SITER_WARM != 0) && !RESIDENT;
     bool inflight = false;                                            // (wave-uniform) chunk Q - 1 of the next pass is on its way in (xr, fr)
     double* const wrow = reinterpret_cast<double*>(lds_d) + lane * FP2r;      // (WCACHE / FCACHE) this lane's weights / values; FP2r: the pitch in doubles (odd)
     const d2_* const xrow = DMA ? lds + (lane / XCPI) * KIB2 + (lane % XCPI) * XPC : xs + lane * XP2;      // (DMA: in slot 0; slot q & 1 at + SLOT2)
@@ -205,18 +193,14 @@ __global__ __launch_bounds__(64, (!RESIDENT && !SENS && CACHE == 0 && ndofs(DIM,
             for (int i = 0; i < XNI; ++i) {
                 int cc = xc0 + i * XCPI;
                 cc = cc < nvalid ? cc : nvalid - 1;
-                unsigned keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(xo + (unsigned)cc * xrowb), "s"(xt), "s"(slot + (unsigned)i * (unsigned)(KIB2 * 16)) : "memory");
+                lds_dma_b128(xo + (unsigned)cc * xrowb, xt, slot + (unsigned)i * (unsigned)(KIB2 * 16));
             }
             if constexpr (!NOF) {
 #pragma unroll
                 for (int i = 0; i < FNI; ++i) {
                     int cc = fc0 + i * FCPI;
                     cc = cc < nvalid ? cc : nvalid - 1;
-                    unsigned keep;
-                    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                                 : "=&s"(keep) : "v"(fo + (unsigned)cc * frowb), "s"(ft), "s"(slot + (unsigned)(XNI + i) * (unsigned)(KIB2 * 16)) : "memory");
+                    lds_dma_b128(fo + (unsigned)cc * frowb, ft, slot + (unsigned)(XNI + i) * (unsigned)(KIB2 * 16));
                 }
             }
         }
@@ -292,13 +276,6 @@ __global__ __launch_bounds__(64, (!RESIDENT && !SENS && CACHE == 0 && ndofs(DIM,
                 dma_wait(q >= 1, nof_tag);
                 compute(q);
             }
-        } else if constexpr (DEEP) {
-            fetch_into(xr, fr, Q - 1, nof_tag);
-            if (Q > 1) fetch_into(xr2, fr2, Q - 2, nof_tag);
-            for (int q = Q - 1; q >= 0; q -= 2) {
-                step(xr, fr, q, 2);
-                if (q >= 1) step(xr2, fr2, q - 1, 2);
-            }
         } else {
             if (staged && !(WARM && inflight)) fetch_into(xr, fr, Q - 1, nof_tag);
             for (int q = Q - 1; q >= 0; --q) step(xr, fr, q, 1);
@@ -360,7 +337,7 @@ __global__ __launch_bounds__(64, (!RESIDENT && !SENS && CACHE == 0 && ndofs(DIM,
     // A case with exactly the function value known (knowns = b?_F: the reference's default mask and BASELINE configs[2]) keeps the factor of
     // its 14 x 14 system (fit_stage.hip: 105 + 14 entries to expand, factor and substitute instead of 120 + 15), chosen by the case's
     // own mask — a mixed wave runs both forms, a case's bits do not depend on its wave-mates.  M then holds the 105 entries of that factor.
-    constexpr bool REDUCED = (WLSQM_SITER_REDUCED != 0) && NO == 15 && !SENS;
+    constexpr bool REDUCED = NO == 15 && !SENS;
     constexpr int N1 = NO - 1, NE1 = N1 * (N1 + 1) / 2;
     const bool mine1 = REDUCED && known == 1ull && dropped == 0ull;
     if constexpr (REDUCED) {
@@ -489,21 +466,10 @@ __global__ __launch_bounds__(64, (!RESIDENT && !SENS && CACHE == 0 && ndofs(DIM,
             double w;
             if constexpr (WCACHE) w = wrow[k];
             else { w = weight(sqdist(d), inv_max, uniform); w = live ? w : 0.0; }
-#if WLSQM_SITER_MODEL_CHAINS > 1
-            // taylor_*D (polyeval.pyx): sum_a c[a] fi[a], as WLSQM_SITER_MODEL_CHAINS interleaved partial sums (shorter dependent chains)
-            double part[WLSQM_SITER_MODEL_CHAINS];
-#pragma unroll
-            for (int i = 0; i < WLSQM_SITER_MODEL_CHAINS; ++i) part[i] = i == 0 ? fi[0] : 0.0;
-#pragma unroll
-            for (int a = 1; a < NO; ++a) part[a % WLSQM_SITER_MODEL_CHAINS] = fma(cc[a], fi[a], part[a % WLSQM_SITER_MODEL_CHAINS]);
-            double model = part[0];
-#pragma unroll
-            for (int i = 1; i < WLSQM_SITER_MODEL_CHAINS; ++i) model += part[i];
-#else
+            // (the sum as 3 interleaved partial sums, also with -amdgpu-sched-strategy=max-ilp: measured flat, removed — profiles/r04zb_ab_siter_chains.txt)
             double model = fi[0];                                     // taylor_*D (polyeval.pyx): sum_a c[a] fi[a]
 #pragma unroll
             for (int a = 1; a < NO; ++a) model = fma(cc[a], fi[a], model);
-#endif
             const double res = live ? f - model : 0.0;
             const double ar = fabs(res);
             norm = ar > norm ? ar : norm;                             // impl.pyx:1037-1041
@@ -614,8 +580,8 @@ static int launch_stage_refine(const KParams& p, long long K, hipStream_t stream
         const int WP = (Q * CH) | 1;
         // (static LDS of the kernel: the padded staging rows, or the DMA form's two slots of a KiB per load instruction — 24 KB for the
         // 15-unknown systems, whose weight cache therefore ends at 30 neighbours instead of 48)
-        constexpr bool dma15 = (WLSQM_SITER_DMA != 0) && ndofs(DIM, ORDER) == 15;
-        constexpr int xni = 64 / (64 / (CH * DIM * 8 / 16)) + ((64 % (64 / (CH * DIM * 8 / 16))) ? 1 : 0), fni = 64 / (64 / (CH * 8 / 16));
+        constexpr bool dma15 = ndofs(DIM, ORDER) == 15;
+        constexpr int xni = ChunkPieces<DIM, CH>::XNI, fni = ChunkPieces<DIM, CH>::FNI;
         const size_t wbytes = (size_t)64 * WP * 8, stat = dma15 ? (size_t)2 * (xni + fni) * (1024 + 16 * WLSQM_SITER_DMA_SKEW) : (size_t)64 * (pitch2(CH * DIM) + pitch2(CH)) * 16;
         long long budget_kb = 40;                                    // four waves per CU (WLSQM_HIP_REFINE_CACHE_KB: A/B)
         env_int("WLSQM_HIP_REFINE_CACHE_KB", &budget_kb);

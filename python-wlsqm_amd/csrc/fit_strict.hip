@@ -33,10 +33,6 @@
 
 #pragma clang fp contract(off)      // the reference is gcc -O2 on x86-64: no contraction; the explicit fma() calls below are polyeval.pyx's own
 
-#ifndef WLSQM_STRICT_ROWS_MINW
-#define WLSQM_STRICT_ROWS_MINW 0      // A/B: waves per SIMD the row-per-lane kernel is compiled for (0: rows_minw below)
-#endif
-
 namespace wlsqm {
 
 namespace strict {
@@ -447,13 +443,10 @@ __device__ __forceinline__ bool fit_strict_group_is_plain(const KParams& p, long
     return __syncthreads_or(mine ? 1 : 0) == 0;
 }
 
-#ifndef WLSQM_STRICT_REG_MINW6
-#define WLSQM_STRICT_REG_MINW6 1      // waves per SIMD the register kernel of the systems up to 6 unknowns is compiled for: registers as needed (C2: 0.74 ms; capped for three / four waves it spills: 0.95 / 1.29; profiles/r03j_ab_strict_minw.txt)
-#endif
-#ifndef WLSQM_STRICT_REG_MINW10
-#define WLSQM_STRICT_REG_MINW10 1     // ... of the 10-unknown systems (C5: 2.00 ms; capped for two waves: 2.79)
-#endif
-__host__ __device__ constexpr int reg_minw(int NO) { return NO <= 6 ? WLSQM_STRICT_REG_MINW6 : WLSQM_STRICT_REG_MINW10; }
+// waves per SIMD the register kernels are compiled for: one, registers as needed.  Capped for more they spilled — measured slower, removed:
+// the systems up to 6 unknowns, C2: 0.74 ms, for three / four waves 0.95 / 1.29; the 10-unknown systems, C5: 2.00 ms, for two waves 2.79
+// (profiles/r03j_ab_strict_minw.txt)
+constexpr int REG_MINW = 1;
 
 // KN1: the groups whose 64 cases all have exactly the function value known (knowns = b?_F = 1, the reference's default mask): the
 // reduced system is DOFs 1 .. NO - 1, again with compile-time indices; the known value moves to the right-hand side term by term
@@ -651,7 +644,7 @@ __device__ __forceinline__ void fit_strict_reg_block(const KParams& p, const lon
 }
 
 template <int DIM, int ORDER, bool KN1>
-__global__ __launch_bounds__(64, reg_minw(ndofs(DIM, ORDER))) void fit_strict_reg_kernel(const KParams p) {
+__global__ __launch_bounds__(64, REG_MINW) void fit_strict_reg_kernel(const KParams p) {
     fit_strict_reg_block<DIM, ORDER, KN1>(p, blockIdx.x);
 }
 
@@ -698,7 +691,7 @@ __device__ __forceinline__ double grp_max(double v) {
 // VGPRs), 7.97 at three waves (168 + 33 spilled), 8.03 at four; with sensitivities 28.6 / 23.0 / 25.9; 3D order 2 with sensitivities:
 // 9.37 / 9.37 / 8.63 (profiles/r03j_ab_strict_minw.txt).  The 20- and 35-unknown systems keep their registers (242 / 389).
 __host__ __device__ constexpr int rows_minw(int NO) {
-    return WLSQM_STRICT_ROWS_MINW ? WLSQM_STRICT_ROWS_MINW : (NO > 16 ? 1 : NO > 10 ? 3 : 4);
+    return NO > 16 ? 1 : NO > 10 ? 3 : 4;
 }
 
 // (vblock: the workgroup's number in the batch)

@@ -30,8 +30,9 @@
 #include "wlsqm_dispatch.hpp"
 #include "wlsqm_kernels.hpp"
 
-#ifndef WLSQM_OP_NT
-#define WLSQM_OP_NT 2      // 1 = non-temporal loads of the fields (configs[3]: 16.9 against 14.7 ms), 2 = non-temporal stores of the results (1.0-1.6 % faster in three interleaved pairs, profiles/r03i_ab_c4_nt.txt: kept), 3 = both
+// ---- compile-time switches (tools/ab_unit.sh rebuilds this unit with -DNAME=value; the table of all of them: DESIGN section 8)
+#ifndef WLSQM_OP_NSET16
+#define WLSQM_OP_NSET16 3   // right-hand-side sets a wave of the 16-wave workgroups keeps in registers per step (128 registers per lane; the other workgroups: 4)
 #endif
 
 namespace wlsqm {
@@ -185,11 +186,8 @@ __global__ __launch_bounds__(64 * WPG) void solve_op_mfma_kernel(const OpParams 
                 // pieces beyond the fk row (K not a multiple of 8) replay the row's first pair: their operator columns are zero and
                 // the ragged mask below clears them
                 const int e = 8 * s + 2 * q;
-#if (WLSQM_OP_NT & 1)
-                const od2_ v = __builtin_nontemporal_load(reinterpret_cast<const od2_*>(src + (e < P.K ? e : 0)));
-#else
+                // (non-temporal loads of the fields measured slower, removed: configs[3] 16.9 against 14.7 ms, profiles/r03i_ab_c4_nt.txt)
                 const od2_ v = *reinterpret_cast<const od2_*>(src + (e < P.K ? e : 0));
-#endif
                 B[2 * s] = v.x; B[2 * s + 1] = v.y;
             }
         };
@@ -238,11 +236,8 @@ __global__ __launch_bounds__(64 * WPG) void solve_op_mfma_kernel(const OpParams 
                 const int a = e - row * no;
                 const int f = row / WPG, cs = row - f * WPG;                    // WPG is a power of two
                 if (!((smask[cs] >> a) & 1ull) && !(P.dbg & 1))
-#if (WLSQM_OP_NT & 2)
+                    // (non-temporal: 1.0-1.6 % faster than plain stores in three interleaved pairs, profiles/r03i_ab_c4_nt.txt; the plain form is removed)
                     __builtin_nontemporal_store(out[e + f * (runp - run)], &P.fi[(r0 + f) * P.sfi_r + (j0 + cs) * P.sfi_j + a]);
-#else
-                    P.fi[(r0 + f) * P.sfi_r + (j0 + cs) * P.sfi_j + a] = out[e + f * (runp - run)];
-#endif
             };
             if (no <= 8) {
                 const int e0 = (int)threadIdx.x, e1 = e0 + 64 * WPG;
@@ -263,9 +258,6 @@ __global__ __launch_bounds__(64 * WPG) void solve_op_mfma_kernel(const OpParams 
         // 14.5 -> 15.8 ms (conservative counts) / 16.1 ms (exact counts) — with one 16-wave workgroup per CU in lock step at the
         // barrier, a burst of 12 requests per wave followed by three compute + store phases suits this memory system better than
         // requests interleaved with the stores.  Kept as tools/experiments/solve_op_asm_pipeline.hip.
-#ifndef WLSQM_OP_NSET16
-#define WLSQM_OP_NSET16 3
-#endif
         constexpr int NSET = (WPG == 16 && KQ >= 8) ? WLSQM_OP_NSET16 : 4;   // (the 16-wave workgroups have 128 registers per lane)
         double B[NSET][KQ];
         for (long long r0 = 0; r0 < P.nrhs; r0 += 16 * NSET) {

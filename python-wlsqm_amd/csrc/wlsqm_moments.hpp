@@ -194,9 +194,7 @@ __device__ __forceinline__ void combine_triple(double (&out)[N], double (&in3)[3
 template <int DIM, int ORDER>
 __device__ __forceinline__ void accumulate_moments_best(double (&mu)[mom_count<DIM>(2 * ORDER)], double (&nu)[mom_count<DIM>(ORDER)],
                                                         const double (&d)[DIM], double w, double f) {
-#ifndef WLSQM_NO_OUTER_MOMENTS
     if constexpr (DIM == 2 && ORDER >= 3) { accumulate_moments_outer2d<ORDER>(mu, nu, d, w, f); return; }
-#endif
     accumulate_moments<DIM, ORDER>(mu, nu, d, w, f);
 }
 

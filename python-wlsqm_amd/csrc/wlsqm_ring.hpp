@@ -52,25 +52,11 @@ __device__ __forceinline__ void swap32(double& x, double& y) {
     x = __hiloint2double((int)hi.x, (int)lo.x); y = __hiloint2double((int)hi.y, (int)lo.y);
 }
 
-#ifndef WLSQM_RING_IBUF_PAD
-#define WLSQM_RING_IBUF_PAD 4    // ints of padding behind every pair of index rows (0: A/B)
-#endif
-#ifndef WLSQM_RING_FI_RUN
-#define WLSQM_RING_FI_RUN 1     // 3D branch-free solve: the 64 fi rows leave as one run of non-temporal 16-byte pieces through LDS instead of 8-byte pieces at an 80-byte pitch: configs[4] at 1M, interleaved, 0.3035-0.3086 against 0.3113-0.3159 ms (profiles/r03i_ab_ring_c5.txt)
-#endif
-#ifndef WLSQM_RING_FI_NT
-#define WLSQM_RING_FI_NT 0      // non-temporal for EVERY fi store of the ring: configs[2] unchanged (its rows already leave as a run), configs[4] 0.31 -> 0.46 ms with its 8-byte pieces at an 80-byte pitch — non-temporal pays for whole lines only
-#endif
+constexpr int RING_IBUF_PAD = 4;      // ints of padding behind every pair of index rows (GATHER: see ibuf in the kernel)
+// How the ring's fi stores leave: plain.  Non-temporal for EVERY one of them — measured slower, removed: configs[2] unchanged (its rows
+// already leave as a run), configs[4] 0.31 -> 0.46 ms with its 8-byte pieces at an 80-byte pitch — non-temporal pays for whole lines only.
 template <class T>
-__device__ __forceinline__ void ring_store(T* dst, const T v) {
-#if defined(WLSQM_RING_NO_STORE)      // experiment only: what the kernel costs without its results leaving (wrong output)
-    if (reinterpret_cast<uintptr_t>(dst) == 8) *dst = v;
-#elif WLSQM_RING_FI_NT
-    __builtin_nontemporal_store(v, dst);
-#else
-    *dst = v;
-#endif
-}
+__device__ __forceinline__ void ring_store(T* dst, const T v) { *dst = v; }
 
 template <int DIM, int K> struct RingGeom {
     static constexpr int WV = 64, TC = 16, LPC = 4;
@@ -117,10 +103,7 @@ __global__ __launch_bounds__(64, MINW) void fit_ring_kernel(const KParams p, con
     // group, addresses c RS + 30 h + ... with RS == 2 (mod 32) — land on the same bank pair for every c (both offsets are even in
     // 8-byte units: re-pitching the rows cannot separate them), a 2-way conflict on every coordinate read: SQ_LDS_BANK_CONFLICT 0.46
     // of the LDS-active cycles of configs[4] since round 2.  Interleaved, the offsets are 2 c + 3 h: 32 different bank pairs.
-#ifndef WLSQM_RING_INTERLEAVE3D
-#define WLSQM_RING_INTERLEAVE3D 1
-#endif
-    constexpr bool ILV = (DIM == 3) && (WLSQM_RING_INTERLEAVE3D != 0) && (G::KC == K) && !GATHER;
+    constexpr bool ILV = (DIM == 3) && (G::KC == K) && !GATHER;
     auto slot_of = [&](int kk) { return ILV ? G::LPC * kk + h : k0 + kk; };      // neighbour slot of this lane's kk-th term
 
     struct Meta { int nk, wm; long long kn; double xi[DIM]; };
@@ -130,7 +113,7 @@ __global__ __launch_bounds__(64, MINW) void fit_ring_kernel(const KParams p, con
     // (unpadded, the sixteen rows of a 64-slot tile start in the same bank: the lanes' reads of their own shares were 16-way conflicts —
     // SQ_LDS_BANK_CONFLICT 67 % of the LDS-active cycles of the kernel, profiles/r03k_pmc_new_kernels.txt; a pair of rows is the smallest
     // unit a 16-byte DMA piece never straddles for every even K)
-    constexpr int IPP = 2 * K + WLSQM_RING_IBUF_PAD;                      // ints per row pair
+    constexpr int IPP = 2 * K + RING_IBUF_PAD;                      // ints per row pair
     auto irow = [&](int r) { return (r >> 1) * IPP + (r & 1) * K; };      // first int of row r
     int nk_ahead = 0;                                                     // GATHER: nk of this lane's case in the tile whose indices are in ibuf
 
@@ -222,12 +205,9 @@ __global__ __launch_bounds__(64, MINW) void fit_ring_kernel(const KParams p, con
         // one region per 64-neighbour part, so that the active lanes of every DMA are a PREFIX of the wave (with the parts
         // interleaved per row the compiler threads the repeated lane condition into two paths and issues the full-row DMAs
         // once for the low and once for the high lanes: wrong rows for K > 64, measured)
-#ifndef WLSQM_RING_IMM_OFFSETS
-#define WLSQM_RING_IMM_OFFSETS 1
-#endif
         bool dma_done = false;
 #if defined(__HIP_DEVICE_COMPILE__)          // (the host pass drops the kernel's stub when it sees the non-zero immediate: device pass only)
-        if constexpr (WLSQM_RING_IMM_OFFSETS != 0 && G::PARTS == 1 && 3 * G::ROWB < 4096) {
+        if constexpr (G::PARTS == 1 && 3 * G::ROWB < 4096) {
             if (nvalid == TC) {
                 // full tile: four per-lane base addresses (rows 0, 4, 8, 12) and the instruction's immediate offset for the three rows
                 // behind each (0 .. 3 ROWB < 4 KiB) instead of sixteen 64-bit multiply-adds; the immediate is added to the LDS address
@@ -417,7 +397,8 @@ __global__ __launch_bounds__(64, MINW) void fit_ring_kernel(const KParams p, con
         expand_moments_from<DIM, ORDER>([&](int i) { return entry(i); }, [&](int i) { return entry(NM + i); }, M, rhs);
         ldlt_factor<NO>(M);
         ldlt_solve<NO>(M, rhs);
-#if WLSQM_RING_FI_RUN
+        // (3D: the 64 fi rows leave as one run of non-temporal 16-byte pieces through LDS instead of 8-byte pieces at an 80-byte pitch: configs[4]
+        // at 1M, interleaved, 0.3035-0.3086 against 0.3113-0.3159 ms, profiles/r03i_ab_ring_c5.txt)
         if constexpr (G::FI_STAGE) {
             static_assert(!G::FI_STAGE || NO <= G::FI_STAGE_NO, "staging area behind the ring");
             // the 64 cases are consecutive (four consecutive tiles, all valid): their rows are ONE run of 64 * NO doubles
@@ -435,15 +416,11 @@ __global__ __launch_bounds__(64, MINW) void fit_ring_kernel(const KParams p, con
                 return;
             }
         }
-#endif
 #pragma unroll
         for (int a = 0; a < NO; ++a) ring_store(&fio[a], rhs[a]);
         havep = false;
     };
-#ifndef WLSQM_RING_FUSE_SOLVE
-#define WLSQM_RING_FUSE_SOLVE 1
-#endif
-    constexpr bool FUSE = (WLSQM_RING_FUSE_SOLVE != 0) && DIM == 3;
+    constexpr bool FUSE = DIM == 3;
 
     constexpr bool DELAY = (DIM == 3);
     bool pending = false;
@@ -606,7 +583,7 @@ static int ring_tiles_per_wg() {
 
 template <int DIM, int K, bool GATHER> struct RingLaunchGeom {        // ring + (index-based) the index buffer of the tile ahead
     static constexpr int TC = RingGeom<DIM, K>::TC;
-    static constexpr size_t LDS_BYTES = RingGeom<DIM, K>::LDS_BYTES + (GATHER ? (size_t)(TC / 2) * (2 * K + WLSQM_RING_IBUF_PAD) * 4 : 0) + (RingGeom<DIM, K>::FI_STAGE ? (size_t)64 * RingGeom<DIM, K>::FI_STAGE_NO * 8 : 0);
+    static constexpr size_t LDS_BYTES = RingGeom<DIM, K>::LDS_BYTES + (GATHER ? (size_t)(TC / 2) * (2 * K + RING_IBUF_PAD) * 4 : 0) + (RingGeom<DIM, K>::FI_STAGE ? (size_t)64 * RingGeom<DIM, K>::FI_STAGE_NO * 8 : 0);
 };
 
 template <int DIM, int ORDER, int K, int UNR, int MINW, bool GATHER = false>

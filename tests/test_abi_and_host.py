@@ -436,3 +436,23 @@ def test_dispatch_header_is_the_one_place():
             declared = set(re.findall(head + ";", t, flags=re.M))
             defined = set(re.findall(head + r"\{", t, flags=re.M))
             assert declared <= defined, "%s declares %s" % (f, sorted(declared - defined))
+
+
+def test_compile_time_switches_are_listed_and_at_the_head():
+    """The compile-time switches of csrc/ (plain text scans): (a) every "#ifndef WLSQM_X" stands in its file's head block, above the first
+    `namespace` — none inside a function body, where nobody finds it; (b) the switches found are the rows of the table in DESIGN.md §8.2,
+    file by file, in both directions: a switch that is added, renamed or retired changes the table with it."""
+    csrc = os.path.join(ROOT, "python-wlsqm_amd", "csrc")
+    found = set()
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".hpp")):
+            continue
+        t = open(os.path.join(csrc, f)).read()
+        first_ns = re.search(r"^namespace\b", t, flags=re.M)
+        for m in re.finditer(r"^[ \t]*#[ \t]*ifndef[ \t]+(WLSQM_[A-Z][A-Z0-9_]*)", t, flags=re.M):
+            assert first_ns is None or m.start() < first_ns.start(), "%s: #ifndef %s below the first namespace" % (f, m.group(1))
+            found.add((f, m.group(1)))
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    rows = re.findall(r"^\| `(\w+\.h(?:ip|pp))` \| `(WLSQM_[A-Z0-9_]+)` \| \S+ \| .+ \|$", design, flags=re.M)
+    assert len(rows) == len(set(rows)) and len({name for _, name in rows}) == len(rows)
+    assert found == set(rows), sorted(found ^ set(rows))

@@ -2,6 +2,8 @@
 # usage (GPU box, repo root): bash tools/ab_unit.sh UNIT CONFIG "-DFLAG=1" ...   — A/B of compile-time variants of one translation unit
 # (csrc/UNIT.hip) on one BASELINE config of bench.py: times the library as built, then rebuilds UNIT.o with each flag set given,
 # relinks and times again (kernel ms, fraction of the HBM peak), three passes each, and restores the library.
+# The flags that exist: the table of compile-time switches in DESIGN.md section 8.2 (each stands in the head block of its csrc/ file);
+# a -D of any other name compiles and changes nothing.
 set -euo pipefail
 UNIT="$1"; CFG="$2"; shift 2
 PKG=python-wlsqm_amd

@@ -2,6 +2,8 @@
 # usage (GPU box, repo root): bash tools/with_variant.sh UNIT "-DFLAG=1 ..." COMMAND [ARGS...]
 # Runs COMMAND with csrc/UNIT.hip rebuilt under the given flags and relinked into the library; the library as built comes back
 # whatever happens (e.g. a profile of a compile-time variant: ... bash tools/profile_config.sh TAG C5 1000000 1404000000).
+# The flags that exist: the table of compile-time switches in DESIGN.md section 8.2 (each stands in the head block of its csrc/ file);
+# a -D of any other name compiles and changes nothing.
 set -euo pipefail
 UNIT="$1"; FLAGS="$2"; shift 2
 PKG=python-wlsqm_amd
