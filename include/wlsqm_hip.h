@@ -257,7 +257,11 @@ int wlsqm_hip_expert_solve_device(wlsqm_expert* h, void* stream, const double* f
  * examples/wlsqm_example.py:103-133).  For every point of the device-resident cloud S[npoints, dimension] the k nearest
  * OTHER points, ascending by (distance, index), into the device array hoods[npoints, k] (int32) — the `hoods` argument of
  * wlsqm_hip_fit_cloud_device.  Exact (uniform-grid search with a provable stop test).  1 <= k <= min(npoints - 1, 213).
- * Synchronises `stream` before returning. */
+ * Synchronises `stream` before returning.
+ * Domain of this and the three searches below: finite coordinates (a NaN or an infinity anywhere in S is WLSQM_EVALUE,
+ * "non-finite coordinates") whose bounding box has a representable squared diagonal (else WLSQM_EVALUE: every squared distance
+ * would be inf).  Squared distances must not underflow either: points closer than about 2^-511 on every axis count as
+ * coincident.  Coincident points are legal; they tie, and ties are ordered by index. */
 int wlsqm_hip_knn_device(int dimension, int64_t npoints, const double* S, int k, int32_t* hoods, int device, void* stream);
 /* Extension: the same search asked only by the FIRST nquery points of the cloud; the remaining npoints - nquery points are
  * candidates only (hoods[nquery, k], indices into S).  The rank of a partitioned cloud searches its own points against its
@@ -271,9 +275,15 @@ int wlsqm_hip_ball_device(int dimension, int64_t npoints, const double* S, doubl
                           int32_t* hoods, int32_t* nk, int device, void* stream);
 /* Extension: nearest point of the device-resident cloud S[ndata, dimension] for each of the device-resident query points
  * X[nquery, x_stride] (queries are not members of the cloud): nearest[nquery] (int64 device array, indices into S; ties go
- * to the smaller index).  What ExpertSolver.interpolate(mode='nearest') needs (cKDTree.query in expert.pyx:830-895). */
+ * to the smaller index).  What ExpertSolver.interpolate(mode='nearest') needs (cKDTree.query in expert.pyx:830-895).
+ * A query with a NaN coordinate, or one so far away that its squared distances overflow, has no nearest point: it gets
+ * 2^31 - 1, which is no index of S (an interpolation plan evaluates to NaN there). */
 int wlsqm_hip_nearest_device(int dimension, int64_t ndata, const double* S, int64_t nquery, const double* X,
                              int64_t x_stride, int64_t* nearest, int device, void* stream);
+/* Extension: the shape of the uniform grid that the four searches above lay over a cloud of npoints points with the bounding
+ * box lo[dimension] .. hi[dimension]: g[dimension] cells per axis of side cell[dimension], about 4 points per cell, at most
+ * 2^27 cells in all.  Host arithmetic only: needs no device.  WLSQM_EVALUE for a box outside the searches' domain. */
+int wlsqm_hip_grid_shape_host(int dimension, int64_t npoints, const double* lo, const double* hi, int32_t* g, double* cell);
 
 /* Extension: build the stored solution operator of the prepared geometry now (8 x 16 x K' bytes per case, K' = the neighbour
  * slots rounded up to a multiple of 8; shared with guests), so that later stacked solves only enqueue work — e.g. before a stream

@@ -11,6 +11,20 @@
 //      free), until the k-th best distance is no larger than the distance to the unvisited region;
 //   4. the k results sorted by (distance, index) — cKDTree's order — and written to hoods[point, :].
 // Exact (no approximation): the stop test is a proof that no unvisited point can be closer.
+//
+// Why the stop test holds.  An unvisited point p has, on some axis, a cell number beyond the visited block, say >= j = cq + r + 1.
+// Its number is the rounded (p - lo) * inv_cell and the block's boundary is the rounded B = lo + j * cell: two independent chains of
+// about five roundings, which differ by less than delta = 10 eps j cell.  But p and B are both REPRESENTABLE numbers.  Where the
+// coordinates' spacing u exceeds 2 delta (a cloud away from the origin, or a coarse lattice) a p below B would have to be a whole
+// spacing below it, which delta + u / 2 does not allow: there p >= B exactly.  Where u <= 2 delta, B - p <= 2 delta = 20 eps j cell
+// (eps = 2^-53), and that is what the sliver pays for: max(1e-9, 2^-48 g) cell, which is 1e-9 cell up to 2^18 cells on an axis (every
+// 2D and 3D grid) and grows with the 1D grids beyond, up to 6e-8 cell at the cap of 2^24.  So p >= B - sliver on that axis, and from
+// there on everything is monotone: the rounded p - x is no smaller than `reach`, its rounded square no smaller than the rounded reach * reach,
+// and the other axes only add to it, fused or not.  The test compares the numbers the kernel computes, not the real ones.
+//
+// Domain.  Finite coordinates whose bounding box has a representable squared diagonal (larger boxes are rejected: every candidate's
+// d2 would be inf and no row could fill).  Squared distances must not underflow either: points closer than about 2^-511 of each other
+// on every axis are at distance 0 for the search, as coincident points are (those stay legal: ties, broken by index).
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -182,8 +196,8 @@ __global__ __launch_bounds__(64) void knn_query_kernel(const double* __restrict_
 #pragma unroll
             for (int m = 0; m < DIM; ++m) {
                 // (minus a sliver: a point's cell number and this boundary are rounded independently)
-                if (cq[m] - r > 0) reach = fmin(reach, x[m] - (G.lo[m] + (cq[m] - r) * G.cell[m]) - 1e-9 * G.cell[m]);
-                if (cq[m] + r < G.g[m] - 1) reach = fmin(reach, (G.lo[m] + (cq[m] + r + 1) * G.cell[m]) - x[m] - 1e-9 * G.cell[m]);
+                if (cq[m] - r > 0) reach = fmin(reach, x[m] - (G.lo[m] + (cq[m] - r) * G.cell[m]) - G.sliver[m]);
+                if (cq[m] + r < G.g[m] - 1) reach = fmin(reach, (G.lo[m] + (cq[m] + r + 1) * G.cell[m]) - x[m] - G.sliver[m]);
             }
             if (reach == DBL_MAX) break;                                   // the whole grid has been visited
             if (reach > 0.0 && ((count == k && worst <= reach * reach) || reach * reach > r2max)) break;
@@ -224,6 +238,57 @@ __global__ __launch_bounds__(64) void knn_query_kernel(const double* __restrict_
 
 using namespace wlsqm;
 
+// The grid's shape, stated once (host arithmetic only: no device is touched).  ~4 points per cell over the live axes: cells of side
+// h = (volume / target)^(1 / live), g = floor(extent / h) cells on an axis, at least 1 and at most the axis cap.  The extents are
+// normalised first (extent = f 2^e with f in [1/2, 1)): the product of the f and the sum of the e are the volume, so that neither the
+// volume of a tiny box underflows (h = 0: every axis at its cap, 2^30 cells in 3D) nor that of a huge one overflows (h = inf: one
+// cell, a brute-force search), and a cloud scaled by a power of two keeps its shape exactly.  With the true h the floors keep the
+// product within the target of at most 2^27 cells (an axis raised to g = 1 has a quotient below 1, which leaves the others the
+// caps' 2^20 or 2^14); the loop at the end holds the budget against the roundings as well.  An axis whose extent is below 2^-537 is
+// not live: the squares of its differences vanish, so it separates no two points, and its 1 / cell would not be finite.
+extern "C" int wlsqm_hip_grid_shape_host(int dimension, int64_t npoints, const double* lo, const double* hi, int32_t* g, double* cell) {
+    if (dimension < 1 || dimension > 3) { set_error("dimension must be 1, 2 or 3"); return WLSQM_EVALUE; }
+    if (!lo || !hi || !g || !cell) { set_error("null array"); return WLSQM_EVALUE; }
+    if (npoints < 1) { set_error("npoints must be >= 1"); return WLSQM_EVALUE; }
+    double ext[3], diag2 = 0.0;
+    for (int m = 0; m < dimension; ++m) {
+        // (an axis on which every point is +inf has lo == hi == inf: the bounds are tested, not their difference)
+        if (!(std::fabs(lo[m]) <= DBL_MAX) || !(std::fabs(hi[m]) <= DBL_MAX)) { set_error("non-finite coordinates"); return WLSQM_EVALUE; }
+        if (hi[m] < lo[m]) { set_error("the box's upper bound is below its lower bound"); return WLSQM_EVALUE; }
+        ext[m] = hi[m] - lo[m];
+        diag2 += ext[m] * ext[m];
+    }
+    // no squared distance inside the box exceeds the squared diagonal (2^-40: room for the roundings of either)
+    if (!(diag2 * (1.0 + 0x1p-40) <= DBL_MAX)) {
+        set_error("the cloud's bounding box is too large: squared distances overflow double precision");
+        return WLSQM_EVALUE;
+    }
+    double f[3] = {0, 0, 0}, prod_f = 1.0;
+    int e[3] = {0, 0, 0}, sum_e = 0, live = 0;
+    for (int m = 0; m < dimension; ++m)
+        if (ext[m] >= 0x1p-537) { f[m] = std::frexp(ext[m], &e[m]); prod_f *= f[m]; sum_e += e[m]; ++live; }
+    // volume = prod_f 2^sum_e with sum_e = live a + b, 0 <= b < live: h = (prod_f 2^b / target)^(1 / live) 2^a, and the 2^a goes to the extents
+    int a = 0, b = 0;
+    if (live) { a = sum_e / live; b = sum_e - a * live; if (b < 0) { b += live; --a; } }
+    const double target_cells = std::max(std::min((double)npoints / 4.0, 134217728.0), 1.0);
+    const double v = std::ldexp(prod_f, b) / target_cells;
+    const double h = live == 3 ? std::cbrt(v) : (live == 2 ? std::sqrt(v) : v);
+    const double cap = dimension == 3 ? 1024.0 : (dimension == 2 ? 16384.0 : 4096.0 * 4096.0);
+    long long cells = 1;
+    for (int m = 0; m < dimension; ++m) {
+        // (the 2^-50: a quotient that is a whole number, as 4 x 16 x 16 for 4096 points in a 1 : 4 : 4 box, must not lose a cell to a rounding)
+        g[m] = f[m] > 0.0 ? (int32_t)std::min(std::max(std::ldexp(f[m], e[m] - a) / h * (1.0 + 0x1p-50), 1.0), cap) : 1;
+        cells *= g[m];
+    }
+    while (cells > 134217728LL) {
+        int big = 0;
+        for (int m = 1; m < dimension; ++m) if (g[m] > g[big]) big = m;
+        cells /= g[big]; g[big] = (g[big] + 1) / 2; cells *= g[big];
+    }
+    for (int m = 0; m < dimension; ++m) cell[m] = f[m] > 0.0 ? ext[m] / g[m] : 1.0;
+    return WLSQM_OK;
+}
+
 // Uniform grid over a device-resident cloud (wlsqm_grid.hpp): bounding box, cells of ~4 points, points sorted by cell.
 int wlsqm::GridIndex::build(int dimension, int64_t npoints, const double* S, hipStream_t s) {
     int rc;
@@ -240,27 +305,17 @@ int wlsqm::GridIndex::build(int dimension, int64_t npoints, const double* S, hip
     WLSQM_HIP_CHECK(hipStreamSynchronize(s));
     G = KnnGrid{};
     G.dim = dimension;
-    double ext[3] = {0, 0, 0}, vol = 1.0;
-    int live = 0;
-    for (int m = 0; m < dimension; ++m) {
-        const double lo = value_of(h_mm[m]), hi = value_of(h_mm[3 + m]);
-        if (!(lo == lo) || !(hi == hi) || hi - lo > DBL_MAX) { set_error("non-finite coordinates"); return WLSQM_EVALUE; }
-        G.lo[m] = lo; ext[m] = hi - lo;
-        if (ext[m] > 0.0) { vol *= ext[m]; ++live; }
-    }
-    // ~4 points per cell over the non-degenerate axes, at most 2^27 cells
-    const double target_cells = std::min((double)n / 4.0, 134217728.0);
-    const double h = live ? std::pow(vol / std::max(target_cells, 1.0), 1.0 / live) : 1.0;
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    for (int m = 0; m < dimension; ++m) { lo[m] = value_of(h_mm[m]); hi[m] = value_of(h_mm[3 + m]); }
+    int32_t g[3] = {1, 1, 1};
+    if ((rc = wlsqm_hip_grid_shape_host(dimension, npoints, lo, hi, g, G.cell))) return rc;
     ncells = 1;
-    for (int m = 0; m < dimension; ++m) {
-        int g = ext[m] > 0.0 ? (int)std::min(std::max(ext[m] / h, 1.0), 4096.0 * 4096.0) : 1;
-        if (dimension == 3) g = std::min(g, 1024); else if (dimension == 2) g = std::min(g, 16384);
-        G.g[m] = std::max(g, 1);
-        G.cell[m] = ext[m] > 0.0 ? ext[m] / G.g[m] : 1.0;
-        G.inv_cell[m] = 1.0 / G.cell[m];
+    for (int m = 0; m < 3; ++m) {
+        if (m >= dimension) G.cell[m] = 1.0;
+        G.lo[m] = lo[m]; G.g[m] = g[m]; G.inv_cell[m] = 1.0 / G.cell[m];
+        G.sliver[m] = std::max(1e-9, 0x1p-48 * G.g[m]) * G.cell[m];
         ncells *= G.g[m];
     }
-    for (int m = dimension; m < 3; ++m) { G.g[m] = 1; G.cell[m] = 1.0; G.inv_cell[m] = 1.0; G.lo[m] = 0.0; }
 
     // 2. sort by cell
     DevBuf d_cell, d_cell2, d_idx, d_tmp;
@@ -289,8 +344,9 @@ static int neighbour_search(int dimension, int64_t npoints, const double* S, int
     if (nquery < 0) nquery = npoints;
     if (nquery > npoints) { set_error("nquery must be <= npoints"); return WLSQM_EVALUE; }
     if (dimension < 1 || dimension > 3) { set_error("dimension must be 1, 2 or 3"); return WLSQM_EVALUE; }
-    if (!S || !hoods) { set_error("null array"); return WLSQM_EVALUE; }
+    // (k before the arrays: a caller's hoods[npoints, 0] has no address to give)
     if (k < 1 || npoints < 2 || (int64_t)k > npoints - 1) { set_error("k must be in 1 .. npoints - 1"); return WLSQM_EVALUE; }
+    if (!S || !hoods) { set_error("null array"); return WLSQM_EVALUE; }
     if (npoints > 0x7fffffffLL) { set_error("at most 2^31 - 1 points"); return WLSQM_EVALUE; }
     const size_t lds = (size_t)k * 64 * (sizeof(double) + sizeof(int));
     if (lds > 160 * 1024) { set_error("k too large for the LDS-resident candidate lists (k <= 213)"); return WLSQM_EVALUE; }
@@ -328,20 +384,23 @@ __global__ __launch_bounds__(64) void nearest_kernel(const double* __restrict__ 
     const long long q = (long long)blockIdx.x * 64 + threadIdx.x;
     if (q >= nq) return;
     double x[DIM]; int cq[DIM];
+    bool nan = false;
 #pragma unroll
-    for (int m = 0; m < DIM; ++m) { x[m] = X[q * sx + m]; cq[m] = cell_coord(x[m], G, m); }
+    for (int m = 0; m < DIM; ++m) { x[m] = X[q * sx + m]; cq[m] = cell_coord(x[m], G, m); nan = nan || x[m] != x[m]; }
+    if (nan) { out[q] = 0x7fffffff; return; }                      // no point is nearest to a NaN: what the walk of the whole grid would find
     int rmax = 0;
 #pragma unroll
     for (int m = 0; m < DIM; ++m) rmax = max(rmax, max(cq[m], G.g[m] - 1 - cq[m]));
     double best = DBL_MAX; int best_idx = 0x7fffffff;
     for (int r = 0; r <= rmax; ++r) {
-        const int z0 = DIM > 2 ? -r : 0, z1 = DIM > 2 ? r : 0, y0 = DIM > 1 ? -r : 0, y1 = DIM > 1 ? r : 0;
+        // the shell's rows inside the grid only: a query beside a thin grid ((16384, 1) cells) walks every ring, and must not step through
+        // the 2 r rows of each that do not exist
+        const int z0 = DIM > 2 ? max(-r, -cq[2]) : 0, z1 = DIM > 2 ? min(r, G.g[2] - 1 - cq[2]) : 0;
+        const int y0 = DIM > 1 ? max(-r, -cq[1]) : 0, y1 = DIM > 1 ? min(r, G.g[1] - 1 - cq[1]) : 0;
         for (int dz = z0; dz <= z1; ++dz) {
             const int cz = DIM > 2 ? cq[2] + dz : 0;
-            if (DIM > 2 && (cz < 0 || cz >= G.g[2])) continue;
             for (int dy = y0; dy <= y1; ++dy) {
                 const int cy = DIM > 1 ? cq[1] + dy : 0;
-                if (DIM > 1 && (cy < 0 || cy >= G.g[1])) continue;
                 const bool face = (DIM > 2 && (dz == -r || dz == r)) || (DIM > 1 && (dy == -r || dy == r));
                 const int step = (face || r == 0) ? 1 : 2 * r;
                 for (int dx = -r; dx <= r; dx += step) {
@@ -365,8 +424,8 @@ __global__ __launch_bounds__(64) void nearest_kernel(const double* __restrict__ 
             double reach = DBL_MAX;
 #pragma unroll
             for (int m = 0; m < DIM; ++m) {
-                if (cq[m] - r > 0) reach = fmin(reach, x[m] - (G.lo[m] + (cq[m] - r) * G.cell[m]) - 1e-9 * G.cell[m]);
-                if (cq[m] + r < G.g[m] - 1) reach = fmin(reach, (G.lo[m] + (cq[m] + r + 1) * G.cell[m]) - x[m] - 1e-9 * G.cell[m]);
+                if (cq[m] - r > 0) reach = fmin(reach, x[m] - (G.lo[m] + (cq[m] - r) * G.cell[m]) - G.sliver[m]);
+                if (cq[m] + r < G.g[m] - 1) reach = fmin(reach, (G.lo[m] + (cq[m] + r + 1) * G.cell[m]) - x[m] - G.sliver[m]);
             }
             if (reach == DBL_MAX || (reach > 0.0 && best <= reach * reach)) break;
         }

@@ -9,18 +9,22 @@ namespace wlsqm {
 
 struct KnnGrid {
     double lo[3], inv_cell[3], cell[3];
+    double sliver[3];      // the stop rule's margin on a cell boundary (knn.hip, head comment): max(1e-9, 2^-48 g) cell
     int g[3];
     int dim;
 };
 
+// Cell number of x on axis m, clamped to the grid IN DOUBLE: a query far outside the box has a quotient beyond int's range, which the
+// conversion must never see, and a NaN compares false twice and lands in cell 0.  Monotone in x (every step is a monotone rounding).
 __device__ __forceinline__ int cell_coord(double x, const KnnGrid& G, int m) {
-    int c = (int)((x - G.lo[m]) * G.inv_cell[m]);
-    return c < 0 ? 0 : (c >= G.g[m] ? G.g[m] - 1 : c);
+    const double t = (x - G.lo[m]) * G.inv_cell[m];
+    return t >= (double)G.g[m] ? G.g[m] - 1 : (t > 0.0 ? (int)t : 0);
 }
 
 // Uniform grid over a device-resident cloud: bounding box, cells of ~4 points, points sorted by cell (knn.hip).  Cell c holds the
 // sorted positions d_start[c] .. d_start[c + 1] - 1; d_perm[pos] is the point's number and d_Ss[pos] its coordinates.  The sort
-// is stable, so the points of one cell come in ascending number.
+// is stable, so the points of one cell come in ascending number.  The shape (g, cell) is wlsqm_hip_grid_shape_host's (knn.hip), which
+// also rejects a box with a non-finite bound or whose squared diagonal overflows.
 struct GridIndex {
     KnnGrid G{};
     long long ncells = 1;

@@ -111,6 +111,9 @@ def lib():
                                         C.c_void_p]
     L.wlsqm_hip_nearest_device.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
                                            C.c_void_p]
+    if hasattr(L, "wlsqm_hip_grid_shape_host"):                      # (older builds of the library, as above)
+        L.wlsqm_hip_grid_shape_host.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.wlsqm_hip_grid_shape_host.restype = C.c_int
     L.wlsqm_hip_expert_interpolate_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
                                                        C.c_void_p]
     L.wlsqm_hip_expert_interpolate_continuous.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_int,

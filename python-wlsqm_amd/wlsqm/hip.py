@@ -657,7 +657,11 @@ def knn(S, k, stream=None, nquery=None):
     ``cKDTree(S).query(S, 1 + k)[1][:, 1:]`` (examples/expertsolver_example.py:48-66).  Exact uniform-grid search on the
     GPU; the result is the ``hoods`` argument of fit_cloud_device / ShardedCloudSolver, or of ``S[hoods]`` for the dense
     API.  1 <= k <= min(npoints - 1, 213).  Synchronises the stream.
-    With `nquery`, only the first nquery points ask and the rest are candidates only: returns (nquery, k)."""
+    With `nquery`, only the first nquery points ask and the rest are candidates only: returns (nquery, k).
+    Domain: finite coordinates (a NaN or an infinity anywhere in S raises ValueError) whose bounding box has a representable squared
+    diagonal (ValueError otherwise); squared distances must not underflow either (points closer than about 2^-511 on every axis
+    count as coincident).  Coincident points are legal.  Equal distances are ordered by index; where a tie straddles the k-th
+    place, which of its members fill the last slots is not specified."""
     import torch
     if S.dim() == 1:
         dim = 1
@@ -685,7 +689,9 @@ def ball(S, radius, max_nk, stream=None):
     """All OTHER points within `radius` of every point of the device-resident cloud S, nearest first, at most max_nk of
     them: returns (hoods, nk) = int32 device tensors (npoints, max_nk) and (npoints,).  The radius form of knn(): what
     the reference's examples/wlsqm_example.py:103-133 builds with ``cKDTree.query_ball_point`` (unused slots of a row
-    hold the point's own index, so the rows stay valid for fit_cloud_device with the returned nk)."""
+    hold the point's own index, so the rows stay valid for fit_cloud_device with the returned nk).
+    The ball is closed (squared distance <= radius * radius, both as computed in float64) and the row ascends by (distance, index);
+    radius > 0, and S in the domain of knn().  Of a ball with more than max_nk members the max_nk nearest are kept (nk == max_nk)."""
     import torch
     dim = 1 if S.dim() == 1 else int(S.shape[1])
     if S.dim() not in (1, 2) or not 1 <= dim <= 3:
@@ -703,7 +709,9 @@ def ball(S, radius, max_nk, stream=None):
 
 def nearest(S, X, stream=None):
     """Index (int64 device tensor, one per row of X) of the point of the device-resident cloud S nearest to each query
-    point X[j] (queries need not belong to the cloud; ties go to the smaller index): ``cKDTree(S).query(X)[1]`` on the GPU."""
+    point X[j] (queries need not belong to the cloud; ties go to the smaller index): ``cKDTree(S).query(X)[1]`` on the GPU.
+    S in the domain of knn().  A query with a NaN coordinate, or one so far away that its squared distances overflow, has no nearest
+    point and gets 2**31 - 1, which is no index of S (a plan evaluates to NaN there)."""
     import torch
     dim = 1 if S.dim() == 1 else int(S.shape[1])
     _check(S, "S", "float64", S.dim()); _check(X, "X", "float64", X.dim())
@@ -713,6 +721,22 @@ def nearest(S, X, stream=None):
     s, dev = _stream_and_device(S, stream)
     B.check(B.lib().wlsqm_hip_nearest_device(dim, int(S.shape[0]), _ptr(S), int(X.shape[0]), _ptr(X), dim, _ptr(out), dev, s))
     return out
+
+
+def grid_shape(dimension, npoints, lo, hi):
+    """(g, cell): the cells per axis (int32 array) and their sides (float64 array) of the uniform grid that knn, ball, nearest and the
+    continuous interpolation lay over a cloud of npoints points with the bounding box lo .. hi.  Host arithmetic only (no device is
+    touched); ValueError for a box outside the searches' domain (see knn)."""
+    import numpy as np
+    dimension = int(dimension)
+    lo = np.ascontiguousarray(np.atleast_1d(lo), dtype=np.float64)
+    hi = np.ascontiguousarray(np.atleast_1d(hi), dtype=np.float64)
+    if dimension not in (1, 2, 3) or lo.shape != (dimension,) or hi.shape != (dimension,):
+        raise ValueError("lo and hi must hold `dimension` = 1..3 numbers each")
+    g = np.ones(dimension, np.int32)
+    cell = np.ones(dimension, np.float64)
+    B.check(B.lib().wlsqm_hip_grid_shape_host(dimension, int(npoints), lo.ctypes.data, hi.ctypes.data, g.ctypes.data, cell.ctypes.data))
+    return g, cell
 
 
 # ---- interpolation plans: search once, evaluate many times (csrc/interp_plan.hip) ----
