@@ -219,6 +219,48 @@ int wlsqm_hip_fit_cloud_adjoint_device(int dimension, int order, int64_t ncases,
                                        const double* g, int64_t g_stride_case, double* grad_slots, int64_t gs_stride_case,
                                        double* grad_fi, int64_t gfi_stride_case, int device, void* stream);
 
+/* ---- the geometry adjoint of the fit (extension; csrc/fit_adjoint.hip) ----
+ * The gradient of L = g . fi_out with respect to the COORDINATES of a basic fit, which the fit is not linear in.  Per case, with
+ * d_k = xk_k - xi, c_k the scaled monomials of d_k, U / Kn / D the unknown, truly known and dropped DOFs, phi = fi_out with the entries
+ * in D replaced by 0, y_U = M_UU^-1 g_U (y = 0 outside U), s_k = c_k . y, r_k = fk_k - c_k . phi, and (d_m c)[a] the scaled monomial
+ * whose exponent on axis m is one lower (0 when that exponent is 0), for k < nk[j]:
+ *   e[k][m] = (dw_k/dd_k,m) s_k r_k + w_k ( r_k (d_m c_k . y) - s_k (d_m c_k . phi) ).
+ * Uniform weights: dw = 0.  Otherwise (alpha = 1e-4, beta = 1 - alpha), D2 = max_k d2_k, rho_k = sqrt(d2_k / D2), t_k = 1 - rho_k:
+ *   dw_k/dd_k,m = -2 beta t_k d_k,m / (rho_k D2),
+ *   E           = sum_k (beta t_k rho_k / D2) s_k r_k,
+ *   e[k*][m]   += 2 d_k*,m E          (D2 moves with the farthest neighbour k* only).
+ * Outputs: grad_xk[j, k, m] = e[k][m] for k < nk[j] and EXACT ZEROS for nk[j] <= k < max_nk; grad_xi[j, m] = -sum_k e[k][m];
+ * grad_fk[j, k] = w_k s_k (nullable: not wanted; for the systems up to 10 unknowns the bits of wlsqm_hip_fit_adjoint_device's).
+ * A case with every DOF known has zeros everywhere.  The fit is not smooth at two kinds of point, and the conventions there are:
+ *   - a neighbour ON xi (rho_k == 0): the cone of |d| at d = 0 contributes 0 (dw_k/dd_k = 0);
+ *   - a tie for the farthest neighbour: k* is the SMALLEST index that attains D2 in the kernel's own fp64 squared distances.
+ * Of `b`: the geometry as for wlsqm_hip_fit_adjoint_device, and b->fk (read) and b->fi, the output of the forward call (read, never
+ * written); b->sens and b->order are not read; b->iterative and b->do_sens must be 0 (WLSQM_EVALUE).  grad_xk has a case and a slot
+ * stride (the `dimension` coordinates of a slot contiguous), grad_xi a case stride, grad_fk a case and a slot stride; none may alias an
+ * input.  g, order_uniform, case_index / nsel, device and stream as for wlsqm_hip_fit_adjoint_device.  Nothing but one kernel launch
+ * (wlsqm_hip_last_kernel(): "geometry-adjoint-lane" or "geometry-adjoint-rows"): no allocation, no host synchronisation, no state; it
+ * can be captured into a hipGraph.  The arithmetic is always the fast kernels'.  1D orders 0-4, 2D orders 0-4, 3D orders 0-2; 3D orders
+ * 3 and 4: WLSQM_EVALUE, "fit_geometry_adjoint: unsupported (dimension, order)". */
+int wlsqm_hip_fit_geometry_adjoint_device(const wlsqm_batch* b, int device, void* stream, int order_uniform,
+                                          const double* g, int64_t g_stride_case,
+                                          double* grad_xk, int64_t gxk_stride_case, int64_t gxk_stride_k,
+                                          double* grad_xi, int64_t gxi_stride_case,
+                                          double* grad_fk, int64_t gfk_stride_case, int64_t gfk_stride_k,
+                                          const int64_t* case_index, int64_t nsel);
+
+/* The same for index-based input: the arguments of wlsqm_hip_fit_cloud_device (F is read; fi is the forward call's output, read and
+ * never written).  grad_slots[j * gs_stride_case + k * dimension + m] = dL/dS[hoods[j, k], m] contributed by slot k of case j, for every
+ * k < max_nk (zeros from nk[j] on; the padding of a hoods row is never dereferenced); grad_own[j * go_stride_case + m] = dL/dS of the
+ * case's own point (point_index[j], or j), m < dimension; grad_F_slots[j * gfs_stride_case + k] (nullable) = dL/dF[hoods[j, k]] as
+ * wlsqm_hip_fit_cloud_adjoint_device writes it.  Summing slots and own rows into dL/dS (npoints, dimension) is the caller's scatter. */
+int wlsqm_hip_fit_cloud_geometry_adjoint_device(int dimension, int order, int64_t ncases, int64_t max_nk,
+                                                const double* S, const double* F, const int32_t* hoods, int64_t hoods_stride_case,
+                                                const int32_t* point_index, const int32_t* nk, const int64_t* knowns,
+                                                const int32_t* weighting_method, const double* fi, int64_t fi_stride_case,
+                                                const double* g, int64_t g_stride_case,
+                                                double* grad_slots, int64_t gs_stride_case, double* grad_own, int64_t go_stride_case,
+                                                double* grad_F_slots, int64_t gfs_stride_case, int device, void* stream);
+
 /* ---- ExpertSolver (expert.pyx:66-781): handle-based prepare-once / solve-many ---- */
 typedef struct wlsqm_expert wlsqm_expert;
 

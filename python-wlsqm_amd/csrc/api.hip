@@ -847,6 +847,78 @@ int wlsqm_hip_fit_cloud_adjoint_device(int dimension, int order, int64_t ncases,
     return launch_fit_adjoint(dimension, order, p, q, (hipStream_t)stream);
 }
 
+// ---- the geometry adjoint of the fit (fit_adjoint.hip): one kernel launch, the fast arithmetic ----
+static int geometry_adjoint_args(GeometryAdjointArgs& q, int dim, int no, int64_t max_nk, const double* g, int64_t g_stride_case,
+                                 int64_t fi_stride_case, double* grad_xk, int64_t gxk_stride_case, int64_t gxk_stride_k, double* grad_xi,
+                                 int64_t gxi_stride_case, double* grad_fk, int64_t gfk_stride_case, int64_t gfk_stride_k) {
+    if (no < 0) { set_error("order must be 0..4"); return WLSQM_EVALUE; }
+    if (max_nk < 0) { set_error("max_nk must be >= 0"); return WLSQM_EVALUE; }
+    if (!g || !grad_xk || !grad_xi) { set_error("null array"); return WLSQM_EVALUE; }
+    if (g_stride_case < no || fi_stride_case < no) { set_error("gradient rows narrower than the number of DOFs"); return WLSQM_EVALUE; }
+    if (gxk_stride_k < dim || gxi_stride_case < dim) { set_error("coordinate gradients narrower than the dimension"); return WLSQM_EVALUE; }
+    q = GeometryAdjointArgs{g, g_stride_case, grad_xk, gxk_stride_case, gxk_stride_k, grad_xi, gxi_stride_case, grad_fk, gfk_stride_case,
+                            gfk_stride_k};
+    return WLSQM_OK;
+}
+
+int wlsqm_hip_fit_geometry_adjoint_device(const wlsqm_batch* b, int device, void* stream, int order_uniform,
+                                          const double* g, int64_t g_stride_case,
+                                          double* grad_xk, int64_t gxk_stride_case, int64_t gxk_stride_k,
+                                          double* grad_xi, int64_t gxi_stride_case,
+                                          double* grad_fk, int64_t gfk_stride_case, int64_t gfk_stride_k,
+                                          const int64_t* case_index, int64_t nsel) {
+    if (!b) { set_error("null batch"); return WLSQM_EVALUE; }
+    if (b->dimension < 1 || b->dimension > 3) { set_error("dimension must be 1, 2 or 3"); return WLSQM_EVALUE; }
+    if (b->ncases < 1) { set_error("max_cases must be >= 1"); return WLSQM_EVALUE; }
+    if (!b->xk || !b->fk || !b->nk || !b->xi || !b->fi || !b->knowns || !b->weighting_method) { set_error("null array in batch"); return WLSQM_EVALUE; }
+    if (b->iterative || b->do_sens) { set_error("fit_geometry_adjoint: the batch must not ask for refinement or sensitivities"); return WLSQM_EVALUE; }
+    GeometryAdjointArgs q;
+    int rc = geometry_adjoint_args(q, b->dimension, wlsqm_hip_number_of_dofs(b->dimension, order_uniform), b->max_nk, g, g_stride_case,
+                                   b->fi_stride_case, grad_xk, gxk_stride_case, gxk_stride_k, grad_xi, gxi_stride_case, grad_fk,
+                                   gfk_stride_case, gfk_stride_k);
+    if (rc != WLSQM_OK) return rc;
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    KParams p{};
+    p.xk = b->xk; p.sxk_j = b->xk_stride_case; p.sxk_k = b->xk_stride_k;
+    p.fk = b->fk; p.sfk_j = b->fk_stride_case; p.sfk_k = b->fk_stride_k;
+    p.nk = b->nk; p.snk = b->nk_stride;
+    p.xi = b->xi; p.sxi_j = b->xi_stride_case;
+    p.fi = b->fi; p.sfi_j = b->fi_stride_case;                      // the forward call's output: read, never written
+    p.knowns = (const long long*)b->knowns; p.sknowns = b->knowns_stride;
+    p.wm = b->weighting_method; p.swm = b->wm_stride;
+    p.ncases = b->ncases; p.max_nk = b->max_nk;
+    if (case_index) { p.case_index = (const long long*)case_index; p.ncases = nsel; }
+    return launch_fit_geometry_adjoint(b->dimension, order_uniform, p, q, (hipStream_t)stream);
+}
+
+int wlsqm_hip_fit_cloud_geometry_adjoint_device(int dimension, int order, int64_t ncases, int64_t max_nk,
+                                                const double* S, const double* F, const int32_t* hoods, int64_t hoods_stride_case,
+                                                const int32_t* point_index, const int32_t* nk, const int64_t* knowns,
+                                                const int32_t* weighting_method, const double* fi, int64_t fi_stride_case,
+                                                const double* g, int64_t g_stride_case,
+                                                double* grad_slots, int64_t gs_stride_case, double* grad_own, int64_t go_stride_case,
+                                                double* grad_F_slots, int64_t gfs_stride_case, int device, void* stream) {
+    if (dimension < 1 || dimension > 3) { set_error("dimension must be 1, 2 or 3"); return WLSQM_EVALUE; }
+    if (ncases < 1) { set_error("max_cases must be >= 1"); return WLSQM_EVALUE; }
+    if (!S || !F || !hoods || !nk || !knowns || !weighting_method || !fi) { set_error("null array"); return WLSQM_EVALUE; }
+    GeometryAdjointArgs q;
+    int rc = geometry_adjoint_args(q, dimension, wlsqm_hip_number_of_dofs(dimension, order), max_nk, g, g_stride_case, fi_stride_case,
+                                   grad_slots, gs_stride_case, dimension, grad_own, go_stride_case, grad_F_slots, gfs_stride_case, 1);
+    if (rc != WLSQM_OK) return rc;
+    if (gs_stride_case < max_nk * dimension || (grad_F_slots && gfs_stride_case < max_nk)) { set_error("slot rows narrower than max_nk"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    KParams p{};
+    p.hoods = hoods; p.shoods_j = hoods_stride_case; p.S = S; p.F = F; p.pidx = point_index;
+    p.nk = nk; p.snk = 1; p.knowns = (const long long*)knowns; p.sknowns = 1; p.wm = weighting_method; p.swm = 1;
+    p.fi = const_cast<double*>(fi); p.sfi_j = fi_stride_case;
+    p.ncases = ncases; p.max_nk = max_nk;
+    return launch_fit_geometry_adjoint(dimension, order, p, q, (hipStream_t)stream);
+}
+
 static int time_launches(int dimension, int order, const KParams& p, long long max_nk, hipStream_t s, int reps, float* ms_out) {
     hipEvent_t e0, e1;
     WLSQM_HIP_CHECK(hipEventCreate(&e0));

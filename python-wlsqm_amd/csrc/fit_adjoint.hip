@@ -296,4 +296,329 @@ int launch_fit_adjoint(int dimension, int order, const KParams& p, const Adjoint
     return WLSQM_EVALUE;
 }
 
+// ---- the geometry adjoint: gradients with respect to the coordinates ------------------------------------------
+// The fit is NOT linear in the offsets d_k = xk_k - xi.  With phi = fi_out (the entries in D replaced by 0), y as above, s_k = c_k . y,
+// r_k = fk_k - c_k . phi and (d_m c)[a] the scaled monomial whose exponent on axis m is one lower (0 when that exponent is 0: it is
+// another entry of c, Lowered below), the gradient of L = gbar . fi_out is, for k < nk,
+//   e[k][m] = (dw_k/dd_k,m) s_k r_k + w_k (r_k (d_m c_k . y) - s_k (d_m c_k . phi)),
+// dw = 0 under uniform weights, else with beta = 1 - 1e-4, D2 = max_k d2_k, rho_k = sqrt(d2_k / D2), t_k = 1 - rho_k
+//   dw_k/dd_k,m = -2 beta t_k d_k,m / (rho_k D2)     (0 where rho_k == 0: the cone of |d| at d = 0 contributes nothing),
+//   E = sum_k (beta t_k rho_k / D2) s_k r_k,   e[k*][m] += 2 d_k*,m E,   k* the SMALLEST index that attains D2 (pass 1's strict `>`:
+//   a tie for the farthest neighbour goes to the smaller index),
+// grad_xk[k][m] = e[k][m] (exact zeros for nk <= k < K), grad_xi[m] = -sum_k e[k][m], and, at no extra cost, grad_fk[k] = w_k s_k: the
+// bits of adjoint_case's for the systems up to 10 unknowns (the same statements in the same order).  A case with every DOF known has
+// zeros everywhere.  Three passes over the neighbours: D2 and k*; M, its factorisation and y (adjoint_solve); the loop above, which
+// accumulates E and the xi sum and keeps d_k* and e[k*] in registers for the fix-up of slot k*.  Two kernels call it, as for the adjoint:
+//   "geometry-adjoint-lane": one lane per case, arbitrary strides, dense or index-based rows, case_index;
+//   "geometry-adjoint-rows": the wave's run of xk in LDS at the odd pitch, grad_xk[k] overwrites neighbour k's DIM coordinates in place
+//                            and the image leaves as one contiguous run; fk is read once: through the image too where a row of
+//                            K (DIM + 1) doubles fits the LDS budget (grad_fk then leaves as a run as well), else by each lane from its
+//                            own global row.
+
+// Pass two of adjoint_case, statement for statement (that routine is left as it was, so that its kernels compile to the code they had):
+// M = C^T W C (upper triangle), the knowns masked out, the factorisation, and y (gbar on entry) overwritten with y_U = M_UU^-1 gbar_U,
+// y = 0 outside U.
+template <int DIM, int ORDER, class Rows>
+__device__ __forceinline__ void adjoint_solve(const Rows& rows, const double (&xi)[DIM], int nk, bool uniform, double inv_max,
+                                              unsigned long long known, double (&y)[ndofs(DIM, ORDER)]) {
+    constexpr int NO = ndofs(DIM, ORDER);
+    constexpr int NE = NO * (NO + 1) / 2;
+    double M[NE];
+#pragma unroll
+    for (int e = 0; e < NE; ++e) M[e] = 0.0;
+    for (int k = 0; k < nk; ++k) {
+        double d[DIM], c[NO];
+        rows.offset(k, xi, d);
+        const double d2 = monomials<DIM, ORDER>(d, c);
+        accumulate_matrix<NO>(M, c, weight(d2, inv_max, uniform));
+    }
+    // knowns: rows and columns masked to identity, their entries of the right-hand side zeroed (the values are zero: nothing moves)
+    {
+        double zero[NO];
+#pragma unroll
+        for (int a = 0; a < NO; ++a) zero[a] = 0.0;
+        eliminate_knowns<NO>(M, y, known, zero);
+    }
+    ldlt_factor<NO>(M);
+    ldlt_solve<NO>(M, y);
+}
+
+// low.idx[m][a]: the DOF whose exponent on axis m is one lower than DOF a's, -1 where that exponent is 0
+template <int DIM, int ORDER>
+struct Lowered {
+    int idx[DIM][ndofs(DIM, ORDER)];
+    constexpr Lowered() : idx{} {
+        constexpr int NO = ndofs(DIM, ORDER);
+        for (int m = 0; m < DIM; ++m)
+            for (int a = 0; a < NO; ++a) {
+                const int p = Mono<DIM>::P[a] - (m == 0), q = Mono<DIM>::Q[a] - (m == 1), r = Mono<DIM>::R[a] - (m == 2);
+                idx[m][a] = -1;
+                for (int b = 0; b < NO; ++b)
+                    if (Mono<DIM>::P[b] == p && Mono<DIM>::Q[b] == q && Mono<DIM>::R[b] == r) idx[m][a] = b;
+            }
+    }
+};
+
+// Row access of the lane form: AdjLaneRows plus the data (fk rows with strides, or F through the hoods row) and the two outputs.
+template <int DIM>
+struct GeoLaneRows {
+    const double* xr; long long sxk_k;
+    const int* hr; const double* S;                 // hr != nullptr: index-based
+    const double* fr; long long sfk_k; const double* F;
+    double* out; long long sout_k;                  // grad_xk: DIM contiguous doubles per slot
+    double* gfk; long long sgfk_k;                  // nullable
+    __device__ __forceinline__ void offset(int k, const double (&xi)[DIM], double (&d)[DIM]) const {
+        const double* q = hr ? S + (long long)hr[k] * DIM : xr + k * sxk_k;
+#pragma unroll
+        for (int m = 0; m < DIM; ++m) d[m] = q[m] - xi[m];
+    }
+    __device__ __forceinline__ double value(int k) const { return hr ? F[hr[k]] : fr[k * sfk_k]; }
+    __device__ __forceinline__ void put(int k, const double (&e)[DIM]) const {
+#pragma unroll
+        for (int m = 0; m < DIM; ++m) out[k * sout_k + m] = e[m];
+    }
+    __device__ __forceinline__ void put_fk(int k, double v) const { if (gfk) gfk[k * sgfk_k] = v; }
+};
+
+// Row access of the rows form: the case's row of the wave's LDS image, overwritten slot by slot; fk and grad_fk in global memory.
+template <int DIM>
+struct GeoLdsRows {
+    double* row;
+    const double* fr; long long sfk_k;
+    double* gfk; long long sgfk_k;                  // nullable
+    __device__ __forceinline__ void offset(int k, const double (&xi)[DIM], double (&d)[DIM]) const {
+#pragma unroll
+        for (int m = 0; m < DIM; ++m) d[m] = row[k * DIM + m] - xi[m];
+    }
+    __device__ __forceinline__ double value(int k) const { return fr[k * sfk_k]; }
+    __device__ __forceinline__ void put(int k, const double (&e)[DIM]) const {
+#pragma unroll
+        for (int m = 0; m < DIM; ++m) row[k * DIM + m] = e[m];
+    }
+    __device__ __forceinline__ void put_fk(int k, double v) const { if (gfk) gfk[k * sgfk_k] = v; }
+};
+
+// The geometry adjoint of one case.  grow: the case's gbar row; firow: the forward call's output row (read, never written); gxi: DIM doubles.
+template <int DIM, int ORDER, class Rows>
+__device__ __forceinline__ void geometry_adjoint_case(const Rows& rows, const double (&xi)[DIM], int nk, int K, bool uniform,
+                                                      unsigned long long known, unsigned long long dropped, const double* grow,
+                                                      const double* firow, double* gxi) {
+    constexpr int NO = ndofs(DIM, ORDER);
+    constexpr unsigned long long FULL = (1ull << NO) - 1ull;
+    constexpr Lowered<DIM, ORDER> low{};
+    constexpr double BETA = 1.0 - 1e-4;
+    double zeros[DIM];
+#pragma unroll
+    for (int m = 0; m < DIM; ++m) zeros[m] = 0.0;
+    if (known == FULL) {                            // nothing to solve: fi_out does not depend on the geometry
+        for (int k = 0; k < K; ++k) { rows.put(k, zeros); rows.put_fk(k, 0.0); }
+#pragma unroll
+        for (int m = 0; m < DIM; ++m) gxi[m] = 0.0;
+        return;
+    }
+    double y[NO];
+#pragma unroll
+    for (int a = 0; a < NO; ++a) y[a] = grow[a];
+    // pass 1: largest squared distance and the first neighbour that attains it; not needed for uniform weights
+    double max_d2 = 0.0;
+    int kstar = -1;
+    if (!uniform) {
+        for (int k = 0; k < nk; ++k) {
+            double d[DIM];
+            rows.offset(k, xi, d);
+            double d2 = d[0] * d[0];
+            if constexpr (DIM >= 2) d2 += d[1] * d[1];
+            if constexpr (DIM == 3) d2 += d[2] * d[2];
+            if (d2 > max_d2) { max_d2 = d2; kstar = k; }
+        }
+    }
+    const double inv_max = inverse_max(max_d2);
+    // pass 2: M = C^T W C, its factorisation and y_U = M_UU^-1 gbar_U, y = 0 outside U
+    adjoint_solve<DIM, ORDER>(rows, xi, nk, uniform, inv_max, known, y);
+    double phi[NO];
+#pragma unroll
+    for (int a = 0; a < NO; ++a) phi[a] = ((dropped >> a) & 1ull) ? 0.0 : firow[a];
+    // pass 3: e[k][m] per neighbour; E, the xi sum, and slot k*'s offset and gradient kept for the fix-up
+    double E = 0.0, sum[DIM], dstar[DIM], estar[DIM];
+#pragma unroll
+    for (int m = 0; m < DIM; ++m) { sum[m] = 0.0; dstar[m] = 0.0; estar[m] = 0.0; }
+    for (int k = 0; k < nk; ++k) {
+        double d[DIM], c[NO], e[DIM];
+        rows.offset(k, xi, d);
+        const double fkk = rows.value(k);           // before put_fk: in the rows form's image grad_fk[k] takes the place of fk[k]
+        const double d2 = monomials<DIM, ORDER>(d, c);
+        const double w = weight(d2, inv_max, uniform);
+        double s = y[0];
+#pragma unroll
+        for (int a = 1; a < NO; ++a) s = fma(c[a], y[a], s);
+        rows.put_fk(k, w * s);
+        double cp = phi[0];
+#pragma unroll
+        for (int a = 1; a < NO; ++a) cp = fma(c[a], phi[a], cp);
+        const double r = fkk - cp;
+        const double sr = s * r;
+        // the weight's own derivative: selects, not branches (uniform weights: inv_max is not finite, everything here is discarded)
+        const double rho = sqrt_unit(d2 * inv_max);
+        const double t = 1.0 - rho;
+        const double bt = (BETA * t) * inv_max;
+        const double dwc = (uniform || !(rho > 0.0)) ? 0.0 : (-2.0 * bt) * recip(rho);
+        E = uniform ? 0.0 : fma(bt * rho, sr, E);
+#pragma unroll
+        for (int m = 0; m < DIM; ++m) {
+            double dcy = 0.0, dcp = 0.0;
+#pragma unroll
+            for (int a = 1; a < NO; ++a) {
+                if (low.idx[m][a] >= 0) {
+                    dcy = fma(c[low.idx[m][a]], y[a], dcy);
+                    dcp = fma(c[low.idx[m][a]], phi[a], dcp);
+                }
+            }
+            e[m] = fma(w, fma(r, dcy, -(s * dcp)), (dwc * d[m]) * sr);
+            sum[m] += e[m];
+            if (k == kstar) { dstar[m] = d[m]; estar[m] = e[m]; }
+        }
+        rows.put(k, e);
+    }
+    for (int k = nk; k < K; ++k) { rows.put(k, zeros); rows.put_fk(k, 0.0); }     // the padding of a ragged row: exact zeros
+    if (kstar >= 0) {                               // D2 moves with its own neighbour only
+#pragma unroll
+        for (int m = 0; m < DIM; ++m) {
+            const double fix = (2.0 * dstar[m]) * E;
+            estar[m] += fix;
+            sum[m] += fix;
+        }
+        rows.put(kstar, estar);
+    }
+#pragma unroll
+    for (int m = 0; m < DIM; ++m) gxi[m] = -sum[m];
+}
+
+template <int DIM, int ORDER>
+__global__ __launch_bounds__(ADJ_BLOCK) void geometry_adjoint_lane_kernel(const KParams p, const GeometryAdjointArgs q) {
+    constexpr int NO = ndofs(DIM, ORDER);
+    const long long t = (long long)blockIdx.x * ADJ_BLOCK + threadIdx.x;
+    if (t >= live_cases(p)) return;
+    const long long j = p.case_index ? p.case_index[t] : t;
+    const int K = (int)p.max_nk;
+    const int nk = max(min(p.nk[j * p.snk], K), 0);                   // never past the end of a row
+    const bool uniform = (p.wm[j * p.swm] == WLSQM_WEIGHT_UNIFORM);
+    unsigned long long known, dropped;
+    effective_mask<NO>(p.knowns[j * p.sknowns], known, dropped);
+    double xi[DIM];
+    GeoLaneRows<DIM> rows;
+    double* out = q.gxk + j * q.sgxk_j;
+    double* gfk = q.gfk ? q.gfk + j * q.sgfk_j : nullptr;
+    if (p.hoods) {
+        const long long pj = own_point(p, j);
+#pragma unroll
+        for (int m = 0; m < DIM; ++m) xi[m] = p.S[pj * DIM + m];
+        rows = GeoLaneRows<DIM>{nullptr, 0, p.hoods + j * p.shoods_j, p.S, nullptr, 0, p.F, out, q.sgxk_k, gfk, q.sgfk_k};
+    } else {
+#pragma unroll
+        for (int m = 0; m < DIM; ++m) xi[m] = p.xi[j * p.sxi_j + m];
+        rows = GeoLaneRows<DIM>{p.xk + j * p.sxk_j, p.sxk_k, nullptr, nullptr, p.fk + j * p.sfk_j, p.sfk_k, nullptr, out, q.sgxk_k,
+                                gfk, q.sgfk_k};
+    }
+    geometry_adjoint_case<DIM, ORDER>(rows, xi, nk, K, uniform, known, dropped, q.g + j * q.sg_j, p.fi + j * p.sfi_j, q.gxi + j * q.sgxi_j);
+}
+
+// fk_image: the row of the image carries the case's K values of fk behind its K * DIM coordinates (dense rows of fk, and of grad_fk when
+// it is wanted, and room within the LDS budget: geometry_fk_image); grad_fk[k] then overwrites fk[k] and leaves as the wave's contiguous
+// run.  Otherwise each lane reads fk from, and writes grad_fk to, its own row in global memory.
+template <int DIM, int ORDER>
+__global__ __launch_bounds__(ADJ_BLOCK) void geometry_adjoint_rows_kernel(const KParams p, const GeometryAdjointArgs q, int pitch, int fk_image) {
+    constexpr int NO = ndofs(DIM, ORDER);
+    extern __shared__ double adj_lds[];
+    const long long j0 = (long long)blockIdx.x * ADJ_BLOCK;
+    const int K = (int)p.max_nk;
+    const long long left = p.ncases - j0;
+    const int ncw = left < ADJ_BLOCK ? (int)left : ADJ_BLOCK;          // the tail group has fewer than 64 cases
+    adjoint_copy_run<true>(adj_lds, pitch, 1, const_cast<double*>(p.xk) + j0 * K * DIM, ncw, K * DIM);
+    if (fk_image) adjoint_copy_run<true>(adj_lds + K * DIM, pitch, 1, const_cast<double*>(p.fk) + j0 * K, ncw, K);
+    __syncthreads();
+    if ((int)threadIdx.x < ncw) {
+        const long long j = j0 + threadIdx.x;
+        const int nk = max(min(p.nk[j * p.snk], K), 0);
+        const bool uniform = (p.wm[j * p.swm] == WLSQM_WEIGHT_UNIFORM);
+        unsigned long long known, dropped;
+        effective_mask<NO>(p.knowns[j * p.sknowns], known, dropped);
+        double xi[DIM];
+#pragma unroll
+        for (int m = 0; m < DIM; ++m) xi[m] = p.xi[j * p.sxi_j + m];
+        double* row = adj_lds + (int)threadIdx.x * pitch;
+        const GeoLdsRows<DIM> rows = fk_image
+            ? GeoLdsRows<DIM>{row, row + K * DIM, 1, q.gfk ? row + K * DIM : nullptr, 1}
+            : GeoLdsRows<DIM>{row, p.fk + j * p.sfk_j, p.sfk_k, q.gfk ? q.gfk + j * q.sgfk_j : nullptr, q.sgfk_k};
+        geometry_adjoint_case<DIM, ORDER>(rows, xi, nk, K, uniform, known, dropped, q.g + j * q.sg_j, p.fi + j * p.sfi_j,
+                                          q.gxi + j * q.sgxi_j);
+    }
+    __syncthreads();
+    adjoint_copy_run<false>(adj_lds, pitch, 1, q.gxk + j0 * K * DIM, ncw, K * DIM);
+    if (fk_image && q.gfk) adjoint_copy_run<false>(adj_lds + K * DIM, pitch, 1, q.gfk + j0 * K, ncw, K);
+}
+
+// The rows form's eligibility is the adjoint's (adjoint_rows_eligible), with grad_xk in xk's layout where the adjoint has grad_fk in fk's:
+// dense rows of xk and of grad_xk, both bases 16-byte aligned, every case of the batch in order, the image within the LDS budget.
+static bool geometry_rows_eligible(int dim, const KParams& p, const GeometryAdjointArgs& q, long long K) {
+    if (p.hoods || p.case_index || p.ncases_dev || !p.xk || K < 1) return false;
+    if (p.sxk_k != dim || p.sxk_j != K * dim || q.sgxk_k != dim || q.sgxk_j != K * dim) return false;
+    if ((reinterpret_cast<uintptr_t>(p.xk) | reinterpret_cast<uintptr_t>(q.gxk)) & 15u) return false;
+    return (size_t)adjoint_pitch(K * dim) * ADJ_BLOCK * sizeof(double) <= ADJ_LDS_BUDGET;
+}
+
+// Whether the rows form's image carries fk (and returns grad_fk) too: dense rows of fk, and of grad_fk when it is wanted, bases 16-byte
+// aligned, and a row of K * (dim + 1) doubles still within the LDS budget (2D order 2 at 32 neighbours and 1D: yes; 3D order 2 at 40 and 2D
+// order 4 at 64: no, 82 and 99 KiB).
+static bool geometry_fk_image(int dim, const KParams& p, const GeometryAdjointArgs& q, long long K) {
+    if (p.sfk_k != 1 || p.sfk_j != K || (reinterpret_cast<uintptr_t>(p.fk) & 15u)) return false;
+    if (q.gfk && (q.sgfk_k != 1 || q.sgfk_j != K || (reinterpret_cast<uintptr_t>(q.gfk) & 15u))) return false;
+    return (size_t)adjoint_pitch(K * (dim + 1)) * ADJ_BLOCK * sizeof(double) <= ADJ_LDS_BUDGET;
+}
+
+template <int DIM, int ORDER>
+static int launch_geometry(const KParams& p, const GeometryAdjointArgs& q, bool rows, hipStream_t stream) {
+    const long long blocks = (p.ncases + ADJ_BLOCK - 1) / ADJ_BLOCK;
+    if (blocks <= 0) return WLSQM_OK;
+    if (blocks > 0x7fffffffLL) { set_error("too many cases for one launch"); return WLSQM_EVALUE; }
+    if (rows) {
+        const int fk_image = geometry_fk_image(DIM, p, q, p.max_nk) ? 1 : 0;
+        const int pitch = adjoint_pitch(p.max_nk * (DIM + fk_image));
+        const size_t lds = (size_t)pitch * ADJ_BLOCK * sizeof(double);
+        if (lds > 64 * 1024) {                                       // the opt-in to more than 64 KiB of dynamic LDS, once per device
+            static bool opted[16] = {};
+            int dev = 0;
+            WLSQM_HIP_CHECK(hipGetDevice(&dev));
+            if (dev < 0 || dev >= 16) { set_error("device ordinal out of range"); return WLSQM_EVALUE; }
+            if (!opted[dev]) {
+                WLSQM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&geometry_adjoint_rows_kernel<DIM, ORDER>),
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)ADJ_LDS_BUDGET));
+                opted[dev] = true;
+            }
+        }
+        hipLaunchKernelGGL((geometry_adjoint_rows_kernel<DIM, ORDER>), dim3((unsigned)blocks), dim3(ADJ_BLOCK), lds, stream, p, q, pitch,
+                           fk_image);
+        WLSQM_HIP_CHECK(hipGetLastError());
+        note_kernel("geometry-adjoint-rows");
+        return WLSQM_OK;
+    }
+    hipLaunchKernelGGL((geometry_adjoint_lane_kernel<DIM, ORDER>), dim3((unsigned)blocks), dim3(ADJ_BLOCK), 0, stream, p, q);
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("geometry-adjoint-lane");
+    return WLSQM_OK;
+}
+
+int launch_fit_geometry_adjoint(int dimension, int order, const KParams& p, const GeometryAdjointArgs& q, hipStream_t stream) {
+    if (p.ncases <= 0) return WLSQM_OK;
+    const char form = env_first("WLSQM_HIP_ADJOINT_FORM");          // the adjoint's switch: =l the lane form, =r the rows form wherever eligible
+    // unset: the rows form wherever it is eligible too; it measured faster at every shape of profiles/geometry_adjoint_timings.json
+    const bool rows = form != 'l' && geometry_rows_eligible(dimension, p, q, p.max_nk);
+#define CASE(D, O) if (dimension == D && order == O) return launch_geometry<D, O>(p, q, rows, stream);
+    CASE(1, 0) CASE(1, 1) CASE(1, 2) CASE(1, 3) CASE(1, 4)
+    CASE(2, 0) CASE(2, 1) CASE(2, 2) CASE(2, 3) CASE(2, 4)
+    CASE(3, 0) CASE(3, 1) CASE(3, 2)
+#undef CASE
+    set_error("fit_geometry_adjoint: unsupported (dimension, order)");
+    return WLSQM_EVALUE;
+}
+
 }  // namespace wlsqm

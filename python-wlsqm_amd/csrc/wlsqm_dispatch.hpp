@@ -62,7 +62,7 @@ namespace wlsqm {
 //   WLSQM_HIP_OP_WPG                 A/B   integer           waves per workgroup of the MFMA kernel (solve_op.hip)
 //   WLSQM_HIP_OP_DEBUG               A/B   integer           experiments of that kernel: 1 no stores, 2 only the first block of fields loaded (solve_op.hip)
 //   WLSQM_HIP_SOLVE_ADJOINT          A/B   =g | =o           the adjoint of the prepared solve: the geometric route (one fit adjoint per field) everywhere / the stored operator's transpose wherever it is eligible, whatever the stack size (expert.hip)
-//   WLSQM_HIP_ADJOINT_FORM           A/B   =l | =r           the adjoint of the fit: the lane form for every batch / the rows form wherever it is eligible, whatever measured faster for the shape (fit_adjoint.hip)
+//   WLSQM_HIP_ADJOINT_FORM           A/B   =l | =r           the adjoint of the fit and its geometry adjoint: the lane form for every batch / the rows form wherever it is eligible, whatever measured faster for the shape (fit_adjoint.hip)
 
 // first character of the value; '\0' when the switch is unset or empty
 inline char env_first(const char* name) { const char* e = getenv(name); return e ? e[0] : '\0'; }
@@ -177,6 +177,18 @@ struct AdjointArgs {
 };
 // p.max_nk is the extent of the neighbour axis (set by the caller); 3D orders 3-4: WLSQM_EVALUE
 int launch_fit_adjoint(int dimension, int order, const KParams& p, const AdjointArgs& q, hipStream_t stream);
+
+// The geometry adjoint of the fit (fit_adjoint.hip): beside the geometry in KParams it READS the data (fk, or F through
+// hoods) and the forward call's output p.fi (never written).  g as above; gxk[j * sgxk_j + k * sgxk_k + m] receives dL/dxk for every
+// k < p.max_nk (zeros from nk[j] on), gxi[j * sgxi_j + m] dL/dxi, gfk (nullable: not wanted) dL/dfk as AdjointArgs::gfk.
+struct GeometryAdjointArgs {
+    const double* g;   long long sg_j;
+    double* gxk;       long long sgxk_j, sgxk_k;
+    double* gxi;       long long sgxi_j;
+    double* gfk;       long long sgfk_j, sgfk_k;
+};
+// p.max_nk is the extent of the neighbour axis (set by the caller); 3D orders 3-4: WLSQM_EVALUE
+int launch_fit_geometry_adjoint(int dimension, int order, const KParams& p, const GeometryAdjointArgs& q, hipStream_t stream);
 
 // fit_tile.hip: the tile path's eligibility, for the families that share it
 bool tile_dense_eligible(int dimension, const KParams& p, long long max_nk);                  // dense contiguous input the tile kernels can take

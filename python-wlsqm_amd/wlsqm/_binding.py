@@ -103,6 +103,16 @@ def lib():
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                      C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     L.wlsqm_hip_fit_cloud_adjoint_device.restype = C.c_int
+    # the geometry adjoint of the fit (wlsqm.hip.fit_many_geometry_adjoint_device, fit_cloud_geometry_adjoint_device)
+    L.wlsqm_hip_fit_geometry_adjoint_device.argtypes = [C.POINTER(Batch), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                                        C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                                        C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
+    L.wlsqm_hip_fit_geometry_adjoint_device.restype = C.c_int
+    L.wlsqm_hip_fit_cloud_geometry_adjoint_device.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                              C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                              C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                              C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+    L.wlsqm_hip_fit_cloud_geometry_adjoint_device.restype = C.c_int
     L.wlsqm_hip_expert_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.wlsqm_hip_knn_device.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]

@@ -13,7 +13,8 @@ from . import _binding as B
 import contextlib
 
 __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_cloud_device", "device_count", "knn", "ball", "nearest",
-           "fit_many_adjoint_device", "fit_cloud_adjoint_device", "differentiable_fit_many", "differentiable_fit_cloud",
+           "fit_many_adjoint_device", "fit_cloud_adjoint_device", "fit_many_geometry_adjoint_device",
+           "fit_cloud_geometry_adjoint_device", "differentiable_fit_many", "differentiable_fit_cloud",
            "differentiable_solve", "differentiable_solve_many",
            "InterpolationPlan", "differentiable_evaluate",
            "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
@@ -485,6 +486,141 @@ def fit_cloud_adjoint_device(dimension, order, S, hoods, nk, knowns, weighting_m
     return grad_F, grad_fi
 
 
+# ---- the geometry adjoint of the fit: gradients with respect to the coordinates (csrc/fit_adjoint.hip) ----
+
+def _coordinate_rows(t, name, like, nrows, K, dimension):
+    """grad_xk / grad_xi / grad_S: a float64 device tensor of the dimensions of `like` (xk, xi or S) that covers nrows rows, K neighbour
+    slots (None: no such axis) and `dimension` contiguous coordinates."""
+    _check(t, name, "float64", like.dim())
+    if t.shape[0] < nrows:
+        raise ValueError(_FEW_ROWS % (name, t.shape[0], nrows))
+    if K is not None and t.shape[1] < K:
+        raise ValueError("%s has %d neighbour slots per case, fk has %d" % (name, t.shape[1], K))
+    if dimension > 1 and (t.stride(-1) != 1 or t.shape[-1] < dimension):
+        raise ValueError("%s must have %d contiguous coordinates on the last axis" % (name, dimension))
+
+
+def fit_many_geometry_adjoint_device(dimension, order, xk, fk, nk, xi, fi_out, knowns, weighting_method, g, grad_xk=None, grad_xi=None,
+                                     grad_fk=False, case_index=None, stream=None):
+    """The vector-Jacobian product of fit_many_device (basic fit, integer `order`) with respect to the COORDINATES: given
+    g (n, >= no) = dL/dfi_out, the arguments of the forward call and fi_out, its output (read, never written), returns
+    (grad_xk, grad_xi, grad_fk) = (dL/dxk with xk's shape over the K = fk.shape[1] slots, dL/dxi with xi's shape, dL/dfk (n, K) or None).
+
+    Per case, with d_k = xk_k - xi, c_k the scaled monomials of d_k, phi = fi_out (0 for a DOF dropped by stray high mask bits),
+    y_U = M_UU^-1 g_U over the unknowns (0 elsewhere), s_k = c_k . y, r_k = fk_k - c_k . phi and (d_m c) the monomials with the exponent
+    on axis m lowered by one:  e[k][m] = (dw_k/dd_k,m) s_k r_k + w_k (r_k (d_m c_k . y) - s_k (d_m c_k . phi));  uniform weights have
+    dw = 0, the others dw_k/dd_k,m = -2 beta t_k d_k,m / (rho_k D2) and e[k*][m] += 2 d_k*,m sum_k (beta t_k rho_k / D2) s_k r_k for the
+    farthest neighbour k* (beta = 1 - 1e-4, D2 = max d2, rho = sqrt(d2 / D2), t = 1 - rho).  grad_xk[j, k] = e[k] for k < nk[j] and
+    exactly 0 for nk[j] <= k; grad_xi[j] = -sum_k e[k]; a case with every DOF known has zeros everywhere.  The fit is not smooth at two
+    kinds of point; the conventions: a neighbour ON xi contributes nothing through its weight (the cone of |d| at d = 0 counts as 0),
+    and a tie for the farthest neighbour goes to the SMALLEST index (in the kernel's own fp64 squared distances).
+
+    grad_fk: False (not wanted: None is returned), None / True (allocated) or a tensor (n, >= K): dL/dfk = w_k s_k from the same pass,
+    for the systems up to 10 unknowns the bits of fit_many_adjoint_device's.  dL/dfi_in stays with fit_many_adjoint_device.  The
+    outputs are allocated when not given (with `case_index`: zero-filled, the kernel writes the selected rows only) and must not alias an
+    input.  One kernel launch on `stream` (default: torch's current stream), no allocation when the outputs are given, no
+    synchronisation: it can be captured.  The arithmetic is always the fast kernels'; hand it the fi_out of the forward call whatever
+    mode that ran in.  3D orders 3 and 4 are not covered (ValueError)."""
+    import torch
+    _adjoint_order(dimension, order)
+    no = _ndofs(dimension, order)
+    b = _batch(dimension, order, xk, fk, nk, xi, fi_out, knowns, weighting_method, None, False, 0, nk)
+    ncases, K = b.ncases, int(fk.shape[1])
+    _double_rows(g, "g", ncases, no)
+    new = torch.zeros if case_index is not None else torch.empty
+    if grad_xk is None:
+        grad_xk = new((ncases, K) + tuple(xk.shape[2:]), dtype=torch.float64, device=g.device)
+    _coordinate_rows(grad_xk, "grad_xk", xk, ncases, K, dimension)
+    if grad_xi is None:
+        grad_xi = new((ncases,) + tuple(xi.shape[1:]), dtype=torch.float64, device=g.device)
+    _coordinate_rows(grad_xi, "grad_xi", xi, ncases, None, dimension)
+    if grad_fk is False:
+        grad_fk = None
+    elif grad_fk is None or grad_fk is True:
+        grad_fk = new((ncases, K), dtype=torch.float64, device=g.device)
+    if grad_fk is not None:
+        _check(grad_fk, "grad_fk", "float64", 2)
+        _rows(ncases, grad_fk=grad_fk)
+        if grad_fk.shape[1] < K:
+            raise ValueError("grad_fk has %d neighbour slots per case, fk has %d" % (grad_fk.shape[1], K))
+    _same_device(g, xk, fk, nk, xi, fi_out, knowns, weighting_method, grad_xk, grad_xi, grad_fk, case_index)
+    s, dev = _stream_and_device(g, stream)
+    ci, nsel = _case_index(case_index)
+    gfk_strides = (int(grad_fk.stride(0)), int(grad_fk.stride(1))) if grad_fk is not None else (0, 0)
+    B.check(B.lib().wlsqm_hip_fit_geometry_adjoint_device(C.byref(b), dev, s, int(order), _ptr(g), int(g.stride(0)),
+                                                          _ptr(grad_xk), int(grad_xk.stride(0)), int(grad_xk.stride(1)),
+                                                          _ptr(grad_xi), int(grad_xi.stride(0)),
+                                                          _ptr(grad_fk), gfk_strides[0], gfk_strides[1], ci, nsel))
+    return grad_xk, grad_xi, grad_fk
+
+
+def fit_cloud_geometry_adjoint_device(dimension, order, S, F, hoods, fi_out, nk, knowns, weighting_method, g, point_index=None,
+                                      grad_S=None, grad_F=False, stream=None, slots=None, own=None, slots_F=None):
+    """The vector-Jacobian product of fit_cloud_device with respect to the point table S: given g (ncases, >= no) = dL/dfi_out, the
+    arguments of the forward call and fi_out, its output, returns (grad_S, grad_F) = (dL/dS with S's shape, dL/dF (npoints,) or None).
+    The formula and the conventions at the two non-smooth points are fit_many_geometry_adjoint_device's.  The kernel runs index-based
+    and writes per case one gradient per neighbour slot, (ncases, K, dim), exact zeros in the padding of a ragged row, and the gradient
+    of the case's own point, (ncases, dim); two ``index_add_`` on the kernel's stream then sum them into grad_S: the slots go to
+    `hoods` (whose padding may hold anything: it is pointed at point 0, where it adds exact zeros), the own-point rows to `point_index`
+    (default: point j).  grad_S (overwritten) is allocated when not given.  grad_F: False (not wanted), None / True (allocated) or a
+    tensor (npoints,): dL/dF from the same pass and one more index_add_.  `slots` (ncases, K * dim), `own` (ncases, dim) and `slots_F`
+    (ncases, K): float64 device tensors that receive what the kernel writes (allocated otherwise).  Asynchronous on `stream`."""
+    import torch
+    _adjoint_order(dimension, order)
+    no = _ndofs(dimension, order)
+    a = _cloud_args(dimension, order, S, F, hoods, fi_out, nk, knowns, weighting_method, point_index)
+    ncases, K, npoints = a[2], a[3], int(S.shape[0])
+    _double_rows(g, "g", ncases, no)
+    z = lambda *shape: torch.empty(shape, dtype=torch.float64, device=g.device)
+    if slots is None:
+        slots = z(ncases, K * dimension)
+    _double_rows(slots, "slots", ncases, K * dimension,
+                 says="slots must be at least (ncases, %d) with a contiguous last axis; got %s" % (K * dimension, tuple(slots.shape)))
+    if own is None:
+        own = z(ncases, dimension)
+    _double_rows(own, "own", ncases, dimension,
+                 says="own must be at least (ncases, %d) with a contiguous last axis; got %s" % (dimension, tuple(own.shape)))
+    if grad_S is None:
+        grad_S = torch.zeros(tuple(S.shape), dtype=torch.float64, device=g.device)
+    else:
+        _check(grad_S, "grad_S", "float64", S.dim())
+        if tuple(grad_S.shape) != tuple(S.shape) or not grad_S.is_contiguous():
+            raise ValueError("grad_S must be contiguous with the shape of S, %s; got %s" % (tuple(S.shape), tuple(grad_S.shape)))
+    if grad_F is False:
+        grad_F = None
+    elif grad_F is None or grad_F is True:
+        grad_F = torch.zeros((npoints,), dtype=torch.float64, device=g.device)
+    if grad_F is not None:
+        _check(grad_F, "grad_F", "float64", 1)
+        if grad_F.shape[0] < npoints:
+            raise ValueError("grad_F has fewer entries than S has points")
+        if slots_F is None:
+            slots_F = z(ncases, K)
+        _double_rows(slots_F, "slots_F", ncases, K,
+                     says="slots_F must be at least (ncases, %d) with a contiguous last axis; got %s" % (K, tuple(slots_F.shape)))
+    else:
+        slots_F = None
+    _same_device(g, S, F, hoods, nk, fi_out, knowns, weighting_method, point_index, slots, own, grad_S, grad_F, slots_F)
+    s, dev = _stream_and_device(g, stream)
+    B.check(B.lib().wlsqm_hip_fit_cloud_geometry_adjoint_device(*a, _ptr(g), int(g.stride(0)), _ptr(slots), int(slots.stride(0)),
+                                                                _ptr(own), int(own.stride(0)), _ptr(slots_F),
+                                                                int(slots_F.stride(0)) if slots_F is not None else 0, dev, s))
+    # the scatter: torch ops, on the stream of the kernel
+    ext = torch.cuda.ExternalStream(int(stream), device=g.device) if stream else None
+    with (torch.cuda.stream(ext) if ext is not None else contextlib.nullcontext()):
+        live = torch.arange(K, device=g.device)[None, :] < nk[:ncases, None]
+        idx = torch.where(live, hoods[:ncases].long(), torch.zeros((), dtype=torch.int64, device=g.device)).reshape(-1)
+        pts = point_index[:ncases].long() if point_index is not None else torch.arange(ncases, device=g.device)
+        flat = grad_S.view(npoints, dimension)
+        flat.zero_()
+        flat.index_add_(0, idx, slots[:ncases, :K * dimension].reshape(ncases * K, dimension))
+        flat.index_add_(0, pts, own[:ncases, :dimension])
+        if grad_F is not None:
+            grad_F.zero_()
+            grad_F.index_add_(0, idx, slots_F[:ncases, :K].reshape(-1))
+    return grad_S, grad_F
+
+
 # ---- autograd: gradients through the fits, the prepared solver (ExpertSolver.solve_adjoint_device; csrc/solve_op.hip, DESIGN.md
 # section 13) and the evaluation of a plan (InterpolationPlan.evaluate_adjoint; DESIGN.md section 14) ----
 
@@ -492,8 +628,8 @@ _AUTOGRAD = None
 
 
 def _autograd():
-    """The torch.autograd.Function classes behind the differentiable_* functions, as a namespace with FitMany, FitCloud, Solve and
-    Evaluate (made at first use: the module does not import torch).  Every forward takes its tensor inputs first."""
+    """The torch.autograd.Function classes behind the differentiable_* functions, as a namespace with FitMany, FitCloud, Solve,
+    Evaluate, FitManyGeometry and FitCloudGeometry (made at first use: the module does not import torch).  Every forward takes its tensor inputs first."""
     global _AUTOGRAD
     if _AUTOGRAD is not None:
         return _AUTOGRAD
@@ -600,7 +736,77 @@ def _autograd():
                 return (plan.evaluate_adjoint(g, diff, grad_fi=gfi, stream=stream),)
             return gradients(ctx, gout, 1, adjoint)
 
-    _AUTOGRAD = types.SimpleNamespace(FitMany=FitMany, FitCloud=FitCloud, Solve=Solve, Evaluate=Evaluate)
+    class FitManyGeometry(torch.autograd.Function):
+        """FitMany with the coordinates among the differentiable inputs: saves fk and the output for the geometry adjoint."""
+        @staticmethod
+        def forward(ctx, xk, xi, fk, fi, dimension, order, nk, knowns, weighting_method, strict, stream):
+            out = fi.detach().clone()
+            fit_many_device(dimension, order, xk.detach(), fk.detach(), nk, xi.detach(), out, knowns, weighting_method, strict=strict,
+                            stream=stream)
+            ctx.save_for_backward(xk, xi, fk, out)
+            ctx.geometry = (dimension, order, nk, knowns, weighting_method, stream)
+            return out
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gout):
+            def adjoint(g, need_xk, need_xi, need_fk, need_fi):
+                dimension, order, nk, knowns, weighting_method, stream = ctx.geometry
+                xk, xi, fk, out = ctx.saved_tensors
+                ncases, K, no = int(nk.shape[0]), int(fk.shape[1]), _ndofs(dimension, order)
+                gxk = gxi = gfk = gfi = None
+                if need_xk or need_xi:
+                    # the geometry kernel; dL/dfk, when wanted, is its fused output
+                    gxk = buffer(tuple(xk.shape), g, xk.shape[0] == ncases and xk.shape[1] == K and (xk.dim() == 2 or xk.shape[2] == dimension))
+                    gxi = buffer(tuple(xi.shape), g, xi.shape[0] == ncases and (xi.dim() == 1 or xi.shape[1] == dimension))
+                    gfk = buffer(tuple(fk.shape), g, fk.shape[0] == ncases) if need_fk else False
+                    _, _, gfk = fit_many_geometry_adjoint_device(dimension, order, xk, fk, nk, xi, out, knowns, weighting_method, g,
+                                                                 grad_xk=gxk, grad_xi=gxi, grad_fk=gfk, stream=stream)
+                    need_fk = False
+                if need_fk or need_fi:
+                    # the existing adjoint: only when fi wants a gradient, or fk alone does
+                    scratch = buffer(tuple(fk.shape), g, fk.shape[0] == ncases)
+                    got, gfi = fit_many_adjoint_device(dimension, order, xk[:, :K], nk, xi, knowns, weighting_method, g, grad_fk=scratch,
+                                                       grad_fi=grad_fi_start(g, need_fi, g.shape[0] == ncases and g.shape[1] == no),
+                                                       stream=stream)
+                    gfk = got if need_fk else gfk
+                return gxk, gxi, gfk, gfi
+            return gradients(ctx, gout, 4, adjoint)
+
+    class FitCloudGeometry(torch.autograd.Function):
+        """FitCloud with the point table among the differentiable inputs."""
+        @staticmethod
+        def forward(ctx, S, F, fi, dimension, order, hoods, nk, knowns, weighting_method, point_index, strict, stream):
+            out = fi.detach().clone()
+            fit_cloud_device(dimension, order, S.detach(), F.detach(), hoods, out, nk, knowns, weighting_method, point_index=point_index,
+                             strict=strict, stream=stream)
+            ctx.save_for_backward(S, F, out)
+            ctx.geometry = (dimension, order, hoods, nk, knowns, weighting_method, point_index, stream)
+            return out
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gout):
+            def adjoint(g, need_S, need_F, need_fi):
+                dimension, order, hoods, nk, knowns, weighting_method, point_index, stream = ctx.geometry
+                S, F, out = ctx.saved_tensors
+                gS = gF = gfi = None
+                if need_S:
+                    gS, gF = fit_cloud_geometry_adjoint_device(dimension, order, S, F, hoods, out, nk, knowns, weighting_method, g,
+                                                               point_index=point_index, grad_F=buffer(tuple(F.shape), g, True) if need_F else False,
+                                                               stream=stream)
+                    need_F = False
+                if need_F or need_fi:
+                    covered = g.shape[0] == int(hoods.shape[0]) and g.shape[1] == _ndofs(dimension, order)
+                    got, gfi = fit_cloud_adjoint_device(dimension, order, S, hoods, nk, knowns, weighting_method, g, point_index=point_index,
+                                                        grad_F=buffer(tuple(F.shape), g, True), grad_fi=grad_fi_start(g, need_fi, covered),
+                                                        stream=stream)
+                    gF = got if need_F else gF
+                return gS, gF, gfi
+            return gradients(ctx, gout, 3, adjoint)
+
+    _AUTOGRAD = types.SimpleNamespace(FitMany=FitMany, FitCloud=FitCloud, Solve=Solve, Evaluate=Evaluate, FitManyGeometry=FitManyGeometry,
+                                      FitCloudGeometry=FitCloudGeometry)
     return _AUTOGRAD
 
 
@@ -611,21 +817,34 @@ def _no_geometry_grad(*geometry):
             raise ValueError("the geometry is not differentiable")
 
 
-def differentiable_fit_many(dimension, order, xk, fk, nk, xi, fi, knowns, weighting_method, strict=None, stream=None):
+def differentiable_fit_many(dimension, order, xk, fk, nk, xi, fi, knowns, weighting_method, strict=None, stream=None, geometry=False):
     """fit_many_device as a differentiable function of fk and fi: returns fi_out, a NEW tensor (fi is cloned, the fit runs in place on
     the clone), through which autograd reaches fk and fi (the basic fit, integer `order`; refinement is not offered: its stop test
     is data-dependent).  The backward pass is fit_many_adjoint_device: one kernel, computed only for the inputs that require a gradient;
     it always runs the fast arithmetic, whatever `strict` the forward used.  The geometry (xk, xi) is not differentiable:
-    ValueError when it requires a gradient.  Once differentiable."""
+    ValueError when it requires a gradient.  Once differentiable.
+
+    geometry=True: a differentiable function of the coordinates xk and xi as well.  The backward pass runs
+    fit_many_geometry_adjoint_device for xk and xi (dL/dfk, when wanted too, is its fused output) and fit_many_adjoint_device only
+    when fi wants a gradient (or fk alone does); nothing is launched for inputs that need none.  The conventions at the fit's two
+    non-smooth points (a neighbour on xi, a tie for the farthest neighbour) are fit_many_geometry_adjoint_device's.  Once differentiable."""
     _adjoint_order(dimension, order)
+    if geometry:
+        return _autograd().FitManyGeometry.apply(xk, xi, fk, fi, dimension, int(order), nk, knowns, weighting_method, strict, stream)
     _no_geometry_grad(xk, xi)
     return _autograd().FitMany.apply(fk, fi, dimension, int(order), xk, nk, xi, knowns, weighting_method, strict, stream)
 
 
-def differentiable_fit_cloud(dimension, order, S, F, hoods, fi, nk, knowns, weighting_method, point_index=None, strict=None, stream=None):
+def differentiable_fit_cloud(dimension, order, S, F, hoods, fi, nk, knowns, weighting_method, point_index=None, strict=None, stream=None,
+                             geometry=False):
     """fit_cloud_device as a differentiable function of the field F (npoints,) and of fi: returns fi_out, a new tensor.  The backward
-    pass is fit_cloud_adjoint_device (index-based kernel + one index_add_ into dL/dF).  S is not differentiable (ValueError)."""
+    pass is fit_cloud_adjoint_device (index-based kernel + one index_add_ into dL/dF).  S is not differentiable (ValueError).
+    geometry=True: a differentiable function of the point table S as well, through fit_cloud_geometry_adjoint_device (dL/dF, when wanted
+    too, from the same kernel; fit_cloud_adjoint_device only when fi wants a gradient or F alone does)."""
     _adjoint_order(dimension, order)
+    if geometry:
+        return _autograd().FitCloudGeometry.apply(S, F, fi, dimension, int(order), hoods, nk, knowns, weighting_method, point_index, strict,
+                                                  stream)
     _no_geometry_grad(S)
     return _autograd().FitCloud.apply(F, fi, dimension, int(order), S, hoods, nk, knowns, weighting_method, point_index, strict, stream)
 
