@@ -513,6 +513,32 @@ int wlsqm_hip_sytrs_batched_host(int n, int64_t count, int lhs_stride, const dou
 int wlsqm_hip_sysv_batched_host(int n, int64_t count, double* A, int32_t* ipiv, int32_t* info, double* b, int device);
 int wlsqm_hip_symmetrize_batched_host(int n, int64_t count, double* A, int device);
 
+/* ---- stencil operators (extension; csrc/stencil.hip) ----
+ * A sparse matrix A of nrows x ncols in sliced ELLPACK with one slice per wavefront ("SELL-64"): an entry is a (column, value) pair,
+ * rows are grouped in slices of 64 consecutive rows, nslices = ceil(nrows / 64).
+ *   len   (nrows,)       int32    live entries of each row
+ *   width (nslices,)     int32    max(len) over the slice's rows; 0 is allowed
+ *   soff  (nslices + 1,) int64    entry offset of each slice; soff[s + 1] - soff[s] = 64 * width[s]
+ *   col   (total,)       int32    columns, total = soff[nslices]
+ *   val   (nop, total)   float64  one value plane per operator at val_stride_op (>= total); all planes share col
+ * Entry e of row i sits at soff[i / 64] + 64 * e + i % 64, so a wave reads 256 contiguous bytes of col and 512 of each val plane per
+ * step.  An entry with e >= len[i] is padding: neither its column nor its value is used, and X is never dereferenced for it, whatever
+ * the arrays hold there (NaN and inf included).  The caller guarantees len[i] <= width[i / 64] (a longer row is cut at the width) and
+ * 0 <= col < ncols for every live entry.
+ *
+ * wlsqm_hip_sell_apply_device:  Y[r, o, i] = alpha * sum_{e < len[i]} val[o][.] * X[r, col[.]] + beta * Y[r, o, i]  for nop >= 1
+ * operators and R >= 1 stacked vectors; X[r, c] is at X[r * x_stride_field + c * x_stride_point], Y[r, o, i] at
+ * Y[r * y_stride_field + o * y_stride_op + i * y_stride_row] (strides in elements).  The sum runs in entry order with fused
+ * multiply-adds, so its bits are a function of the structure and the inputs; beta == 0 does not read Y.  Y must not overlap X.
+ * One kernel launch on `stream`: no allocation, no synchronisation, no state; nrows == 0 launches nothing.  The transposed product is
+ * the same call on the transposed matrix stored in the same format.  WLSQM_EVALUE for nop < 1, R < 1, nrows > 64 * nslices or a null
+ * array. */
+int wlsqm_hip_sell_apply_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                const int32_t* col, const double* val, int64_t val_stride_op, int nop,
+                                int64_t R, const double* X, int64_t x_stride_field, int64_t x_stride_point,
+                                double* Y, int64_t y_stride_field, int64_t y_stride_op, int64_t y_stride_row,
+                                double alpha, double beta, int device, void* stream);
+
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ---- */
 /* Runs `reps` back-to-back launches of the fit kernel for batch `b` (device-resident, uniform
  * order) on `stream`, bracketed by HIP events on that stream; returns the mean kernel time in

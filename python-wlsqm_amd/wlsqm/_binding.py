@@ -174,6 +174,12 @@ def lib():
                                                                 C.c_int]
         for name in ("prepare_adjoint", "adjoint_info", "export_transposed", "eval_adjoint_device"):
             getattr(L, "wlsqm_hip_interp_plan_" + name).restype = C.c_int
+    # stencil operators (wlsqm.hip.StencilOperator): the SELL-64 product
+    if hasattr(L, "wlsqm_hip_sell_apply_device"):                    # (older builds of the library, as above)
+        L.wlsqm_hip_sell_apply_device.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                                  C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int, C.c_void_p]
+        L.wlsqm_hip_sell_apply_device.restype = C.c_int
     # batched dense solves (wlsqm.utils.lapackdrivers, wlsqm.hip.*_batched)
     for op in ("getrf", "gesv", "sytrf", "sysv"):
         solve = op in ("gesv", "sysv")

@@ -17,6 +17,7 @@ __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_c
            "fit_cloud_geometry_adjoint_device", "differentiable_fit_many", "differentiable_fit_cloud",
            "differentiable_solve", "differentiable_solve_many",
            "InterpolationPlan", "differentiable_evaluate",
+           "StencilOperator", "stencil_rows", "differentiable_stencil_apply",
            "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
            "getrf_batched", "getrs_batched", "gesv_batched", "sytrf_batched", "sytrs_batched", "sysv_batched", "symmetrize_batched"]
 
@@ -126,21 +127,21 @@ def _rows(n, **arrays):
             raise ValueError(_FEW_ROWS % (name, t.shape[0], n))
 
 
-def _double_rows(t, name, nrows, ncols, of=None, says=None):
+def _double_rows(t, name, nrows, ncols, of=None, says=None, lead=0):
     """fi, g, grad_fi, slots: a float64 device tensor (>= nrows, >= ncols) with a contiguous last axis.  `of`: the (dimension, order)
     that ncols is the number of DOFs of, for the callers whose message names them; `says` is a caller's own sentence for a wrong
-    layout or extent, raised in place of the three below."""
-    _check(t, name, "float64", 2)
+    layout or extent, raised in place of the three below; `lead`: the number of axes in front of the rows (a stack of such tensors)."""
+    _check(t, name, "float64", 2 + lead)
     if says is not None:
-        if t.shape[0] < nrows or t.shape[1] < ncols or t.stride(1) != 1:
+        if t.shape[lead] < nrows or t.shape[lead + 1] < ncols or t.stride(lead + 1) != 1:
             raise ValueError(says)
         return
-    if t.stride(1) != 1:
+    if t.stride(lead + 1) != 1:
         raise ValueError("Buffer and memoryview are not contiguous in the same dimension. (argument %s)" % name)
-    if t.shape[0] < nrows:
-        raise ValueError(_FEW_ROWS % (name, t.shape[0], nrows))
-    if t.shape[1] < ncols:
-        raise ValueError("%s has %d columns, need at least number_of_dofs%s = %d" % (name, t.shape[1], "(%d, %d)" % of if of else "", ncols))
+    if t.shape[lead] < nrows:
+        raise ValueError(_FEW_ROWS % (name, t.shape[lead], nrows))
+    if t.shape[lead + 1] < ncols:
+        raise ValueError("%s has %d columns, need at least number_of_dofs%s = %d" % (name, t.shape[lead + 1], "(%d, %d)" % of if of else "", ncols))
 
 
 def _dense_geometry(dimension, xk, nk, xi, knowns, weighting_method):
@@ -805,8 +806,29 @@ def _autograd():
                 return gS, gF, gfi
             return gradients(ctx, gout, 3, adjoint)
 
+    class StencilApply(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, F, known, op, stream):
+            ctx.call = (op, stream, tuple(F.shape), tuple(known.shape) if known is not None else None)
+            return op.apply(F.detach(), known=known.detach() if known is not None else None, stream=stream)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gout):
+            def adjoint(g, need_F, need_known):
+                op, stream, F_shape, known_shape = ctx.call
+                gF = gknown = None
+                if need_F:
+                    # entries of F beyond the operator's points are never read by the forward: zeros
+                    gF = buffer(F_shape, g, F_shape[-1] == op.npoints)
+                    op.apply_transpose(g, out=gF[..., :op.npoints], stream=stream)
+                if need_known:
+                    gknown = op._known_adjoint(g, known_shape, stream)
+                return gF, gknown
+            return gradients(ctx, gout, 2, adjoint)
+
     _AUTOGRAD = types.SimpleNamespace(FitMany=FitMany, FitCloud=FitCloud, Solve=Solve, Evaluate=Evaluate, FitManyGeometry=FitManyGeometry,
-                                      FitCloudGeometry=FitCloudGeometry)
+                                      FitCloudGeometry=FitCloudGeometry, StencilApply=StencilApply)
     return _AUTOGRAD
 
 
@@ -1273,6 +1295,427 @@ def differentiable_evaluate(plan, fi, diff=0, stream=None):
     _no_geometry_grad(plan)
     diffs, single = _diff_list(diff)
     return _autograd().Evaluate.apply(fi, plan, diffs[0] if single else diffs, stream)
+
+
+# ---- stencil operators: differential operators of the fit as sparse matrices (csrc/stencil.hip) ----
+
+def stencil_rows(dimension, order, *what, device=None):
+    """The rows (lambda) of named operators for StencilOperator, in the DOF order of wlsqm.fitter.defs: a float64 tensor (nop, no) on
+    `device` (None: the host; move it to the cloud's device).  Each `what` is 'value' (the fitted function value), 'gradient' (one row
+    per axis), 'laplacian' (the sum of the pure second derivatives) or a DOF index such as wlsqm.i2_XY.  ValueError for a `what` that
+    needs a higher order than `order`."""
+    import torch
+    from .fitter import defs
+    dimension = int(dimension)
+    no = _ndofs(dimension, order)
+    axes = "XYZ"[:dimension]
+
+    def row(*dofs):
+        r = [0.0] * no
+        for a in dofs:
+            if isinstance(a, str):
+                a = getattr(defs, "i%d_%s" % (dimension, a))
+            if not 0 <= a < _NDOF[dimension][4]:
+                raise ValueError("a %dD fit has the DOFs 0 .. %d; got %d" % (dimension, _NDOF[dimension][4] - 1, a))
+            if a >= no:
+                need = min(o for o in range(5) if _NDOF[dimension][o] > a)
+                raise ValueError("DOF %d needs a fit of order %d or more; got order %d" % (a, need, int(order)))
+            r[a] = 1.0
+        return r
+
+    rows = []
+    for w in what:
+        if w == "value":
+            rows.append(row("F"))
+        elif w == "gradient":
+            rows.extend(row(a) for a in axes)
+        elif w == "laplacian":
+            rows.append(row(*(a + "2" for a in axes)))
+        elif isinstance(w, int) and not isinstance(w, bool):
+            rows.append(row(w))
+        else:
+            raise ValueError("what must be 'value', 'gradient', 'laplacian' or a DOF index; got %r" % (w,))
+    if not rows:
+        raise ValueError("stencil_rows needs at least one operator")
+    return torch.tensor(rows, dtype=torch.float64, device=device)
+
+
+def _torch_stream(stream, device):
+    """The context in which torch operations run on the raw HIP stream `stream` (None / 0: torch's current stream)."""
+    if not stream:
+        return contextlib.nullcontext()
+    import torch
+    return torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=device))
+
+
+def _extent(t):
+    """[lo, hi) in bytes of the memory a strided tensor touches; None for an empty one."""
+    lo = hi = 0
+    for n, st in zip(t.shape, t.stride()):
+        if n == 0:
+            return None
+        if st >= 0:
+            hi += (n - 1) * st
+        else:
+            lo += (n - 1) * st
+    size = t.element_size()
+    return t.data_ptr() + lo * size, t.data_ptr() + (hi + 1) * size
+
+
+def _overlap(a, b):
+    ea, eb = _extent(a), _extent(b)
+    return ea is not None and eb is not None and ea[0] < eb[1] and eb[0] < ea[1]
+
+
+def _sell_pack(lens):
+    """The SELL-64 frame of rows with `lens` (int64 device tensor, at least one row) live entries: (len int32, width int32, soff int64,
+    total).  One host read."""
+    import torch
+    nrows = int(lens.shape[0])
+    ns = (nrows + 63) // 64
+    padded = torch.zeros((ns * 64,), dtype=torch.int64, device=lens.device)
+    padded[:nrows] = lens
+    width = padded.view(ns, 64).max(dim=1).values
+    soff = torch.zeros((ns + 1,), dtype=torch.int64, device=lens.device)
+    soff[1:] = torch.cumsum(64 * width, 0)
+    return lens.to(torch.int32), width.to(torch.int32), soff, int(soff[-1])
+
+
+def _sell_launch(m, nop, val_ptr, R, X_ptr, sx_f, sx_p, Y, sy_f, sy_o, sy_i, alpha, beta, dev, s):
+    """One wlsqm_hip_sell_apply_device on the matrix m = dict(nrows, len, width, soff, col, total): the forward and the transposed product."""
+    B.check(B.lib().wlsqm_hip_sell_apply_device(m["nrows"], int(m["width"].shape[0]), _ptr(m["len"]), _ptr(m["width"]), _ptr(m["soff"]),
+                                                _ptr(m["col"]), C.c_void_p(val_ptr), m["total"], nop, R, C.c_void_p(X_ptr), sx_f, sx_p,
+                                                _ptr(Y), sy_f, sy_o, sy_i, float(alpha), float(beta), dev, s))
+
+
+class StencilOperator:
+    """Differential operators of the fit as one sparse matrix on the device: row j holds the coefficients with which operator o,
+    sum_a rows[o, a] d_a (a over the DOFs of wlsqm.fitter.defs), of the local model of case j depends on the point values, so that
+    ``apply(F)[o, j]`` is what ``rows[o] . fi_out[j]`` is after ``fit_cloud_device`` on the same geometry — in one pass over
+    4 + 8 nop bytes per neighbour, with no solve.  DESIGN.md section 16 has the algebra, the layout and the kernel.
+
+    dimension, order (an int), S, hoods, nk, knowns, weighting_method, point_index: the geometry as fit_cloud_adjoint_device takes it.
+    rows: float64 device tensor (nop, no), the same operators at every point, or (nop, ncases, no), variable coefficients (see
+    stencil_rows).  The constructor runs fit_cloud_adjoint_device once per operator with g = rows[o] (the coefficients are that
+    kernel's bits), packs them with torch operations on `stream` and synchronises; it keeps no reference to S.  3D orders 3 and 4 are
+    not covered (ValueError, as the adjoint).
+
+    The row of case j holds (hoods[j, k], slots[j, k]) for k < nk[j] in slot order, then, iff the function value is among the case's
+    knowns (bit F), one entry (point_index[j], grad_fi[j, 0]): the dependence on the point's own value.  A column named twice in a
+    row stays two entries.  Known DOFs other than F (and DOFs dropped by stray high mask bits, which leave the fit as they came) give an
+    affine term: ``known_coef`` (nop, ncases, no) holds their coefficients (column 0 zeroed where it went into the matrix) and
+    ``has_known_derivatives`` says whether any is non-zero; apply() then needs ``known``.
+
+    Numerics: an F-known fit subtracts the point's own value before it sums; a stencil applies to F as given, and a derivative's
+    coefficients sum to zero only to rounding.  A large constant offset in F costs digits in proportion to sum |c_k F_k|: subtract a
+    reference value from F first."""
+
+    def __init__(self, dimension, order, S, hoods, nk, knowns, weighting_method, rows, point_index=None, stream=None):
+        import torch
+        self._m = self._t = self._tval = None
+        no = _adjoint_order(dimension, order)
+        ncases, K = _cloud_geometry(dimension, S, hoods, nk, knowns, weighting_method, point_index,
+                                    "S must be contiguous; hoods must have a contiguous last axis")
+        if not hasattr(rows, "dim") or rows.dim() not in (2, 3):
+            raise ValueError("rows must be (nop, no) or (nop, ncases, no)")
+        per_case = rows.dim() == 3
+        _double_rows(rows, "rows", ncases if per_case else 1, no, (int(dimension), int(order)), lead=1 if per_case else 0)
+        nop = int(rows.shape[0])
+        if nop < 1:
+            raise ValueError(_FEW_ROWS % ("rows", nop, 1))
+        _same_device(S, hoods, nk, knowns, weighting_method, point_index, rows)
+        npoints, device = int(S.shape[0]), S.device
+        z = lambda *shape: torch.empty(shape, dtype=torch.float64, device=device)
+        with _torch_stream(stream, device):
+            slots, gfi, scratch = z(nop, ncases, K), z(nop, ncases, no), z(npoints)
+        for o in range(nop):
+            with _torch_stream(stream, device):
+                g = rows[o] if per_case else rows[o, :no].expand(ncases, no).contiguous()
+            fit_cloud_adjoint_device(dimension, order, S, hoods, nk, knowns, weighting_method, g, point_index=point_index,
+                                     grad_F=scratch, grad_fi=gfi[o], stream=stream, slots=slots[o])
+        with _torch_stream(stream, device):
+            fknown = (knowns[:ncases] & 1) != 0
+            zero = torch.zeros((), dtype=torch.float64, device=device)
+            own = torch.where(fknown[None, :], gfi[:, :, 0], zero)
+            gfi[:, :, 0] = torch.where(fknown[None, :], zero, gfi[:, :, 0])
+            pts = point_index[:ncases].long() if point_index is not None else torch.arange(ncases, device=device)
+            self._pack(hoods[:ncases], nk[:ncases], slots, own, fknown, pts, npoints)
+            self.known_coef = gfi
+            self.has_known_derivatives = bool((gfi != 0).any())
+        self.dimension, self.order, self.no = int(dimension), int(order), no
+
+    @classmethod
+    def from_coefficients(cls, hoods, nk, slots, npoints, own=None, own_mask=None, point_index=None, stream=None):
+        """The operator of given coefficients (no fit): row j holds (hoods[j, k], slots[o, j, k]) for k < nk[j], then, where own_mask[j],
+        (point_index[j], own[o, j]).  hoods (ncases, K) int32, nk (ncases,) int32, slots (nop, ncases, K) and own (nop, ncases) float64,
+        own_mask (ncases,) bool, point_index (ncases,) int32 (default: row j names point j): device tensors.  Only live slots are
+        looked at: the padding of hoods and slots may hold anything.  Synchronises."""
+        import torch
+        self = cls.__new__(cls)
+        self._m = self._t = self._tval = None
+        _check(hoods, "hoods", "int32", 2); _check(nk, "nk", "int32", 1)
+        ncases, K = int(hoods.shape[0]), int(hoods.shape[1])
+        _rows(ncases, nk=nk)
+        _double_rows(slots, "slots", ncases, K, lead=1,
+                     says="slots must be at least (nop, ncases, %d) with a contiguous last axis; got %s" % (K, tuple(slots.shape)))
+        nop = int(slots.shape[0])
+        if nop < 1 or ncases < 1:
+            raise ValueError(_FEW_ROWS % ("slots", min(nop, ncases), 1))
+        if (own is None) != (own_mask is None):
+            raise ValueError("own and own_mask go together")
+        if own is not None:
+            _double_rows(own, "own", nop, ncases, says="own must be at least (%d, %d) with a contiguous last axis; got %s"
+                         % (nop, ncases, tuple(own.shape)))
+            _check(own_mask, "own_mask", "bool", 1)
+            _rows(ncases, own_mask=own_mask)
+        if point_index is not None:
+            _check(point_index, "point_index", "int32", 1)
+            _rows(ncases, point_index=point_index)
+        _same_device(hoods, nk, slots, own, own_mask, point_index)
+        device = hoods.device
+        with _torch_stream(stream, device):
+            pts = point_index[:ncases].long() if point_index is not None else torch.arange(ncases, device=device)
+            self._pack(hoods, nk[:ncases], slots[:, :ncases, :K], own[:nop, :ncases] if own is not None else None,
+                       own_mask[:ncases] if own_mask is not None else None, pts, int(npoints))
+        self.known_coef, self.has_known_derivatives = None, False
+        self.dimension = self.order = None
+        self.no = 0
+        return self
+
+    def _pack(self, hoods, nk, slots, own, own_mask, pts, npoints):
+        """The SELL-64 arrays from per-slot coefficients (torch operations on the current stream; three host reads)."""
+        import torch
+        nop, ncases, K = (int(v) for v in slots.shape)
+        device = hoods.device
+        nkc = nk.long().clamp(0, K)
+        lens = nkc + own_mask.long() if own_mask is not None else nkc
+        len32, width, soff, total = _sell_pack(lens)
+        j = torch.arange(ncases, device=device)
+        live = torch.arange(K, device=device)[None, :] < nkc[:, None]
+        base = soff[j // 64] + j % 64
+        dest = (base[:, None] + 64 * torch.arange(K, device=device)[None, :])[live]
+        cols = hoods[live].long()
+        bad = ((cols < 0) | (cols >= npoints)).any()
+        col = torch.zeros((total,), dtype=torch.int32, device=device)
+        val = torch.zeros((nop, total), dtype=torch.float64, device=device)
+        col[dest] = cols.to(torch.int32)
+        val[:, dest] = slots[:, live]
+        if own_mask is not None:
+            d_own = (base + 64 * nkc)[own_mask]
+            c_own = pts[own_mask]
+            bad = bad | ((c_own < 0) | (c_own >= npoints)).any()
+            col[d_own] = c_own.to(torch.int32)
+            val[:, d_own] = own[:, own_mask]
+        if bool(bad):
+            raise ValueError("a live entry names a point outside 0 .. npoints - 1 = %d" % (npoints - 1))
+        self._m = dict(nrows=ncases, len=len32, width=width, soff=soff, col=col, total=total)
+        self._val, self._nk, self._own_mask = val, nkc, own_mask
+        self._nnz = int(lens.sum())
+        self.nop, self.ncases, self.npoints, self.K, self._device = nop, ncases, int(npoints), K, device
+
+    def _live(self):
+        if getattr(self, "_m", None) is None:
+            raise RuntimeError("the stencil operator has been closed")
+        return self._m
+
+    def close(self):
+        """Release the device memory now; harmless when called again."""
+        self._m = self._t = self._val = self._tval = self._nk = self._own_mask = self.known_coef = None
+
+    def memory_used(self):
+        """Bytes of device memory the operator holds (the transposed matrix included once built)."""
+        self._live()
+        held = list(self._m.values()) + [self._val, self._nk, self._own_mask, self.known_coef]
+        if self._t is not None:
+            held += list(self._t.values()) + [self._tval]
+        return sum(t.numel() * t.element_size() for t in held if hasattr(t, "numel"))
+
+    @property
+    def fill(self):
+        """Live entries over stored entries of the forward matrix (1.0: no padding)."""
+        m = self._live()
+        return self._nnz / m["total"] if m["total"] else 1.0
+
+    @property
+    def fill_transposed(self):
+        """The same for the transposed matrix; None until prepare_transpose has built it."""
+        self._live()
+        if self._t is None:
+            return None
+        return self._nnz / self._t["total"] if self._t["total"] else 1.0
+
+    def _entries(self):
+        """(src, row): the position in col / val and the row of every live entry, in (case, entry) order."""
+        import torch
+        m = self._live()
+        device = self._device
+        j = torch.arange(self.ncases, device=device)
+        e = torch.arange(self.K + 1, device=device)
+        live = e[None, :] < m["len"].long()[:, None]
+        base = m["soff"][j // 64] + j % 64
+        return (base[:, None] + 64 * e[None, :])[live], j[:, None].expand(self.ncases, self.K + 1)[live]
+
+    def _apply_args(self, F, known):
+        """The checks of apply's inputs: (stacked, R)."""
+        self._live()
+        if not hasattr(F, "dim") or not hasattr(F, "is_cuda"):
+            raise ValueError("argument F must be a device (HIP) tensor")
+        stacked = F.dim() == 2
+        _check(F, "F", "float64", 2 if stacked else 1)
+        R = int(F.shape[0]) if stacked else 1
+        if F.shape[-1] < self.npoints:
+            raise ValueError("F has fewer entries than S has points")
+        if R < 1:
+            raise ValueError(_FEW_ROWS % ("F", R, 1))
+        if F.device != self._device:
+            raise ValueError("all tensors must be on the same device")
+        if known is None:
+            if self.has_known_derivatives:
+                raise ValueError("the operator depends on known DOFs other than F: pass known=, (ncases, >= %d) with the known values of "
+                                 "every case in their DOF columns (the fi that the fit would be given), or a stack of those" % self.no)
+        elif self.known_coef is not None:
+            lead = 1 if hasattr(known, "dim") and known.dim() == 3 else 0
+            _double_rows(known, "known", self.ncases, self.no, lead=lead)
+            if lead and (not stacked or known.shape[0] != R):
+                raise ValueError("known is a stack of %d, F %s" % (known.shape[0], "a stack of %d" % R if stacked else "one field"))
+            _same_device(F, known)
+        return stacked, R
+
+    def _out(self, out, shape, beta, against, device):
+        import torch
+        if out is None:
+            return (torch.zeros if beta != 0 else torch.empty)(shape, dtype=torch.float64, device=device)
+        _check(out, "out", "float64", len(shape))
+        if tuple(out.shape) != tuple(shape):
+            raise ValueError("out must be a float64 device tensor of shape %s; got %s" % (tuple(shape), tuple(out.shape)))
+        if out.device != device:
+            raise ValueError("all tensors must be on the same device")
+        if _overlap(out, against):
+            raise ValueError("out overlaps the input in memory: the product does not run in place")
+        return out
+
+    def apply(self, F, out=None, alpha=1.0, beta=0.0, known=None, stream=None):
+        """out = alpha * (A F + the known term) + beta * out.  F (npoints,) or (R, npoints), float64 on the operator's device, any
+        strides; returns (nop, ncases) or (R, nop, ncases) (`out`: that shape, any strides, not overlapping F; beta == 0 never reads
+        it).  known: (ncases, >= no) or a stack (R, ncases, >= no), the known values in their DOF columns; required (ValueError) when
+        has_known_derivatives, its term is added by torch operations on the same stream.  Otherwise one kernel launch on `stream`
+        (default: torch's current stream): no allocation when `out` is given, no synchronisation, so it can be captured."""
+        import torch
+        stacked, R = self._apply_args(F, known)
+        m = self._m
+        out = self._out(out, ((R,) if stacked else ()) + (self.nop, self.ncases), beta, F, self._device)
+        s, dev = _stream_and_device(F, stream)
+        _sell_launch(m, self.nop, self._val.data_ptr(), R, F.data_ptr(), int(F.stride(0)) if stacked else 0, int(F.stride(-1)), out,
+                     int(out.stride(0)) if stacked else 0, int(out.stride(-2)), int(out.stride(-1)), alpha, beta, dev, s)
+        if known is not None and self.has_known_derivatives:
+            with _torch_stream(stream, self._device):
+                out.add_(torch.einsum("oja,...ja->...oj", self.known_coef, known[..., :self.ncases, :self.no]), alpha=float(alpha))
+        return out
+
+    def _known_adjoint(self, g, known_shape, stream):
+        """dL/dknown from g = dL/d(apply's result): known_coef-weighted, zeros where the forward reads nothing."""
+        import torch
+        with _torch_stream(stream, self._device):
+            out = torch.zeros(known_shape, dtype=torch.float64, device=self._device)
+            if self.known_coef is not None:
+                if g.dim() == 3 and len(known_shape) == 2:
+                    g = g.sum(dim=0)
+                out[..., :self.ncases, :self.no] = torch.einsum("...oj,oja->...ja", g, self.known_coef)
+        return out
+
+    def prepare_transpose(self, stream=None):
+        """Build the transposed matrix now, npoints x ncases in the same format: a stable sort of the entries by column, ties in
+        (case, entry) order, so the transposed sums are deterministic.  Without this call the first transposed use builds it, which
+        allocates and synchronises — RuntimeError when that would happen inside a graph capture.  Returns True when this call built it."""
+        import torch
+        m = self._live()
+        if self._t is not None:
+            return False
+        with _torch_stream(stream, self._device):
+            if self._device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the operator has no transposed matrix yet and the stream is capturing: call prepare_transpose before the capture")
+            src, row = self._entries()
+            c = m["col"][src].long()
+            c_sorted, order = torch.sort(c, stable=True)
+            tlens = torch.bincount(c, minlength=self.npoints)
+            start = torch.cumsum(tlens, 0) - tlens
+            et = torch.arange(c.shape[0], device=self._device) - start[c_sorted]
+            len32, width, soff, total = _sell_pack(tlens)
+            dest = soff[c_sorted // 64] + 64 * et + c_sorted % 64
+            tcol = torch.zeros((total,), dtype=torch.int32, device=self._device)
+            tval = torch.zeros((self.nop, total), dtype=torch.float64, device=self._device)
+            tcol[dest] = row[order].to(torch.int32)
+            tval[:, dest] = self._val[:, src[order]]
+            self._t = dict(nrows=self.npoints, len=len32, width=width, soff=soff, col=tcol, total=total)
+            self._tval = tval
+        return True
+
+    def apply_transpose(self, g, out=None, alpha=1.0, beta=0.0, stream=None):
+        """out = alpha * sum_o A_o^T g[o] + beta * out.  g (nop, ncases) or (R, nop, ncases), any strides; returns (npoints,) or
+        (R, npoints).  The same kernel on the transposed matrix, one launch per operator (each adds to `out` in operator order): no
+        atomics, the bits are a function of the operator and of g.  Builds the transposed matrix at the first use (prepare_transpose)."""
+        self._live()
+        if not hasattr(g, "dim") or not hasattr(g, "is_cuda"):
+            raise ValueError("argument g must be a device (HIP) tensor")
+        stacked = g.dim() == 3
+        _check(g, "g", "float64", 3 if stacked else 2)
+        if tuple(g.shape[-2:]) != (self.nop, self.ncases):
+            raise ValueError("g must be (nop, ncases) = (%d, %d), or a stack of those; got %s" % (self.nop, self.ncases, tuple(g.shape)))
+        R = int(g.shape[0]) if stacked else 1
+        if R < 1:
+            raise ValueError(_FEW_ROWS % ("g", R, 1))
+        if g.device != self._device:
+            raise ValueError("all tensors must be on the same device")
+        out = self._out(out, ((R,) if stacked else ()) + (self.npoints,), beta, g, self._device)
+        if self._t is None:
+            self.prepare_transpose(stream)
+        s, dev = _stream_and_device(g, stream)
+        for o in range(self.nop):
+            _sell_launch(self._t, 1, self._tval.data_ptr() + 8 * o * self._t["total"], R, g.data_ptr() + 8 * o * int(g.stride(-2)),
+                         int(g.stride(0)) if stacked else 0, int(g.stride(-1)), out, int(out.stride(0)) if stacked else 0, 0,
+                         int(out.stride(-1)), alpha, beta if o == 0 else 1.0, dev, s)
+        return out
+
+    def coefficients(self):
+        """(slots (nop, ncases, K), own (nop, ncases)): the coefficients unpacked, per neighbour slot and on the point's own value;
+        exact zeros in the padding and where a row has no own entry."""
+        import torch
+        m = self._live()
+        device = self._device
+        slots = torch.zeros((self.nop, self.ncases, self.K), dtype=torch.float64, device=device)
+        own = torch.zeros((self.nop, self.ncases), dtype=torch.float64, device=device)
+        j = torch.arange(self.ncases, device=device)
+        k = torch.arange(self.K, device=device)
+        live = k[None, :] < self._nk[:, None]
+        base = m["soff"][j // 64] + j % 64
+        slots[:, live] = self._val[:, (base[:, None] + 64 * k[None, :])[live]]
+        if self._own_mask is not None:
+            own[:, self._own_mask] = self._val[:, (base + 64 * self._nk)[self._own_mask]]
+        return slots, own
+
+    def to_sparse_csr(self, o=0):
+        """Operator `o` as a torch.sparse_csr_tensor (ncases, npoints): columns sorted, duplicates summed."""
+        import torch
+        self._live()
+        if not 0 <= int(o) < self.nop:
+            raise ValueError("the operator has %d value planes; got o = %d" % (self.nop, int(o)))
+        src, row = self._entries()
+        coo = torch.sparse_coo_tensor(torch.stack([row, self._m["col"][src].long()]), self._val[int(o), src],
+                                      (self.ncases, self.npoints))
+        import warnings
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)       # torch announces its CSR support as beta at the first use
+            return coo.coalesce().to_sparse_csr()
+
+
+def differentiable_stencil_apply(op, F, known=None, stream=None):
+    """op.apply(F, known=known) as a differentiable function of F (npoints,) or (R, npoints) and of `known`: the same bits as apply,
+    with a grad_fn.  The backward pass is op.apply_transpose (the same kernel on the transposed matrix, no atomics), computed only
+    when F requires a gradient; dL/dF has F's full shape, zeros beyond the operator's points.  `known` receives the
+    known_coef-weighted gradients.  Call op.prepare_transpose() first when the backward pass is to be captured into a graph.
+    Once differentiable."""
+    op._apply_args(F, known)                       # before anything is detached
+    return _autograd().StencilApply.apply(F, known, op, stream)
 
 
 # ---- batched dense solves (the kernels behind wlsqm.utils.lapackdrivers), device-resident ----
