@@ -524,7 +524,8 @@ int wlsqm_hip_symmetrize_batched_host(int n, int64_t count, double* A, int devic
  * Entry e of row i sits at soff[i / 64] + 64 * e + i % 64, so a wave reads 256 contiguous bytes of col and 512 of each val plane per
  * step.  An entry with e >= len[i] is padding: neither its column nor its value is used, and X is never dereferenced for it, whatever
  * the arrays hold there (NaN and inf included).  The caller guarantees len[i] <= width[i / 64] (a longer row is cut at the width) and
- * 0 <= col < ncols for every live entry.
+ * 0 <= col < ncols for every live entry.  The writers of the layout keep the same rule from their side: wlsqm_hip_stencil_build_device
+ * and wlsqm_hip_sell_permute_device (below) write live entries only and leave the padding of col and val as it is.
  *
  * wlsqm_hip_sell_apply_device:  Y[r, o, i] = alpha * sum_{e < len[i]} val[o][.] * X[r, col[.]] + beta * Y[r, o, i]  for nop >= 1
  * operators and R >= 1 stacked vectors; X[r, c] is at X[r * x_stride_field + c * x_stride_point], Y[r, o, i] at
@@ -538,6 +539,35 @@ int wlsqm_hip_sell_apply_device(int64_t nrows, int64_t nslices, const int32_t* l
                                 int64_t R, const double* X, int64_t x_stride_field, int64_t x_stride_point,
                                 double* Y, int64_t y_stride_field, int64_t y_stride_op, int64_t y_stride_row,
                                 double alpha, double beta, int device, void* stream);
+
+/* wlsqm_hip_stencil_build_device (csrc/fit_adjoint.hip): the coefficients of nop operators of the fit written straight into that layout,
+ * row j = case j, one wave per slice.  The geometry arguments are those of wlsqm_hip_fit_cloud_adjoint_device; rows[o * rows_stride_op +
+ * j * rows_stride_case + a] is lambda_o of case j (rows_stride_case == 0: the same operators at every case).  With n = clamp(nk[j], 0,
+ * max_nk) and y_o = M_UU^-1 lambda_o (ONE factorisation per case for all operators), entry k < n of row j is
+ * (hoods[j, k], w_k (c_k . y_o)): the bits of wlsqm_hip_fit_cloud_adjoint_device's grad_slots for g = lambda_o for the systems up to 10
+ * unknowns; where bit F is in knowns[j], entry n is (point_index[j] or j, grad_fi[j, 0] of that call).  known_coef[o * kc_stride_op +
+ * j * kc_stride_case + a] (nullable) is that call's grad_fi[j, a], column 0 zeroed where it went into the matrix.  A case with every DOF
+ * known has zeros on its neighbours and lambda in the known terms.  col is nullable (not written: the neighbour lists have not changed).
+ * PRECONDITION: len[j] = clamp(nk[j], 0, max_nk) + (bit F of knowns[j]) and soff is the frame of those len (nslices + 1 entries).  Entry e
+ * of row j is written iff e < len[j] and e < (soff[j / 64 + 1] - soff[j / 64]) / 64; padding entries of col and val are neither read nor
+ * written, the padding of a hoods row is never dereferenced.  A frame that breaks the precondition costs wrong values (entries of a
+ * row left unwritten, or a row cut short) and never a write outside the arrays that soff describes.  Live entries of hoods are the
+ * caller's to keep within S, as for every index-based call.  ONE kernel launch on `stream` (wlsqm_hip_last_kernel(): "stencil-build"):
+ * no allocation, no synchronisation, no state; ncases == 0 launches nothing.  1D orders 0-4, 2D orders 0-4, 3D orders 0-2; otherwise
+ * WLSQM_EVALUE, "fit_adjoint: unsupported (dimension, order)". */
+int wlsqm_hip_stencil_build_device(int dimension, int order, int64_t ncases, int64_t max_nk,
+                                   const double* S, const int32_t* hoods, int64_t hoods_stride_case,
+                                   const int32_t* point_index, const int32_t* nk, const int64_t* knowns,
+                                   const int32_t* weighting_method,
+                                   const double* rows, int64_t rows_stride_op, int64_t rows_stride_case, int nop,
+                                   const int32_t* len, const int64_t* soff, int32_t* col, double* val, int64_t val_stride_op,
+                                   double* known_coef, int64_t kc_stride_op, int64_t kc_stride_case, int device, void* stream);
+
+/* wlsqm_hip_sell_permute_device: out[o * out_stride_op + dest[e]] = in[o * in_stride_op + src[e]] for e < n and o < nop, one (dest, src)
+ * pair for all planes: the values of a transposed matrix from those of the forward one.  dest must not name a position twice; positions
+ * that no pair names are neither read nor written.  One kernel launch ("stencil-permute"), as above; n == 0 launches nothing. */
+int wlsqm_hip_sell_permute_device(int64_t n, const int32_t* dest, const int32_t* src, const double* in, int64_t in_stride_op,
+                                  double* out, int64_t out_stride_op, int nop, int device, void* stream);
 
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ---- */
 /* Runs `reps` back-to-back launches of the fit kernel for batch `b` (device-resident, uniform

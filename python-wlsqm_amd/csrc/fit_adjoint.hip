@@ -621,4 +621,269 @@ int launch_fit_geometry_adjoint(int dimension, int order, const KParams& p, cons
     return WLSQM_EVALUE;
 }
 
+// ---- the stencil build: the adjoint's coefficients of a block of operators, stored as SELL-64 ------------------
+// What StencilOperator's constructor assembles from one adjoint-lane launch per operator, a scatter and a pack, in one launch: one lane per
+// case, which is one lane per row of the matrix, one wave per slice, so coefficient k of the 64 rows of a slice leaves as one contiguous
+// 512-byte run per value plane.  Passes one and two are adjoint_case's (M, the knowns masked, ONE factorisation); then, for NB operators
+// at a time, y_o = M_UU^-1 lambda_o and one pass over the neighbours that forms c_k and w_k once and stores w_k (c_k . y_o) for every
+// operator of the block.  The statements of adjoint_case in its order: for the systems up to 10 unknowns (pin_fma) the coefficients are
+// the bits of "adjoint-lane".  More than NB operators loop over the blocks with the factor in registers.
+struct StencilBuildArgs {
+    const double* lam; long long slam_o, slam_j;    // lambda[o, j, :] (slam_j == 0: the same operators at every case)
+    int nop;
+    const int32_t* len; const long long* soff;      // the frame: entry e of row j sits at soff[j / 64] + 64 e + j % 64 and is written iff e < len[j]
+    int32_t* col;                                   // nullable: not written
+    double* val; long long sval_o;
+    double* kc; long long skc_o, skc_j;             // known_coef, nullable
+};
+
+// eliminate_knowns on the right-hand side with the knowns' values zero: g[a] = fma(-M[a, om], 0, g[a]) per known om.  It leaves a finite
+// non-zero g[a] as it is; what it does to a zero (the sign) or when M[a, om] is not finite (NaN) it does to -0.0 as well, and adding
+// that result to g[a] gives, bit for bit, what the chain started from g[a] gives.  So the chain runs once per case, on z = -0.0 (which
+// masks M on the way, as pass two needs), and every operator's right-hand side is lambda + z (0 at the knowns).  z[a] is -0.0, +0.0
+// or NaN: two bits per DOF (zpos, znan) carry it through the blocks.
+template <int NO>
+__device__ __forceinline__ void build_rhs(const double* lam, unsigned zpos, unsigned znan, unsigned long long known, double (&y)[NO]) {
+#pragma unroll
+    for (int a = 0; a < NO; ++a) {
+        const double z = ((znan >> a) & 1u) ? __builtin_nan("") : ((zpos >> a) & 1u) ? 0.0 : -0.0;
+        y[a] = ((known >> a) & 1ull) ? 0.0 : lam[a] + z;
+    }
+}
+
+// Where the entries of row j go (entry e at at + 64 e) and how many of them may be written: e < len[j], and e < the slice's width, so
+// that whatever nk, the mask and len say no write leaves the slice.
+__device__ __forceinline__ void build_frame(const StencilBuildArgs& q, long long j, long long& at, int& live) {
+    const long long s0 = q.soff[blockIdx.x];
+    const long long wid = (q.soff[blockIdx.x + 1] - s0) >> 6;
+    live = q.len[j];
+    live = live < wid ? live : (int)wid;
+    at = s0 + threadIdx.x;
+}
+
+// ONE: the launch has one operator (NB == 1), there is no loop over blocks and the factor dies with its only solve.  Beyond 10 unknowns
+// the factor's 240 registers cannot stay live through pass three of a loop over blocks without scratch (profiles/isa_r06.txt): there, and
+// there only, each lane parks its factor in LDS behind the factorisation (slot e of lane l at e * 64 + l: no bank conflicts, no barrier,
+// a lane reads what it wrote) and every block's solve reads it back.
+// At most two waves per SIMD: a lane walks its own row of hoods, so a wave's loads of hr[k] touch 64 lines that serve the next 32 values
+// of k only while they stay in the CU's 32 KiB of L1.  Measured on 1M points of 2D order 2 at 24 neighbours: the one-operator kernel, whose 91
+// registers would admit five waves, took 1.25 ms, the four-operator kernel (206 registers, two waves) 0.53 ms for three operators.
+template <int DIM, int ORDER, int NB, bool ONE>
+__global__ __launch_bounds__(ADJ_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 2))) void stencil_build_kernel(const KParams p, const StencilBuildArgs q) {
+    constexpr int NO = ndofs(DIM, ORDER);
+    constexpr int NE = NO * (NO + 1) / 2;
+    constexpr bool PARK = !ONE && !pin_fma(NO);
+    static_assert(!ONE || NB == 1, "one operator is a block of one");
+    constexpr unsigned long long FULL = (1ull << NO) - 1ull;
+    const long long j = (long long)blockIdx.x * ADJ_BLOCK + threadIdx.x;       // the row; blockIdx.x is the slice
+    if (j >= p.ncases) return;
+    const int K = (int)p.max_nk;
+    const int nk = max(min(p.nk[j * p.snk], K), 0);                   // never past the end of a row
+    const bool uniform = (p.wm[j * p.swm] == WLSQM_WEIGHT_UNIFORM);
+    const long long raw = p.knowns[j * p.sknowns];
+    unsigned long long known, dropped;
+    effective_mask<NO>(raw, known, dropped);
+    const bool fknown = (raw & 1ll) != 0;                            // the row ends in the entry of the point's own value
+    const long long pj = own_point(p, j);
+    const int* hr = p.hoods + j * p.shoods_j;
+    if (known == FULL) {                            // nothing to solve: zeros on the neighbours, lambda in the known terms
+        long long at; int live;
+        build_frame(q, j, at, live);
+        if (q.col) {
+            for (int k = 0; k < nk; ++k)
+                if (k < live) q.col[at + 64LL * k] = hr[k];
+            if (fknown && nk < live) q.col[at + 64LL * nk] = (int32_t)pj;
+        }
+        for (int o = 0; o < q.nop; ++o) {
+            const double* lo = q.lam + j * q.slam_j + o * q.slam_o;
+            double* v = q.val + o * q.sval_o + at;
+            for (int k = 0; k < nk; ++k)
+                if (k < live) v[64LL * k] = 0.0;
+            if (fknown && nk < live) v[64LL * nk] = lo[0];
+            if (q.kc) {
+                double* kc = q.kc + o * q.skc_o + j * q.skc_j;
+#pragma unroll
+                for (int a = 0; a < NO; ++a) kc[a] = (a == 0 && fknown) ? 0.0 : lo[a];
+            }
+        }
+        return;
+    }
+    double xi[DIM];
+#pragma unroll
+    for (int m = 0; m < DIM; ++m) xi[m] = p.S[pj * DIM + m];
+    const AdjLaneRows<DIM> rows{nullptr, 0, hr, p.S, nullptr, 0};
+    // pass 1: largest squared distance; not needed for uniform weights
+    double max_d2 = 0.0;
+    if (!uniform) {
+        for (int k = 0; k < nk; ++k) {
+            double d[DIM];
+            rows.offset(k, xi, d);
+            double d2 = d[0] * d[0];
+            if constexpr (DIM >= 2) d2 += d[1] * d[1];
+            if constexpr (DIM == 3) d2 += d[2] * d[2];
+            if (d2 > max_d2) max_d2 = d2;
+        }
+    }
+    const double inv_max = inverse_max(max_d2);
+    // pass 2: M = C^T W C (upper triangle)
+    double M[NE];
+#pragma unroll
+    for (int e = 0; e < NE; ++e) M[e] = 0.0;
+    for (int k = 0; k < nk; ++k) {
+        double d[DIM], c[NO];
+        rows.offset(k, xi, d);
+        const double d2 = monomials<DIM, ORDER>(d, c);
+        accumulate_matrix<NO>(M, c, weight(d2, inv_max, uniform));
+    }
+    // knowns: rows and columns masked to identity; z is what the elimination does to a right-hand side (build_rhs)
+    unsigned zpos = 0, znan = 0;
+    {
+        double zero[NO], z[NO];
+#pragma unroll
+        for (int a = 0; a < NO; ++a) { zero[a] = 0.0; z[a] = -0.0; }
+        eliminate_knowns<NO>(M, z, known, zero);
+#pragma unroll
+        for (int a = 0; a < NO; ++a) {
+            if (z[a] != z[a]) znan |= 1u << a;
+            else if (!__builtin_signbit(z[a])) zpos |= 1u << a;
+        }
+    }
+    ldlt_factor<NO>(M);
+    __shared__ double parked[PARK ? NE * ADJ_BLOCK : 1];
+    if constexpr (PARK) {
+#pragma unroll
+        for (int e = 0; e < NE; ++e) parked[e * ADJ_BLOCK + threadIdx.x] = M[e];
+    }
+    const bool sums = (known & ~dropped) != 0ull;
+    // the frame and the operators' addresses are formed here, behind the factorisation, which has no register to spare for them
+    long long at; int live;
+    build_frame(q, j, at, live);
+    const double* lam = q.lam + j * q.slam_j;
+    const int nop = ONE ? 1 : q.nop;
+    for (int o0 = 0; o0 < nop; o0 += NB) {
+        const int nb = nop - o0 < NB ? nop - o0 : NB;                // wave-uniform
+        double y[NB][NO], acc[NB][NO];
+        if constexpr (PARK) {
+            __asm__ volatile("" ::: "memory");      // the loads stay inside the loop: hoisted, the factor would be live through pass three again
+#pragma unroll
+            for (int e = 0; e < NE; ++e) M[e] = parked[e * ADJ_BLOCK + threadIdx.x];
+        }
+#pragma unroll
+        for (int o = 0; o < NB; ++o) {
+            build_rhs<NO>(lam + (o0 + (o < nb ? o : 0)) * q.slam_o, zpos, znan, known, y[o]);
+            ldlt_solve<NO>(M, y[o]);                // y_U = M_UU^-1 lambda_U, y = 0 outside U
+#pragma unroll
+            for (int a = 0; a < NO; ++a) acc[o][a] = 0.0;
+        }
+        // pass 3: w_k (c_k . y_o) into the value planes; the true knowns' columns collect sum_k c_k[a] (.) = (M y_o)[a]
+        double* val = q.val + o0 * q.sval_o + at;
+#pragma unroll 1
+        for (int k = 0; k < nk; ++k) {
+            double d[DIM], c[NO];
+            rows.offset(k, xi, d);
+            const double d2 = monomials<DIM, ORDER>(d, c);
+            const double w = weight(d2, inv_max, uniform);
+            if (o0 == 0 && q.col && k < live) q.col[at + 64LL * k] = hr[k];
+#pragma unroll
+            for (int o = 0; o < NB; ++o) {
+                double s = y[o][0];
+#pragma unroll
+                for (int a = 1; a < NO; ++a) s = fma(c[a], y[o][a], s);
+                const double gk = w * s;
+                if (o < nb && k < live) val[o * q.sval_o + 64LL * k] = gk;
+                if (sums) {
+                    // adjoint_case's `acc[0] += gk` leaves the compiler the choice to contract gk = w * s into the sum, and it chooses by
+                    // the size of the loop: "adjoint-lane" has fma(w, s, acc[0]) up to 3 unknowns (the loop is unswitched on `sums`, product
+                    // and sum share a block) and the plain sum from 4 on (read from its ISA, all 13 instantiations; tests/
+                    // test_gpu_stencil_update.py holds every system up to 10 unknowns to the constructor's bits).  Spelled out either way.
+                    if constexpr (NO <= 3) {
+                        acc[o][0] = fma(w, s, acc[o][0]);
+                    } else {
+#pragma clang fp contract(off)
+                        acc[o][0] = acc[o][0] + gk;
+                    }
+#pragma unroll
+                    for (int a = 1; a < NO; ++a) acc[o][a] = fma(c[a], gk, acc[o][a]);
+                }
+            }
+        }
+        if (o0 == 0 && q.col && fknown && nk < live) q.col[at + 64LL * nk] = (int32_t)pj;
+#pragma unroll
+        for (int o = 0; o < NB; ++o) {
+            if (o < nb) {
+                const double* gb = lam + (o0 + o) * q.slam_o;         // read again: a copy of lambda beside the factor costs the 15-unknown system scratch
+                if (fknown && nk < live) val[o * q.sval_o + 64LL * nk] = gb[0] - acc[o][0];
+                if (q.kc) {
+                    double* kc = q.kc + (o0 + o) * q.skc_o + j * q.skc_j;
+#pragma unroll
+                    for (int a = 0; a < NO; ++a) {
+                        double v = 0.0;                                          // an unknown's incoming value is never read by the fit
+                        if ((known >> a) & 1ull) v = ((dropped >> a) & 1ull) ? gb[a] : gb[a] - acc[o][a];
+                        kc[a] = (a == 0 && fknown) ? 0.0 : v;
+                    }
+                }
+            }
+        }
+    }
+}
+
+// Operators per block: what the register file carries beside the factor without scratch (profiles/isa_r06.txt).
+constexpr int stencil_build_block(int no) { return no <= 6 ? 4 : no <= 10 ? 2 : 1; }
+
+template <int DIM, int ORDER>
+static int launch_stencil_build(const KParams& p, const StencilBuildArgs& q, hipStream_t stream) {
+    constexpr int NB = stencil_build_block(ndofs(DIM, ORDER));
+    const long long blocks = (p.ncases + ADJ_BLOCK - 1) / ADJ_BLOCK;
+    if (blocks > 0x7fffffffLL) { set_error("too many cases for one launch"); return WLSQM_EVALUE; }
+    if (q.nop == 1) hipLaunchKernelGGL((stencil_build_kernel<DIM, ORDER, 1, true>), dim3((unsigned)blocks), dim3(ADJ_BLOCK), 0, stream, p, q);
+    else hipLaunchKernelGGL((stencil_build_kernel<DIM, ORDER, NB, false>), dim3((unsigned)blocks), dim3(ADJ_BLOCK), 0, stream, p, q);
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("stencil-build");
+    return WLSQM_OK;
+}
+
+static int launch_stencil_build_any(int dimension, int order, const KParams& p, const StencilBuildArgs& q, hipStream_t stream) {
+#define CASE(D, O) if (dimension == D && order == O) return launch_stencil_build<D, O>(p, q, stream);
+    CASE(1, 0) CASE(1, 1) CASE(1, 2) CASE(1, 3) CASE(1, 4)
+    CASE(2, 0) CASE(2, 1) CASE(2, 2) CASE(2, 3) CASE(2, 4)
+    CASE(3, 0) CASE(3, 1) CASE(3, 2)
+#undef CASE
+    set_error("fit_adjoint: unsupported (dimension, order)");
+    return WLSQM_EVALUE;
+}
+
 }  // namespace wlsqm
+
+using namespace wlsqm;
+
+extern "C" {
+
+int wlsqm_hip_stencil_build_device(int dimension, int order, int64_t ncases, int64_t max_nk,
+                                   const double* S, const int32_t* hoods, int64_t hoods_stride_case,
+                                   const int32_t* point_index, const int32_t* nk, const int64_t* knowns,
+                                   const int32_t* weighting_method,
+                                   const double* rows, int64_t rows_stride_op, int64_t rows_stride_case, int nop,
+                                   const int32_t* len, const int64_t* soff, int32_t* col, double* val, int64_t val_stride_op,
+                                   double* known_coef, int64_t kc_stride_op, int64_t kc_stride_case, int device, void* stream) {
+    if (dimension < 1 || dimension > 3) { set_error("dimension must be 1, 2 or 3"); return WLSQM_EVALUE; }
+    const int no = wlsqm_hip_number_of_dofs(dimension, order);
+    if (no < 0) { set_error("order must be 0..4"); return WLSQM_EVALUE; }
+    if (ncases < 0) { set_error("ncases must be >= 0"); return WLSQM_EVALUE; }
+    if (max_nk < 0) { set_error("max_nk must be >= 0"); return WLSQM_EVALUE; }
+    if (nop < 1) { set_error("stencil_build: nop must be >= 1"); return WLSQM_EVALUE; }
+    if (ncases > 0 && (!S || !hoods || !nk || !knowns || !weighting_method || !rows || !len || !soff || !val)) { set_error("null array"); return WLSQM_EVALUE; }
+    if (known_coef && kc_stride_case < no) { set_error("gradient rows narrower than the number of DOFs"); return WLSQM_EVALUE; }
+    if (hoods_stride_case < max_nk) { set_error("hoods rows narrower than max_nk"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    const int rc = scope.enter(device);
+    if (rc != WLSQM_OK || ncases == 0) return rc;
+    KParams p{};
+    p.hoods = hoods; p.shoods_j = hoods_stride_case; p.S = S; p.pidx = point_index;
+    p.nk = nk; p.snk = 1; p.knowns = (const long long*)knowns; p.sknowns = 1; p.wm = weighting_method; p.swm = 1;
+    p.ncases = ncases; p.max_nk = max_nk;
+    const StencilBuildArgs q{rows, rows_stride_op, rows_stride_case, nop, len, reinterpret_cast<const long long*>(soff), col, val, val_stride_op,
+                             known_coef, kc_stride_op, kc_stride_case};
+    return launch_stencil_build_any(dimension, order, p, q, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -133,6 +133,16 @@ static int sell_launch(const SellArgs& a, hipStream_t stream) {
     return WLSQM_OK;
 }
 
+// out[o][dest[e]] = in[o][src[e]] for e < n: the values of the transposed matrix from those of the forward one (or any other
+// rearrangement of the live entries), one (dest, src) pair for all planes.  Padding is named by no pair: neither read nor written.
+__global__ void __launch_bounds__(256) sell_permute_kernel(long long n, const int32_t* dest, const int32_t* src, const double* in,
+                                                           long long in_stride_op, double* out, long long out_stride_op, int nop) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const long long d = dest[e], s = src[e];
+    for (int o = 0; o < nop; ++o) out[o * out_stride_op + d] = in[o * in_stride_op + s];
+}
+
 }  // namespace wlsqm
 
 using namespace wlsqm;
@@ -163,6 +173,21 @@ int wlsqm_hip_sell_apply_device(int64_t nrows, int64_t nslices, const int32_t* l
     a.Y = Y; a.sy_f = y_stride_field; a.sy_o = y_stride_op; a.sy_i = y_stride_row;
     a.alpha = alpha; a.beta = beta;
     return sell_launch(a, (hipStream_t)stream);
+}
+
+int wlsqm_hip_sell_permute_device(int64_t n, const int32_t* dest, const int32_t* src, const double* in, int64_t in_stride_op,
+                                  double* out, int64_t out_stride_op, int nop, int device, void* stream) {
+    if (nop < 1) { set_error("sell_permute: nop must be >= 1"); return WLSQM_EVALUE; }
+    if (n < 0 || (n + 255) / 256 > 0x7fffffffLL) { set_error("sell_permute: n must be 0 .. 2^39"); return WLSQM_EVALUE; }
+    if (n > 0 && (!dest || !src || !in || !out)) { set_error("null array"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    const int rc = scope.enter(device);
+    if (rc != WLSQM_OK || n == 0) return rc;
+    hipLaunchKernelGGL(sell_permute_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long long)n, dest, src, in,
+                       (long long)in_stride_op, out, (long long)out_stride_op, nop);
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("stencil-permute");
+    return WLSQM_OK;
 }
 
 }  // extern "C"

@@ -180,6 +180,16 @@ def lib():
                                                   C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                                   C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int, C.c_void_p]
         L.wlsqm_hip_sell_apply_device.restype = C.c_int
+    # the fused build of the value planes on a moved cloud and the transposed values (StencilOperator.update)
+    if hasattr(L, "wlsqm_hip_stencil_build_device"):
+        L.wlsqm_hip_stencil_build_device.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                     C.c_int64, C.c_int, C.c_void_p]
+        L.wlsqm_hip_stencil_build_device.restype = C.c_int
+        L.wlsqm_hip_sell_permute_device.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
+                                                    C.c_int, C.c_void_p]
+        L.wlsqm_hip_sell_permute_device.restype = C.c_int
     # batched dense solves (wlsqm.utils.lapackdrivers, wlsqm.hip.*_batched)
     for op in ("getrf", "gesv", "sytrf", "sysv"):
         solve = op in ("gesv", "sysv")

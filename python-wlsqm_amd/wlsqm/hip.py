@@ -1412,7 +1412,7 @@ class StencilOperator:
 
     def __init__(self, dimension, order, S, hoods, nk, knowns, weighting_method, rows, point_index=None, stream=None):
         import torch
-        self._m = self._t = self._tval = None
+        self._m = self._t = self._tval = self._tpair = None
         no = _adjoint_order(dimension, order)
         ncases, K = _cloud_geometry(dimension, S, hoods, nk, knowns, weighting_method, point_index,
                                     "S must be contiguous; hoods must have a contiguous last axis")
@@ -1441,8 +1441,13 @@ class StencilOperator:
             pts = point_index[:ncases].long() if point_index is not None else torch.arange(ncases, device=device)
             self._pack(hoods[:ncases], nk[:ncases], slots, own, fknown, pts, npoints)
             self.known_coef = gfi
-            self.has_known_derivatives = bool((gfi != 0).any())
+            # what update() answers from the masks alone: some DOF other than an F that went into the matrix is known or dropped
+            full = (1 << no) - 1
+            low = knowns[:ncases] & full
+            structural = ((low & ~1) != 0) | (((knowns[:ncases] & ~full) != 0) & (low != full))
+            self.has_known_derivatives, self._structural = torch.stack([(gfi != 0).any(), structural.any()]).tolist()
         self.dimension, self.order, self.no = int(dimension), int(order), no
+        self._geo, self._rows = (hoods, nk, knowns, weighting_method, point_index), rows
 
     @classmethod
     def from_coefficients(cls, hoods, nk, slots, npoints, own=None, own_mask=None, point_index=None, stream=None):
@@ -1452,7 +1457,7 @@ class StencilOperator:
         looked at: the padding of hoods and slots may hold anything.  Synchronises."""
         import torch
         self = cls.__new__(cls)
-        self._m = self._t = self._tval = None
+        self._m = self._t = self._tval = self._tpair = None
         _check(hoods, "hoods", "int32", 2); _check(nk, "nk", "int32", 1)
         ncases, K = int(hoods.shape[0]), int(hoods.shape[1])
         _rows(ncases, nk=nk)
@@ -1478,6 +1483,7 @@ class StencilOperator:
             self._pack(hoods, nk[:ncases], slots[:, :ncases, :K], own[:nop, :ncases] if own is not None else None,
                        own_mask[:ncases] if own_mask is not None else None, pts, int(npoints))
         self.known_coef, self.has_known_derivatives = None, False
+        self._geo = self._rows = None
         self.dimension = self.order = None
         self.no = 0
         return self
@@ -1520,15 +1526,90 @@ class StencilOperator:
 
     def close(self):
         """Release the device memory now; harmless when called again."""
-        self._m = self._t = self._val = self._tval = self._nk = self._own_mask = self.known_coef = None
+        self._m = self._t = self._val = self._tval = self._tpair = self._nk = self._own_mask = self.known_coef = None
+        self._geo = self._rows = None
 
     def memory_used(self):
-        """Bytes of device memory the operator holds (the transposed matrix included once built)."""
+        """Bytes of device memory the operator holds (the transposed matrix included once built, with the index pair that update()
+        refreshes its values through).  The caller's hoods, nk, knowns, weighting_method, point_index and rows, which the operator
+        references for update(), are not counted."""
         self._live()
         held = list(self._m.values()) + [self._val, self._nk, self._own_mask, self.known_coef]
         if self._t is not None:
-            held += list(self._t.values()) + [self._tval]
+            held += list(self._t.values()) + [self._tval, getattr(self, "_tpair", None)]
         return sum(t.numel() * t.element_size() for t in held if hasattr(t, "numel"))
+
+    def update(self, S, hoods=None, rows=None, check=True, stream=None):
+        """Recompute every value plane, the own entries and known_coef for the points where they are now, S (>= npoints rows, as the
+        constructor takes it), into the arrays the operator already holds: the constructor's coefficients on the new geometry (its
+        bits for the systems up to 10 unknowns), by one fused kernel (csrc/fit_adjoint.hip, "stencil-build": one factorisation per case
+        for all operators).  The operator keeps references to the hoods, nk, knowns, weighting_method, point_index and rows it was
+        built with (not to S) and reads them here: the caller must not resize or free them.
+
+        rows: new operators, the same nop and the same (nop, no) or (nop, ncases, no) form.  hoods: new neighbour lists of the same
+        shape and dtype for the same nk (a fixed-k search redone); the columns are rewritten and a transposed matrix built for the old
+        ones is dropped (fill_transposed is None again, the next transposed use rebuilds it).  Without new hoods a built transposed
+        matrix has its values refreshed by a second kernel.  Changing nk or knowns needs a new operator.
+
+        check=True verifies that every live index is in 0 .. npoints - 1 before anything is enqueued (torch operations, one host read;
+        ValueError as the constructor's; RuntimeError inside a graph capture).  check=False enqueues kernels only: no allocation, no
+        synchronisation, at most two launches on `stream`, so update + apply can be captured and replayed after S.copy_(...).
+        Afterwards has_known_derivatives is structural: true iff some case has a known or dropped DOF other than an F that went into
+        the matrix, whatever the values of rows (the constructor's answer looks at the coefficients, and may be False where this is
+        True).  RuntimeError for an operator from from_coefficients (no fit to redo) or a closed one."""
+        m = self._live()
+        if getattr(self, "_geo", None) is None:
+            raise RuntimeError("the stencil operator was made from coefficients: there is no fit to redo")
+        old_hoods, nk, knowns, weighting_method, point_index = self._geo
+        new_hoods = old_hoods if hoods is None else hoods
+        if not hasattr(S, "dim") or not hasattr(S, "is_cuda"):
+            raise ValueError("argument S must be a device (HIP) tensor")
+        if hoods is not None:
+            _check(hoods, "hoods", "int32", 2)
+            if tuple(hoods.shape) != (self.ncases, self.K):
+                raise ValueError("hoods must be (%d, %d) int32 as the operator was built with; got %s: another shape needs a new operator"
+                                 % (self.ncases, self.K, tuple(hoods.shape)))
+        ncases, K = _cloud_geometry(self.dimension, S, new_hoods, nk, knowns, weighting_method, point_index,
+                                    "S must be contiguous; hoods must have a contiguous last axis")
+        if S.shape[0] < self.npoints:
+            raise ValueError("S has fewer points than the operator's npoints = %d" % self.npoints)
+        new_rows = self._rows if rows is None else rows
+        per_case = self._rows.dim() == 3
+        if rows is not None:
+            if not hasattr(rows, "dim") or rows.dim() != self._rows.dim() or rows.shape[0] != self.nop:
+                raise ValueError("rows must keep the operator's form, %s with nop = %d"
+                                 % ("(nop, ncases, no)" if per_case else "(nop, no)", self.nop))
+            _double_rows(rows, "rows", ncases if per_case else 1, self.no, (self.dimension, self.order), lead=1 if per_case else 0)
+        _same_device(self._val, S, new_hoods, new_rows)
+        s, dev = _stream_and_device(S, stream)
+        if check:
+            import torch
+            with _torch_stream(stream, self._device):
+                if self._device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("update checks the indices with a host read and the stream is capturing: pass check=False inside the capture")
+                live = torch.arange(K, device=self._device)[None, :] < self._nk[:, None]
+                cols = new_hoods[:ncases][live]
+                bad = ((cols < 0) | (cols >= self.npoints)).any()
+                if self._own_mask is not None:
+                    pts = point_index[:ncases][self._own_mask] if point_index is not None else None
+                    if pts is not None:
+                        bad = bad | ((pts < 0) | (pts >= self.npoints)).any()
+                if bool(bad):
+                    raise ValueError("a live entry names a point outside 0 .. npoints - 1 = %d" % (self.npoints - 1))
+        B.check(B.lib().wlsqm_hip_stencil_build_device(
+            self.dimension, self.order, ncases, K, _ptr(S), _ptr(new_hoods), int(new_hoods.stride(0)), _ptr(point_index), _ptr(nk),
+            _ptr(knowns), _ptr(weighting_method), _ptr(new_rows), int(new_rows.stride(0)), int(new_rows.stride(1)) if per_case else 0,
+            self.nop, _ptr(m["len"]), _ptr(m["soff"]), _ptr(m["col"]) if hoods is not None else None, _ptr(self._val), m["total"],
+            _ptr(self.known_coef), int(self.known_coef.stride(0)), int(self.known_coef.stride(1)), dev, s))
+        tpair = getattr(self, "_tpair", None)
+        if hoods is not None or tpair is None:
+            self._t = self._tval = self._tpair = None       # built for other columns (or too large for the pair): rebuilt at the next use
+        elif self._t is not None:
+            B.check(B.lib().wlsqm_hip_sell_permute_device(int(tpair.shape[1]), _ptr(tpair[0]), _ptr(tpair[1]),
+                                                          _ptr(self._val), m["total"], _ptr(self._tval), self._t["total"], self.nop, dev, s))
+        self._geo, self._rows = (new_hoods, nk, knowns, weighting_method, point_index), new_rows
+        self.has_known_derivatives = self._structural
+        return self
 
     @property
     def fill(self):
@@ -1648,6 +1729,9 @@ class StencilOperator:
             tval[:, dest] = self._val[:, src[order]]
             self._t = dict(nrows=self.npoints, len=len32, width=width, soff=soff, col=tcol, total=total)
             self._tval = tval
+            # (dest, src) of every live entry, for update(): one 8-byte pair per entry; positions beyond int32 go without (update then
+            # drops the transposed matrix and the next use rebuilds it)
+            self._tpair = torch.stack([dest, src[order]]).to(torch.int32) if max(total, m["total"]) < 2 ** 31 else None
         return True
 
     def apply_transpose(self, g, out=None, alpha=1.0, beta=0.0, stream=None):
@@ -1713,7 +1797,8 @@ def differentiable_stencil_apply(op, F, known=None, stream=None):
     with a grad_fn.  The backward pass is op.apply_transpose (the same kernel on the transposed matrix, no atomics), computed only
     when F requires a gradient; dL/dF has F's full shape, zeros beyond the operator's points.  `known` receives the
     known_coef-weighted gradients.  Call op.prepare_transpose() first when the backward pass is to be captured into a graph.
-    Once differentiable."""
+    The backward pass reads the operator as it is then: an op.update between forward and backward invalidates the graph, as any
+    in-place change of a saved tensor does (it is not detected).  Once differentiable."""
     op._apply_args(F, known)                       # before anything is detached
     return _autograd().StencilApply.apply(F, known, op, stream)
 
