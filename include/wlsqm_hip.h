@@ -569,6 +569,40 @@ int wlsqm_hip_stencil_build_device(int dimension, int order, int64_t ncases, int
 int wlsqm_hip_sell_permute_device(int64_t n, const int32_t* dest, const int32_t* src, const double* in, int64_t in_stride_op,
                                   double* out, int64_t out_stride_op, int nop, int device, void* stream);
 
+/* ---- implicit solves with a stencil operator (extension; csrc/krylov.hip) ----
+ * BiCGSTAB on M x = b, M = diag(d) + scale * A, A one value plane of a SQUARE matrix in the SELL-64 layout above (nrows == ncols, row i
+ * the equation of point i; `val` points at the plane), d_i = diag[i] or, with diag == NULL, diag_const.  jacobi != 0: right-preconditioned
+ * with the inverse of M's diagonal, d_i + scale * (the sum of row i's entries in column i, in entry order), recomputed by every start.
+ * All state lives in `workspace`, wlsqm_hip_krylov_workspace_bytes(nrows) bytes of device memory, 8-byte aligned, which the caller keeps
+ * from start to the last read; b, x, diag and the workspace must not overlap.  Its first 128 bytes are the scalars:
+ *   double rho, rho_old, alpha, omega, rr, stop, dot0, dot1;  int32 iterations, status, done, maxiter;
+ * rr = (r, r) of the recursive residual, stop = max(rtol * ||b||_2, atol), the solve stops when sqrt(rr) <= stop.  status: -1 running,
+ * 0 converged, 1 iteration limit, 2 breakdown (rho == 0 or (r0, v) == 0), 3 a non-finite scalar, 4 a zero or non-finite Jacobi diagonal
+ * (found before the first iteration: x stays as given).  Every status >= 0 sets `done`, and every kernel returns at its head when `done`
+ * is set: iterations enqueued behind a stopped solve leave x and the scalars untouched.  b == 0 with x == 0 converges at 0 iterations
+ * without a division; (t, t) == 0 takes omega = 0.  The padding of col and val and rows beyond nrows are neither read nor written.
+ * Every dot product is summed in a fixed order without atomics: the bits of x and of the scalars are a function of the arguments.
+ * The calls do nothing but kernel launches on `stream` (wlsqm_hip_last_kernel(): "krylov-diag", "krylov-spmv-dot", "krylov-update",
+ * "krylov-reduce"): no allocation, no synchronisation, no host state.  WLSQM_EVALUE for nrows < 1, nrows > 64 * nslices, a null array,
+ * rtol or atol negative or not finite, maxiter or niter negative.
+ *
+ * wlsqm_hip_krylov_start_device: the Jacobi diagonal, r = r0 = b - M x, the scalars and the threshold (at most 4 launches).
+ * wlsqm_hip_krylov_bicgstab_device: `niter` iterations behind a start with the same arguments, 8 launches each; the solve stops by
+ *   itself at convergence, at the start's maxiter or at a breakdown.
+ * wlsqm_hip_krylov_product_device: the solve's fused product on its own, out = M in with dot0 = (out, w) and dot1 = (out, out) left in
+ *   the scalars (2 launches; it uses the workspace's partial sums, so not between a start and the end of its solve). */
+int64_t wlsqm_hip_krylov_workspace_bytes(int64_t nrows);
+int wlsqm_hip_krylov_start_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                  const int32_t* col, const double* val, const double* diag, double diag_const, double scale, int jacobi,
+                                  const double* b, const double* x, double rtol, double atol, int64_t maxiter, void* workspace,
+                                  int device, void* stream);
+int wlsqm_hip_krylov_bicgstab_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                     const int32_t* col, const double* val, const double* diag, double diag_const, double scale, int jacobi,
+                                     double* x, int64_t niter, void* workspace, int device, void* stream);
+int wlsqm_hip_krylov_product_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                    const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                    const double* in, const double* w, double* out, void* workspace, int device, void* stream);
+
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ---- */
 /* Runs `reps` back-to-back launches of the fit kernel for batch `b` (device-resident, uniform
  * order) on `stream`, bracketed by HIP events on that stream; returns the mean kernel time in

@@ -190,6 +190,17 @@ def lib():
         L.wlsqm_hip_sell_permute_device.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
                                                     C.c_int, C.c_void_p]
         L.wlsqm_hip_sell_permute_device.restype = C.c_int
+    # implicit solves with a stencil operator (wlsqm.hip.StencilSolver): BiCGSTAB resident on the device
+    if hasattr(L, "wlsqm_hip_krylov_start_device"):                  # (older builds of the library, as above)
+        system = [C.c_int64, C.c_int64] + [C.c_void_p] * 6 + [C.c_double, C.c_double]     # the SELL-64 arrays, diag, diag_const, scale
+        L.wlsqm_hip_krylov_workspace_bytes.argtypes = [C.c_int64]
+        L.wlsqm_hip_krylov_workspace_bytes.restype = C.c_int64
+        L.wlsqm_hip_krylov_start_device.argtypes = system + [C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int64, C.c_void_p,
+                                                             C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_bicgstab_device.argtypes = system + [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_product_device.argtypes = system + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        for name in ("start", "bicgstab", "product"):
+            getattr(L, "wlsqm_hip_krylov_%s_device" % name).restype = C.c_int
     # batched dense solves (wlsqm.utils.lapackdrivers, wlsqm.hip.*_batched)
     for op in ("getrf", "gesv", "sytrf", "sysv"):
         solve = op in ("gesv", "sysv")

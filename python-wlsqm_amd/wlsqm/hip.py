@@ -10,6 +10,7 @@ import ctypes as C
 
 from . import _binding as B
 
+import collections
 import contextlib
 
 __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_cloud_device", "device_count", "knn", "ball", "nearest",
@@ -17,7 +18,7 @@ __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_c
            "fit_cloud_geometry_adjoint_device", "differentiable_fit_many", "differentiable_fit_cloud",
            "differentiable_solve", "differentiable_solve_many",
            "InterpolationPlan", "differentiable_evaluate",
-           "StencilOperator", "stencil_rows", "differentiable_stencil_apply",
+           "StencilOperator", "stencil_rows", "differentiable_stencil_apply", "StencilSolver", "SolveInfo",
            "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
            "getrf_batched", "getrs_batched", "gesv_batched", "sytrf_batched", "sytrs_batched", "sysv_batched", "symmetrize_batched"]
 
@@ -1448,6 +1449,7 @@ class StencilOperator:
             self.has_known_derivatives, self._structural = torch.stack([(gfi != 0).any(), structural.any()]).tolist()
         self.dimension, self.order, self.no = int(dimension), int(order), no
         self._geo, self._rows = (hoods, nk, knowns, weighting_method, point_index), rows
+        self._point_index = point_index
 
     @classmethod
     def from_coefficients(cls, hoods, nk, slots, npoints, own=None, own_mask=None, point_index=None, stream=None):
@@ -1484,6 +1486,7 @@ class StencilOperator:
                        own_mask[:ncases] if own_mask is not None else None, pts, int(npoints))
         self.known_coef, self.has_known_derivatives = None, False
         self._geo = self._rows = None
+        self._point_index = point_index
         self.dimension = self.order = None
         self.no = 0
         return self
@@ -1527,7 +1530,7 @@ class StencilOperator:
     def close(self):
         """Release the device memory now; harmless when called again."""
         self._m = self._t = self._val = self._tval = self._tpair = self._nk = self._own_mask = self.known_coef = None
-        self._geo = self._rows = None
+        self._geo = self._rows = self._point_index = None
 
     def memory_used(self):
         """Bytes of device memory the operator holds (the transposed matrix included once built, with the index pair that update()
@@ -1801,6 +1804,194 @@ def differentiable_stencil_apply(op, F, known=None, stream=None):
     in-place change of a saved tensor does (it is not detected).  Once differentiable."""
     op._apply_args(F, known)                       # before anything is detached
     return _autograd().StencilApply.apply(F, known, op, stream)
+
+
+SolveInfo = collections.namedtuple("SolveInfo", "status iterations residual")
+SolveInfo.__doc__ = """What a StencilSolver says of a solve.  status: 0 converged, 1 iteration limit, 2 breakdown (rho = 0 or (r0, v) = 0),
+3 a non-finite scalar, 4 a zero or non-finite Jacobi diagonal, -1 still running (enqueue with fewer iterations than the solve needs
+always ends in 1).  iterations: those completed.  residual: the recursive ||r||_2 (NaN with status 4: no residual was formed)."""
+
+
+class StencilSolver:
+    """Solves M x = b with M = diag(d) + scale * A_o, A_o value plane `o` of a square StencilOperator, by BiCGSTAB resident on the
+    device (csrc/krylov.hip): eight kernel launches per iteration, two passes over the matrix, every dot product
+    formed in the pass that produces its vector, no host synchronisation inside `enqueue`.  The bits of x, of the iteration count and
+    of the residual are a function of the operator, diag, scale, b, x and the tolerances: no atomics, eager and captured runs agree.
+
+    op: square — ncases == npoints, row j the equation of point j (point_index None or the identity; checked here with one host read,
+    ValueError) — not closed, and without known derivatives (their affine term belongs in b).  The solver reads the operator's arrays
+    at every solve: after op.update(...) it solves with the new values, and nothing has to be called on the solver.
+    diag: a float, or a contiguous float64 device tensor (npoints,) that is read at every solve (the caller may change it in place).
+    preconditioner: "jacobi" (the inverse of M's diagonal, recomputed at the start of every solve) or None.
+    All workspace, 9 npoints + 2 ceil(npoints / 256) + 16 doubles, is allocated here; close() releases it."""
+
+    def __init__(self, op, o=0, diag=1.0, scale=1.0, preconditioner="jacobi"):
+        self._ws = None
+        if not isinstance(op, StencilOperator):
+            raise ValueError("op must be a StencilOperator")
+        op._live()
+        if op.ncases != op.npoints:
+            raise ValueError("the operator must be square: it has %d rows (cases) for %d points" % (op.ncases, op.npoints))
+        if op.has_known_derivatives:
+            raise ValueError("the operator depends on known DOFs other than F: their affine term belongs in b, build the operator without them")
+        if not 0 <= int(o) < op.nop:
+            raise ValueError("the operator has %d value planes; got o = %d" % (op.nop, int(o)))
+        if preconditioner not in ("jacobi", None):
+            raise ValueError("preconditioner must be 'jacobi' or None; got %r" % (preconditioner,))
+        self._op, self._o, self._jacobi = op, int(o), 1 if preconditioner == "jacobi" else 0
+        self.npoints, self._device = op.npoints, op._device
+        self.scale = float(scale)
+        if hasattr(diag, "dim"):
+            self._vector(diag, "diag")
+            self.diag = diag
+        else:
+            self.diag = float(diag)
+        import torch
+        pi = getattr(op, "_point_index", None)
+        if pi is not None and not bool((pi[:op.ncases].long() == torch.arange(op.ncases, device=pi.device)).all()):
+            raise ValueError("row j of the operator must be the equation of point j: point_index must be None or the identity")
+        nbytes = int(B.lib().wlsqm_hip_krylov_workspace_bytes(self.npoints))
+        self._ws = torch.zeros((nbytes // 8,), dtype=torch.float64, device=self._device)
+
+    def _live(self):
+        if getattr(self, "_ws", None) is None:
+            raise RuntimeError("the stencil solver has been closed")
+        return self._op._live()
+
+    def close(self):
+        """Release the workspace now; harmless when called again.  The operator stays the caller's."""
+        self._ws = self._op = None
+        if hasattr(self.__dict__.get("diag"), "dim"):
+            self.diag = None
+
+    def memory_used(self):
+        """Bytes of device memory the solver holds (the operator's and a diag tensor are the caller's)."""
+        self._live()
+        return self._ws.numel() * self._ws.element_size()
+
+    def _vector(self, t, name):
+        if not hasattr(t, "dim") or not hasattr(t, "is_cuda"):
+            raise ValueError("argument %s must be a device (HIP) tensor" % name)
+        _check(t, name, "float64", 1)
+        if tuple(t.shape) != (self.npoints,) or (self.npoints > 1 and t.stride(0) != 1):
+            raise ValueError("%s must be a contiguous float64 device tensor of shape (%d,); got shape %s with strides %s"
+                             % (name, self.npoints, tuple(t.shape), tuple(t.stride())))
+        if t.device != self._device:
+            raise ValueError("all tensors must be on the same device")
+
+    def _vectors(self, **named):
+        """The checks of the vectors of a call: each one (npoints,) float64 contiguous on the operator's device, none overlapping
+        another, the diag tensor or the workspace."""
+        self._live()
+        for name, t in named.items():
+            self._vector(t, name)
+        held = dict(named, workspace=self._ws)
+        if hasattr(self.diag, "dim"):
+            held["diag"] = self.diag
+        names = list(held)
+        for i, a in enumerate(names):
+            for b in names[i + 1:]:
+                if a in named and _overlap(held[a], held[b]):
+                    raise ValueError("%s overlaps %s in memory" % (a, b))
+
+    @staticmethod
+    def _tolerances(rtol, atol, maxiter):
+        rtol, atol, maxiter = float(rtol), float(atol), int(maxiter)
+        if not (0.0 <= rtol < float("inf")) or not (0.0 <= atol < float("inf")):
+            raise ValueError("rtol and atol must be finite and >= 0; got %r, %r" % (rtol, atol))
+        if not 0 <= maxiter < 2 ** 31:
+            raise ValueError("the number of iterations must be 0 .. 2^31 - 1; got %d" % maxiter)
+        return rtol, atol, maxiter
+
+    def _system(self):
+        m = self._op._m
+        d = self.diag
+        return (m["nrows"], int(m["width"].shape[0]), _ptr(m["len"]), _ptr(m["width"]), _ptr(m["soff"]), _ptr(m["col"]),
+                C.c_void_p(self._op._val.data_ptr() + 8 * self._o * m["total"]), _ptr(d) if hasattr(d, "dim") else None,
+                0.0 if hasattr(d, "dim") else d, self.scale)
+
+    def _no_capture(self, what, stream):
+        import torch
+        with _torch_stream(stream, self._device):
+            if self._device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("%s reads the solve's scalars on the host and the stream is capturing: use enqueue inside the capture "
+                                   "and info() after the replay" % what)
+
+    def _start(self, b, x, rtol, atol, maxiter, dev, s):
+        B.check(B.lib().wlsqm_hip_krylov_start_device(*self._system(), self._jacobi, _ptr(b), _ptr(x), rtol, atol, maxiter, _ptr(self._ws),
+                                                      dev, s))
+
+    def _iterate(self, x, niter, dev, s):
+        B.check(B.lib().wlsqm_hip_krylov_bicgstab_device(*self._system(), self._jacobi, _ptr(x), niter, _ptr(self._ws), dev, s))
+
+    def enqueue(self, b, x, iterations, rtol=1e-10, atol=0.0, stream=None):
+        """The start of a solve and `iterations` iterations, as kernel launches on `stream` (default: torch's current stream) and nothing
+        else: no allocation, no host read, so it can be captured into a graph, also behind op.update(S, check=False).  The solve stops
+        by itself, on the device, at ||r|| <= max(rtol ||b||, atol), after `iterations` (status 1) or at a breakdown; what is enqueued
+        behind the stop leaves x and the scalars untouched.  x (npoints,) holds the initial guess and receives the solution.
+        info() tells later how it went."""
+        self._vectors(b=b, x=x)
+        rtol, atol, iterations = self._tolerances(rtol, atol, iterations)
+        s, dev = _stream_and_device(x, stream)
+        self._start(b, x, rtol, atol, iterations, dev, s)
+        self._iterate(x, iterations, dev, s)
+        return self
+
+    def _read(self, what, stream):
+        """(SolveInfo, done) from the scalars: one read of 128 bytes, which synchronises with the stream."""
+        self._live()
+        self._no_capture(what, stream)
+        with _torch_stream(stream, self._device):
+            head = self._ws[:16].cpu().numpy()
+        ints = head[8:10].view("int32")
+        return SolveInfo(int(ints[1]), int(ints[0]), float(head[4]) ** 0.5), bool(ints[2])
+
+    def info(self, stream=None):
+        """SolveInfo of the last solve enqueued on `stream`: one read of 128 bytes, which synchronises with that stream (RuntimeError
+        inside a graph capture)."""
+        return self._read("info", stream)[0]
+
+    def solve(self, b, x, rtol=1e-10, atol=0.0, maxiter=1000, check_every=8, stream=None):
+        """x <- the solution of M x = b from the initial guess in x; returns SolveInfo(status, iterations, residual).  Enqueues
+        `check_every` iterations, reads the scalars (one synchronisation) and repeats, up to `maxiter` iterations in all.  The stop is
+        taken on the device after every iteration, so `iterations` is exact whatever check_every is; with check_every=1 no launch is
+        enqueued behind the stop either.  RuntimeError inside a graph capture."""
+        self._vectors(b=b, x=x)
+        rtol, atol, maxiter = self._tolerances(rtol, atol, maxiter)
+        check_every = int(check_every)
+        if check_every < 1:
+            raise ValueError("check_every must be >= 1; got %d" % check_every)
+        self._no_capture("solve", stream)
+        s, dev = _stream_and_device(x, stream)
+        self._start(b, x, rtol, atol, maxiter, dev, s)
+        left = maxiter
+        while True:
+            n = min(check_every, left)
+            self._iterate(x, n, dev, s)
+            left -= n
+            info, done = self._read("solve", stream)
+            if done or left == 0:
+                return info
+
+    def product(self, v, w=None, out=None, stream=None):
+        """(M v, (M v, w), (M v, M v)): the solve's own fused product and the dot products of its pass (w default v), for checks and
+        for residuals.  One host read of the two sums; not between an enqueue and the end of its solve."""
+        import torch
+        self._live()
+        self._no_capture("product", stream)
+        w = v if w is None else w
+        if out is None:
+            with _torch_stream(stream, self._device):
+                out = torch.empty((self.npoints,), dtype=torch.float64, device=self._device)
+        if w is v:
+            self._vectors(v=v, out=out)
+        else:
+            self._vectors(v=v, w=w, out=out)
+        s, dev = _stream_and_device(v, stream)
+        B.check(B.lib().wlsqm_hip_krylov_product_device(*self._system(), _ptr(v), _ptr(w), _ptr(out), _ptr(self._ws), dev, s))
+        with _torch_stream(stream, self._device):
+            head = self._ws[:16].cpu().numpy()
+        return out, float(head[6]), float(head[7])
 
 
 # ---- batched dense solves (the kernels behind wlsqm.utils.lapackdrivers), device-resident ----
