@@ -590,7 +590,15 @@ int wlsqm_hip_sell_permute_device(int64_t n, const int32_t* dest, const int32_t*
  * wlsqm_hip_krylov_bicgstab_device: `niter` iterations behind a start with the same arguments, 8 launches each; the solve stops by
  *   itself at convergence, at the start's maxiter or at a breakdown.
  * wlsqm_hip_krylov_product_device: the solve's fused product on its own, out = M in with dot0 = (out, w) and dot1 = (out, out) left in
- *   the scalars (2 launches; it uses the workspace's partial sums, so not between a start and the end of its solve). */
+ *   the scalars (2 launches; it uses the workspace's partial sums, so not between a start and the end of its solve).
+ * wlsqm_hip_krylov_grads_device ("krylov-grads"): the gradients of a loss L through the solve, from x and the
+ *   solution lam of M^T lam = dL/dx, in one pass over the forward matrix.  Each output is optional (NULL / 0):
+ *     grad_val (total doubles, one plane in the layout of `val`): -((scale * lam[j]) * x[col]) at every live entry of row j, two
+ *       roundings; +0.0 in every padding position, the lanes of rows beyond nrows included;
+ *     grad_diag (nrows): -(lam[j] * x[j]);
+ *     want_scale: dot0 of the scalars = -(lam, A x), the row sums those of the product, summed in the fixed order of the dot products.
+ *   One launch, and the reduce when want_scale is set; not between a start and the end of its solve.  lam, x and the outputs must not
+ *   overlap.  WLSQM_EVALUE as above, for a null lam or x, and when no output is asked for. */
 int64_t wlsqm_hip_krylov_workspace_bytes(int64_t nrows);
 int wlsqm_hip_krylov_start_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
                                   const int32_t* col, const double* val, const double* diag, double diag_const, double scale, int jacobi,
@@ -602,6 +610,10 @@ int wlsqm_hip_krylov_bicgstab_device(int64_t nrows, int64_t nslices, const int32
 int wlsqm_hip_krylov_product_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
                                     const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
                                     const double* in, const double* w, double* out, void* workspace, int device, void* stream);
+int wlsqm_hip_krylov_grads_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                  const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                  const double* lam, const double* x, double* grad_val, double* grad_diag, int want_scale,
+                                  void* workspace, int device, void* stream);
 
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ---- */
 /* Runs `reps` back-to-back launches of the fit kernel for batch `b` (device-resident, uniform

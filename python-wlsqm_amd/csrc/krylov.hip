@@ -19,7 +19,7 @@ namespace wlsqm {
 struct KrylovScalars {              // 128 bytes at the head of the workspace; wlsqm/hip.py reads it as 8 doubles and 4 int32
     double rho, rho_old, alpha, omega;
     double rr, stop;                // (r, r) of the recursive residual; the threshold max(rtol ||b||, atol) on its root
-    double dot0, dot1;              // wlsqm_hip_krylov_product_device's results
+    double dot0, dot1;              // wlsqm_hip_krylov_product_device's results; dot0 also wlsqm_hip_krylov_grads_device's dL/dscale
     int iterations, status, done, maxiter;
     double pad[6];
 };
@@ -158,6 +158,66 @@ __global__ void __launch_bounds__(256) krylov_diag_kernel(const KrylovSys m, dou
     block_sums<false>(bad, 0.0, partial, gridDim.x);
 }
 
+// The gradients of a loss through the solve M x = b, lam the solution of M^T lam = dL/dx, in one pass over the
+// forward matrix with krylov_spmv_kernel's mapping.  Each output is a template flag, so a pass without SCALE never loads val and a
+// pass without VALUES never stores into a plane:
+//   VALUES: gval[at + 64 e] = -(t * x[col]) with t = c * lam_j, two roundings, for the live entries of row j; +0.0 in every padding
+//           position of the slice, the lanes of rows beyond nrows included (their padding col is never loaded)
+//   DIAG:   gdiag[j] = -(lam_j * x_j)
+//   SCALE:  the workgroup's partial of sum_j lam_j * (row j of A) x, the row sum krylov_row_sum's bits (the same fma chain)
+template <bool VALUES, bool DIAG, bool SCALE>
+__global__ void __launch_bounds__(256) krylov_grads_kernel(const KrylovSys m, const double* lam, const double* x, double* gval,
+                                                           double* gdiag, double* partial) {
+    const int lane = threadIdx.x & 63;
+    const long long s = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long row = s * 64 + lane;
+    double a = 0.0;
+    if (s * 64 < m.nrows) {                                      // wave-uniform
+        const bool live = row < m.nrows;
+        const double lj = live ? lam[row] : 0.0;
+        if (DIAG && live) gdiag[row] = -(lj * x[row]);
+        if (VALUES || SCALE) {
+            constexpr int UNROLL = 8;
+            const int wid = __builtin_amdgcn_readfirstlane(m.width[s]);
+            const long long at = m.soff[s] + lane;
+            int n = live ? m.len[row] : 0;
+            n = n < wid ? n : wid;
+            const int32_t* col = m.col + at;
+            const double* val = m.val + at;
+            double* out = gval + at;
+            const double t = m.c * lj;
+            double acc = 0.0;
+            for (int e = 0; e < wid; e += UNROLL) {              // wave-uniform
+                if (e + UNROLL <= n) {
+                    double xs[UNROLL], vs[UNROLL];
+#pragma unroll
+                    for (int u = 0; u < UNROLL; ++u) {
+                        xs[u] = x[col[64LL * (e + u)]];
+                        if (SCALE) vs[u] = val[64LL * (e + u)];
+                    }
+#pragma unroll
+                    for (int u = 0; u < UNROLL; ++u) {
+                        if (VALUES) out[64LL * (e + u)] = -(t * xs[u]);
+                        if (SCALE) acc = __builtin_fma(vs[u], xs[u], acc);
+                    }
+                } else {
+                    for (int u = 0; u < UNROLL && e + u < wid; ++u) {
+                        if (e + u < n) {
+                            const double xv = x[col[64LL * (e + u)]];
+                            if (VALUES) out[64LL * (e + u)] = -(t * xv);
+                            if (SCALE) acc = __builtin_fma(val[64LL * (e + u)], xv, acc);
+                        } else if (VALUES) {
+                            out[64LL * (e + u)] = 0.0;
+                        }
+                    }
+                }
+            }
+            if (SCALE) a = lj * acc;
+        }
+    }
+    if (SCALE) block_sums<false>(a, 0.0, partial, gridDim.x);
+}
+
 enum { UPDATE_P = 0, UPDATE_S = 1, UPDATE_X = 2 };
 
 //   UPDATE_P: p = r + beta (p - omega v) (the first iteration: p = r), phat = dinv p
@@ -194,14 +254,14 @@ __global__ void __launch_bounds__(256) krylov_update_kernel(long long nrows, con
     }
 }
 
-enum { REDUCE_DIAG = 0, REDUCE_RESIDUAL = 1, REDUCE_ALPHA = 2, REDUCE_OMEGA = 3, REDUCE_RHO = 4, REDUCE_PRODUCT = 5 };
+enum { REDUCE_DIAG = 0, REDUCE_RESIDUAL = 1, REDUCE_ALPHA = 2, REDUCE_OMEGA = 3, REDUCE_RHO = 4, REDUCE_PRODUCT = 5, REDUCE_NEGATED = 6 };
 
 __device__ __forceinline__ void krylov_stop(KrylovScalars* sc, int status) { sc->status = status; sc->done = 1; }
 
 // One workgroup: the partials of both planes in index order (thread t takes t, t + 256, ...), then the scalar step of `mode` in one lane.
 __global__ void __launch_bounds__(256) krylov_reduce_kernel(int mode, const double* partial, long long nwg, int planes, KrylovScalars* sc,
                                                             double rtol, double atol, int maxiter) {
-    if (mode != REDUCE_DIAG && mode != REDUCE_PRODUCT && sc->done) return;      // uniform
+    if (mode != REDUCE_DIAG && mode != REDUCE_PRODUCT && mode != REDUCE_NEGATED && sc->done) return;      // uniform
     __shared__ double sums[2];
     double a = 0.0, b = 0.0;
     for (long long i = threadIdx.x; i < nwg; i += 256) {
@@ -254,6 +314,9 @@ __global__ void __launch_bounds__(256) krylov_reduce_kernel(int mode, const doub
         else if (!__builtin_isfinite((s0 / rho_old) * (sc->alpha / sc->omega))) krylov_stop(sc, KRYLOV_NONFINITE);   // the next beta
         break;
     }
+    case REDUCE_NEGATED:                                         // krylov_grads_kernel's sum: dL/dscale = -(lam, A x)
+        sc->dot0 = -s0;
+        break;
     default:                                                     // REDUCE_PRODUCT
         sc->dot0 = s0; sc->dot1 = s1;
         break;
@@ -277,6 +340,12 @@ static int krylov_system(const char* who, KrylovSys& m, int64_t nrows, int64_t n
 
 static void krylov_reduce(int mode, const KrylovWork& w, long long nwg, int planes, double rtol, double atol, int maxiter, hipStream_t stream) {
     hipLaunchKernelGGL(krylov_reduce_kernel, dim3(1), dim3(256), 0, stream, mode, (const double*)w.partial, nwg, planes, w.sc, rtol, atol, maxiter);
+}
+
+template <bool VALUES, bool DIAG, bool SCALE>
+static void krylov_grads_launch(const KrylovSys& m, const KrylovWork& k, const double* lam, const double* x, double* gval, double* gdiag,
+                                hipStream_t s) {
+    hipLaunchKernelGGL((krylov_grads_kernel<VALUES, DIAG, SCALE>), dim3((unsigned)k.nwg), dim3(256), 0, s, m, lam, x, gval, gdiag, k.partial);
 }
 
 }  // namespace wlsqm
@@ -369,6 +438,35 @@ int wlsqm_hip_krylov_product_device(int64_t nrows, int64_t nslices, const int32_
     krylov_reduce(REDUCE_PRODUCT, k, k.nwg, 2, 0.0, 0.0, 0, s);
     WLSQM_HIP_CHECK(hipGetLastError());
     note_kernel("krylov-spmv-dot");
+    return WLSQM_OK;
+}
+
+int wlsqm_hip_krylov_grads_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                  const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                  const double* lam, const double* x, double* grad_val, double* grad_diag, int want_scale,
+                                  void* workspace, int device, void* stream) {
+    KrylovSys m;
+    int rc = krylov_system("krylov_grads", m, nrows, nslices, len, width, soff, col, val, diag, diag_const, scale, workspace);
+    if (rc != WLSQM_OK) return rc;
+    if (!lam || !x) { set_error("krylov_grads: null array"); return WLSQM_EVALUE; }
+    if (!grad_val && !grad_diag && !want_scale) { set_error("krylov_grads: no output is asked for"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const KrylovWork k = krylov_work(workspace, nrows, false);
+    switch ((grad_val ? 4 : 0) | (grad_diag ? 2 : 0) | (want_scale ? 1 : 0)) {
+    case 1: krylov_grads_launch<false, false, true>(m, k, lam, x, grad_val, grad_diag, s); break;
+    case 2: krylov_grads_launch<false, true, false>(m, k, lam, x, grad_val, grad_diag, s); break;
+    case 3: krylov_grads_launch<false, true, true>(m, k, lam, x, grad_val, grad_diag, s); break;
+    case 4: krylov_grads_launch<true, false, false>(m, k, lam, x, grad_val, grad_diag, s); break;
+    case 5: krylov_grads_launch<true, false, true>(m, k, lam, x, grad_val, grad_diag, s); break;
+    case 6: krylov_grads_launch<true, true, false>(m, k, lam, x, grad_val, grad_diag, s); break;
+    default: krylov_grads_launch<true, true, true>(m, k, lam, x, grad_val, grad_diag, s); break;
+    }
+    if (want_scale) krylov_reduce(REDUCE_NEGATED, k, k.nwg, 1, 0.0, 0.0, 0, s);
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-grads");
     return WLSQM_OK;
 }
 

@@ -201,6 +201,11 @@ def lib():
         L.wlsqm_hip_krylov_product_device.argtypes = system + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         for name in ("start", "bicgstab", "product"):
             getattr(L, "wlsqm_hip_krylov_%s_device" % name).restype = C.c_int
+    # the gradients through such a solve (StencilSolver.gradients)
+    if hasattr(L, "wlsqm_hip_krylov_grads_device"):
+        L.wlsqm_hip_krylov_grads_device.argtypes = ([C.c_int64, C.c_int64] + [C.c_void_p] * 6 + [C.c_double, C.c_double]
+                                                    + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p])
+        L.wlsqm_hip_krylov_grads_device.restype = C.c_int
     # batched dense solves (wlsqm.utils.lapackdrivers, wlsqm.hip.*_batched)
     for op in ("getrf", "gesv", "sytrf", "sysv"):
         solve = op in ("gesv", "sysv")

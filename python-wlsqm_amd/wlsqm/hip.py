@@ -19,6 +19,7 @@ __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_c
            "differentiable_solve", "differentiable_solve_many",
            "InterpolationPlan", "differentiable_evaluate",
            "StencilOperator", "stencil_rows", "differentiable_stencil_apply", "StencilSolver", "SolveInfo",
+           "SolveGradients", "differentiable_stencil_solve",
            "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
            "getrf_batched", "getrs_batched", "gesv_batched", "sytrf_batched", "sytrs_batched", "sysv_batched", "symmetrize_batched"]
 
@@ -631,7 +632,7 @@ _AUTOGRAD = None
 
 def _autograd():
     """The torch.autograd.Function classes behind the differentiable_* functions, as a namespace with FitMany, FitCloud, Solve,
-    Evaluate, FitManyGeometry and FitCloudGeometry (made at first use: the module does not import torch).  Every forward takes its tensor inputs first."""
+    Evaluate, FitManyGeometry, FitCloudGeometry, StencilApply and StencilSolve (made at first use: the module does not import torch).  Every forward takes its tensor inputs first."""
     global _AUTOGRAD
     if _AUTOGRAD is not None:
         return _AUTOGRAD
@@ -828,9 +829,88 @@ def _autograd():
                 return gF, gknown
             return gradients(ctx, gout, 2, adjoint)
 
+    class StencilSolve(torch.autograd.Function):
+        """StencilSolver.solve with b, the diag tensor, the point table and the coefficients among the differentiable inputs."""
+        @staticmethod
+        def forward(ctx, b, diag, S, slots, own, x0, solver, rtol, atol, maxiter, check_every, adjoint_rtol, stream):
+            op = solver._op
+            det = lambda t: t.detach() if t is not None else None
+            if S is not None:
+                op.update(S.detach(), stream=stream)
+            if slots is not None:
+                op.set_coefficients(slots.detach(), det(own), stream=stream)
+            with _torch_stream(stream, solver._device):
+                x = x0.detach().clone() if x0 is not None else torch.zeros((solver.npoints,), dtype=torch.float64, device=solver._device)
+            info = solver.solve(b.detach(), x, rtol=rtol, atol=atol, maxiter=maxiter, check_every=check_every, stream=stream)
+            if info.status != 0:
+                raise RuntimeError("the forward solve did not converge: status %d, %r" % (info.status, info))
+            ctx.save_for_backward(x, *(t for t in (S, slots, own) if t is not None))
+            ctx.call = (solver, S is not None, slots is not None, own is not None, adjoint_rtol if adjoint_rtol is not None else rtol,
+                        maxiter, check_every, stream)
+            return x
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gout):
+            def adjoint(g, need_b, need_diag, need_S, need_slots, need_own):
+                solver, has_S, has_slots, has_own, rtol, maxiter, check_every, stream = ctx.call
+                x, *made_from = ctx.saved_tensors
+                op, o, device = solver._op, solver._o, solver._device
+                solver._no_capture("the backward pass of differentiable_stencil_solve", stream)
+                if has_S:                                    # the operator back where the forward had it
+                    op.update(made_from[0].detach(), check=False, stream=stream)
+                elif has_slots:
+                    op.set_coefficients(made_from[0].detach(), made_from[1].detach() if has_own else None, stream=stream)
+                with _torch_stream(stream, device):
+                    lam = torch.zeros((solver.npoints,), dtype=torch.float64, device=device)
+                    x = x.detach()
+                info = solver.solve(g, lam, rtol=rtol, atol=0.0, maxiter=maxiter, check_every=check_every, stream=stream, transpose=True)
+                if info.status != 0:
+                    raise RuntimeError("the adjoint solve did not converge: status %d, %r" % (info.status, info))
+                gdiag = gS = gslots = gown = None
+                if need_diag or need_slots or need_own:
+                    got = solver.gradients(lam, x, values=need_slots or need_own, diag=need_diag, stream=stream)
+                    gdiag = got.diag
+                    if got.values is not None:
+                        with _torch_stream(stream, device):
+                            sl, ow = op.unpack(got.values)
+                            if need_slots:
+                                gslots = torch.zeros(tuple(made_from[0].shape), dtype=torch.float64, device=device)
+                                gslots[o, :op.ncases, :op.K] = sl
+                            if need_own:
+                                gown = torch.zeros(tuple(made_from[1].shape), dtype=torch.float64, device=device)
+                                gown[o, :op.ncases] = ow
+                if need_S:
+                    gS = _solve_geometry_adjoint(solver, made_from[0].detach(), x, lam, stream)
+                return lam, gdiag, gS, gslots, gown
+            return gradients(ctx, gout, 5, adjoint)
+
     _AUTOGRAD = types.SimpleNamespace(FitMany=FitMany, FitCloud=FitCloud, Solve=Solve, Evaluate=Evaluate, FitManyGeometry=FitManyGeometry,
-                                      FitCloudGeometry=FitCloudGeometry, StencilApply=StencilApply)
+                                      FitCloudGeometry=FitCloudGeometry, StencilApply=StencilApply, StencilSolve=StencilSolve)
     return _AUTOGRAD
+
+
+def _solve_geometry_adjoint(solver, S, x, lam, stream):
+    """dL/dS through M x = b at fixed x, lam and neighbour lists: -scale * lam^T (dA_o) x.  Row j of A_o applied to x is
+    rows[o] . fi_out[j] of a fit of F = x, so this is the geometry adjoint of that fit with g_j = -scale * lam_j * rows[o]
+    (DESIGN.md section 18): one fit and one geometry-adjoint launch, with the adjoint's two index_add_."""
+    import torch
+    op = solver._op
+    hoods, nk, knowns, weighting_method, point_index = op._geo
+    rows, no, n = op._rows, op.no, op.ncases
+    with _torch_stream(stream, solver._device):
+        if S.shape[0] == op.npoints:
+            F = x
+        else:                                                # points beyond the operator's: no live entry names them
+            F = torch.zeros((S.shape[0],), dtype=torch.float64, device=solver._device)
+            F[:op.npoints] = x
+        fi = torch.zeros((n, no), dtype=torch.float64, device=solver._device)
+        fi[:, 0] = x[:n]                                     # the F-known cases take their own value from here (row j is point j)
+        row = rows[solver._o, :n, :no] if rows.dim() == 3 else rows[solver._o, :no][None, :]
+        g = ((-solver.scale) * lam[:n])[:, None] * row
+    fit_cloud_device(op.dimension, op.order, S, F, hoods, fi, nk, knowns, weighting_method, point_index=point_index, stream=stream)
+    return fit_cloud_geometry_adjoint_device(op.dimension, op.order, S, F, hoods, fi, nk, knowns, weighting_method, g.contiguous(),
+                                             point_index=point_index, stream=stream)[0]
 
 
 def _no_geometry_grad(*geometry):
@@ -1763,22 +1843,85 @@ class StencilOperator:
                          int(out.stride(-1)), alpha, beta if o == 0 else 1.0, dev, s)
         return out
 
-    def coefficients(self):
-        """(slots (nop, ncases, K), own (nop, ncases)): the coefficients unpacked, per neighbour slot and on the point's own value;
-        exact zeros in the padding and where a row has no own entry."""
+    def _slot_positions(self):
+        """(live (ncases, K) bool, dest: the position in col / val of every live neighbour slot, d_own: that of every own entry or None)."""
         import torch
         m = self._live()
         device = self._device
-        slots = torch.zeros((self.nop, self.ncases, self.K), dtype=torch.float64, device=device)
-        own = torch.zeros((self.nop, self.ncases), dtype=torch.float64, device=device)
         j = torch.arange(self.ncases, device=device)
         k = torch.arange(self.K, device=device)
         live = k[None, :] < self._nk[:, None]
         base = m["soff"][j // 64] + j % 64
-        slots[:, live] = self._val[:, (base[:, None] + 64 * k[None, :])[live]]
-        if self._own_mask is not None:
-            own[:, self._own_mask] = self._val[:, (base + 64 * self._nk)[self._own_mask]]
+        dest = (base[:, None] + 64 * k[None, :])[live]
+        return live, dest, (base + 64 * self._nk)[self._own_mask] if self._own_mask is not None else None
+
+    def _unpack(self, planes):
+        import torch
+        nop = int(planes.shape[0])
+        slots = torch.zeros((nop, self.ncases, self.K), dtype=torch.float64, device=self._device)
+        own = torch.zeros((nop, self.ncases), dtype=torch.float64, device=self._device)
+        live, dest, d_own = self._slot_positions()
+        slots[:, live] = planes[:, dest]
+        if d_own is not None:
+            own[:, self._own_mask] = planes[:, d_own]
         return slots, own
+
+    def coefficients(self):
+        """(slots (nop, ncases, K), own (nop, ncases)): the coefficients unpacked, per neighbour slot and on the point's own value;
+        exact zeros in the padding and where a row has no own entry."""
+        self._live()
+        return self._unpack(self._val)
+
+    def unpack(self, plane):
+        """(slots (ncases, K), own (ncases,)) of any plane in the operator's layout, a contiguous float64 device tensor (total,) — a
+        value plane, or StencilSolver.gradients' `values`: what coefficients() does for the operator's own planes, exact zeros in the
+        padding and where a row has no own entry.  Torch operations on the current stream."""
+        m = self._live()
+        if not hasattr(plane, "dim") or not hasattr(plane, "is_cuda"):
+            raise ValueError("argument plane must be a device (HIP) tensor")
+        _check(plane, "plane", "float64", 1)
+        if tuple(plane.shape) != (m["total"],) or (m["total"] > 1 and plane.stride(0) != 1):
+            raise ValueError("plane must be a contiguous float64 device tensor of shape (%d,), the operator's layout; got shape %s with "
+                             "strides %s" % (m["total"], tuple(plane.shape), tuple(plane.stride())))
+        if plane.device != self._device:
+            raise ValueError("all tensors must be on the same device")
+        slots, own = self._unpack(plane.view(1, -1))
+        return slots[0], own[0]
+
+    def set_coefficients(self, slots, own=None, stream=None):
+        """Write new coefficients into the arrays the operator holds: slots (nop, ncases, K) and, for an operator with own entries, own
+        (nop, ncases), as from_coefficients takes them (only live slots and rows with an own entry are looked at).  The structure stays
+        and the padding is untouched.  A built transposed matrix has its values refreshed as update() does (dropped where it is too
+        large for the index pair; the next transposed use rebuilds it).  Torch index operations on `stream` and at most one kernel
+        launch; no host read.  ValueError when `own` is given to an operator without own entries or missing for one with them."""
+        m = self._live()
+        for t, name in ((slots, "slots"), (own, "own")):
+            if t is not None and (not hasattr(t, "dim") or not hasattr(t, "is_cuda")):
+                raise ValueError("argument %s must be a device (HIP) tensor" % name)
+        _double_rows(slots, "slots", self.ncases, self.K, lead=1,
+                     says="slots must be at least (nop, ncases, %d) with a contiguous last axis; got %s" % (self.K, tuple(slots.shape)))
+        if int(slots.shape[0]) != self.nop:
+            raise ValueError("slots has %d value planes, the operator %d" % (int(slots.shape[0]), self.nop))
+        if (own is None) != (self._own_mask is None):
+            raise ValueError("own goes together with an operator that has own entries: this one has %s"
+                             % ("none" if self._own_mask is None else "them"))
+        if own is not None:
+            _double_rows(own, "own", self.nop, self.ncases, says="own must be at least (%d, %d) with a contiguous last axis; got %s"
+                         % (self.nop, self.ncases, tuple(own.shape)))
+        _same_device(self._val, slots, own)
+        with _torch_stream(stream, self._device):
+            live, dest, d_own = self._slot_positions()
+            self._val[:, dest] = slots.detach()[:, :self.ncases, :self.K][:, live]
+            if d_own is not None:
+                self._val[:, d_own] = own.detach()[:self.nop, :self.ncases][:, self._own_mask]
+        tpair = getattr(self, "_tpair", None)
+        if tpair is None:
+            self._t = self._tval = None                     # too large for the pair: rebuilt at the next use
+        elif self._t is not None:
+            s, dev = _stream_and_device(self._val, stream)
+            B.check(B.lib().wlsqm_hip_sell_permute_device(int(tpair.shape[1]), _ptr(tpair[0]), _ptr(tpair[1]),
+                                                          _ptr(self._val), m["total"], _ptr(self._tval), self._t["total"], self.nop, dev, s))
+        return self
 
     def to_sparse_csr(self, o=0):
         """Operator `o` as a torch.sparse_csr_tensor (ncases, npoints): columns sorted, duplicates summed."""
@@ -1806,6 +1949,10 @@ def differentiable_stencil_apply(op, F, known=None, stream=None):
     return _autograd().StencilApply.apply(F, known, op, stream)
 
 
+SolveGradients = collections.namedtuple("SolveGradients", "values diag scale")
+SolveGradients.__doc__ = """What StencilSolver.gradients returns: dL/d(the entries of the value plane) in the operator's layout, dL/d(diag)
+and dL/d(scale) (a 0-d device tensor); None for what was not asked for."""
+
 SolveInfo = collections.namedtuple("SolveInfo", "status iterations residual")
 SolveInfo.__doc__ = """What a StencilSolver says of a solve.  status: 0 converged, 1 iteration limit, 2 breakdown (rho = 0 or (r0, v) = 0),
 3 a non-finite scalar, 4 a zero or non-finite Jacobi diagonal, -1 still running (enqueue with fewer iterations than the solve needs
@@ -1823,7 +1970,9 @@ class StencilSolver:
     at every solve: after op.update(...) it solves with the new values, and nothing has to be called on the solver.
     diag: a float, or a contiguous float64 device tensor (npoints,) that is read at every solve (the caller may change it in place).
     preconditioner: "jacobi" (the inverse of M's diagonal, recomputed at the start of every solve) or None.
-    All workspace, 9 npoints + 2 ceil(npoints / 256) + 16 doubles, is allocated here; close() releases it."""
+    All workspace, 9 npoints + 2 ceil(npoints / 256) + 16 doubles, is allocated here; close() releases it.
+    solve, enqueue and product take transpose=True for M^T; gradients() and differentiable_stencil_solve carry a loss through the
+    solve."""
 
     def __init__(self, op, o=0, diag=1.0, scale=1.0, preconditioner="jacobi"):
         self._ws = None
@@ -1903,12 +2052,19 @@ class StencilSolver:
             raise ValueError("the number of iterations must be 0 .. 2^31 - 1; got %d" % maxiter)
         return rtol, atol, maxiter
 
-    def _system(self):
-        m = self._op._m
+    def _system(self, transpose=False):
+        """The system's arguments of the C entry points: M, or M^T = diag(d) + scale * A_o^T on the operator's transposed arrays."""
+        m, val = (self._op._t, self._op._tval) if transpose else (self._op._m, self._op._val)
         d = self.diag
         return (m["nrows"], int(m["width"].shape[0]), _ptr(m["len"]), _ptr(m["width"]), _ptr(m["soff"]), _ptr(m["col"]),
-                C.c_void_p(self._op._val.data_ptr() + 8 * self._o * m["total"]), _ptr(d) if hasattr(d, "dim") else None,
+                C.c_void_p(val.data_ptr() + 8 * self._o * m["total"]), _ptr(d) if hasattr(d, "dim") else None,
                 0.0 if hasattr(d, "dim") else d, self.scale)
+
+    def _transposed(self, transpose, stream):
+        """The operator's transposed matrix, built at the first transposed use (prepare_transpose: RuntimeError inside a capture)."""
+        if transpose and self._op._t is None:
+            self._op.prepare_transpose(stream)
+        return bool(transpose)
 
     def _no_capture(self, what, stream):
         import torch
@@ -1917,24 +2073,29 @@ class StencilSolver:
                 raise RuntimeError("%s reads the solve's scalars on the host and the stream is capturing: use enqueue inside the capture "
                                    "and info() after the replay" % what)
 
-    def _start(self, b, x, rtol, atol, maxiter, dev, s):
-        B.check(B.lib().wlsqm_hip_krylov_start_device(*self._system(), self._jacobi, _ptr(b), _ptr(x), rtol, atol, maxiter, _ptr(self._ws),
-                                                      dev, s))
+    def _start(self, b, x, rtol, atol, maxiter, dev, s, transpose=False):
+        B.check(B.lib().wlsqm_hip_krylov_start_device(*self._system(transpose), self._jacobi, _ptr(b), _ptr(x), rtol, atol, maxiter,
+                                                      _ptr(self._ws), dev, s))
 
-    def _iterate(self, x, niter, dev, s):
-        B.check(B.lib().wlsqm_hip_krylov_bicgstab_device(*self._system(), self._jacobi, _ptr(x), niter, _ptr(self._ws), dev, s))
+    def _iterate(self, x, niter, dev, s, transpose=False):
+        B.check(B.lib().wlsqm_hip_krylov_bicgstab_device(*self._system(transpose), self._jacobi, _ptr(x), niter, _ptr(self._ws), dev, s))
 
-    def enqueue(self, b, x, iterations, rtol=1e-10, atol=0.0, stream=None):
+    def enqueue(self, b, x, iterations, rtol=1e-10, atol=0.0, stream=None, transpose=False):
         """The start of a solve and `iterations` iterations, as kernel launches on `stream` (default: torch's current stream) and nothing
         else: no allocation, no host read, so it can be captured into a graph, also behind op.update(S, check=False).  The solve stops
         by itself, on the device, at ||r|| <= max(rtol ||b||, atol), after `iterations` (status 1) or at a breakdown; what is enqueued
         behind the stop leaves x and the scalars untouched.  x (npoints,) holds the initial guess and receives the solution.
-        info() tells later how it went."""
+        info() tells later how it went.
+
+        transpose=True solves M^T x = b, M^T = diag(d) + scale * A_o^T, by the same kernels on the operator's transposed matrix (the
+        Jacobi diagonal is the same numbers).  That matrix is built at the first transposed use, which allocates and synchronises
+        (RuntimeError inside a capture: call op.prepare_transpose() first); op.update keeps it refreshed."""
         self._vectors(b=b, x=x)
         rtol, atol, iterations = self._tolerances(rtol, atol, iterations)
+        transpose = self._transposed(transpose, stream)
         s, dev = _stream_and_device(x, stream)
-        self._start(b, x, rtol, atol, iterations, dev, s)
-        self._iterate(x, iterations, dev, s)
+        self._start(b, x, rtol, atol, iterations, dev, s, transpose)
+        self._iterate(x, iterations, dev, s, transpose)
         return self
 
     def _read(self, what, stream):
@@ -1951,31 +2112,32 @@ class StencilSolver:
         inside a graph capture)."""
         return self._read("info", stream)[0]
 
-    def solve(self, b, x, rtol=1e-10, atol=0.0, maxiter=1000, check_every=8, stream=None):
+    def solve(self, b, x, rtol=1e-10, atol=0.0, maxiter=1000, check_every=8, stream=None, transpose=False):
         """x <- the solution of M x = b from the initial guess in x; returns SolveInfo(status, iterations, residual).  Enqueues
         `check_every` iterations, reads the scalars (one synchronisation) and repeats, up to `maxiter` iterations in all.  The stop is
         taken on the device after every iteration, so `iterations` is exact whatever check_every is; with check_every=1 no launch is
-        enqueued behind the stop either.  RuntimeError inside a graph capture."""
+        enqueued behind the stop either.  RuntimeError inside a graph capture.  transpose=True: M^T x = b, as enqueue."""
         self._vectors(b=b, x=x)
         rtol, atol, maxiter = self._tolerances(rtol, atol, maxiter)
         check_every = int(check_every)
         if check_every < 1:
             raise ValueError("check_every must be >= 1; got %d" % check_every)
         self._no_capture("solve", stream)
+        transpose = self._transposed(transpose, stream)
         s, dev = _stream_and_device(x, stream)
-        self._start(b, x, rtol, atol, maxiter, dev, s)
+        self._start(b, x, rtol, atol, maxiter, dev, s, transpose)
         left = maxiter
         while True:
             n = min(check_every, left)
-            self._iterate(x, n, dev, s)
+            self._iterate(x, n, dev, s, transpose)
             left -= n
             info, done = self._read("solve", stream)
             if done or left == 0:
                 return info
 
-    def product(self, v, w=None, out=None, stream=None):
+    def product(self, v, w=None, out=None, stream=None, transpose=False):
         """(M v, (M v, w), (M v, M v)): the solve's own fused product and the dot products of its pass (w default v), for checks and
-        for residuals.  One host read of the two sums; not between an enqueue and the end of its solve."""
+        for residuals.  One host read of the two sums; not between an enqueue and the end of its solve.  transpose=True: M^T v."""
         import torch
         self._live()
         self._no_capture("product", stream)
@@ -1987,11 +2149,119 @@ class StencilSolver:
             self._vectors(v=v, out=out)
         else:
             self._vectors(v=v, w=w, out=out)
+        transpose = self._transposed(transpose, stream)
         s, dev = _stream_and_device(v, stream)
-        B.check(B.lib().wlsqm_hip_krylov_product_device(*self._system(), _ptr(v), _ptr(w), _ptr(out), _ptr(self._ws), dev, s))
+        B.check(B.lib().wlsqm_hip_krylov_product_device(*self._system(transpose), _ptr(v), _ptr(w), _ptr(out), _ptr(self._ws), dev, s))
         with _torch_stream(stream, self._device):
             head = self._ws[:16].cpu().numpy()
         return out, float(head[6]), float(head[7])
+
+    def gradients(self, lam, x, values=False, diag=False, scale=False, stream=None):
+        """The gradients of a loss L through the solve M x = b, from x and lam, the solution of M^T lam = dL/dx (solve(transpose=True)):
+        SolveGradients(values, diag, scale), each None unless asked for with True or with a tensor to write into.
+          values: (total,) in the operator's layout, -((scale * lam_j) * x_col) at every live entry of row j, +0.0 in the padding:
+                  dL/d(the entries of value plane o); op.unpack(values) gives it per slot.
+          diag:   (npoints,), -(lam_i * x_i): dL/d(diag).
+          scale:  a 0-d device tensor, -(lam, A_o x): dL/d(scale), copied from the workspace on the stream (no host read).
+        One kernel launch on `stream` ("krylov-grads": one pass over the forward matrix), and the one-workgroup reduce for `scale`;
+        no synchronisation, no allocation when the outputs are given.  lam, x and the outputs are contiguous float64 tensors on the
+        operator's device that overlap neither each other nor the diag tensor, the operator's values or the workspace.  Like product,
+        not between an enqueue and the end of its solve."""
+        import torch
+        m = self._live()
+        total = int(m["total"])
+        asked = lambda flag: flag is not None and flag is not False
+        if not (asked(values) or asked(diag) or asked(scale)):
+            raise ValueError("gradients: none of values, diag and scale is asked for")
+        f64 = dict(dtype=torch.float64, device=self._device)
+        with _torch_stream(stream, self._device):
+            gval = torch.empty((total,), **f64) if values is True else (values if asked(values) else None)
+            gdiag = torch.empty((self.npoints,), **f64) if diag is True else (diag if asked(diag) else None)
+            gscale = torch.empty((), **f64) if scale is True else (scale if asked(scale) else None)
+        named = dict(lam=lam, x=x)
+        if gdiag is not None:
+            named["grad_diag"] = gdiag
+        self._vectors(**named)
+        others = dict(named, workspace=self._ws, **{"the operator's values": self._op._val})
+        if hasattr(self.diag, "dim"):
+            others["diag"] = self.diag
+        for t, name, shape in ((gval, "values", (total,)), (gscale, "scale", None)):
+            if t is None:
+                continue
+            if not hasattr(t, "dim") or not hasattr(t, "is_cuda"):
+                raise ValueError("argument %s must be True, False or a device (HIP) tensor" % name)
+            if shape is None:
+                if str(t.dtype) != "torch.float64" or not t.is_cuda or t.numel() != 1:
+                    raise ValueError("scale must be a float64 device tensor of one element; got %s of shape %s" % (t.dtype, tuple(t.shape)))
+            else:
+                _check(t, name, "float64", 1)
+                if tuple(t.shape) != shape or (total > 1 and t.stride(0) != 1):
+                    raise ValueError("%s must be a contiguous float64 device tensor of shape %s, the operator's layout; got shape %s with "
+                                     "strides %s" % (name, shape, tuple(t.shape), tuple(t.stride())))
+            if t.device != self._device:
+                raise ValueError("all tensors must be on the same device")
+            for other, held in others.items():
+                if _overlap(t, held):
+                    raise ValueError("%s overlaps %s in memory" % (name, other))
+            others[name] = t
+        s, dev = _stream_and_device(x, stream)
+        B.check(B.lib().wlsqm_hip_krylov_grads_device(*self._system(), _ptr(lam), _ptr(x), _ptr(gval) if total else None, _ptr(gdiag),
+                                                      1 if gscale is not None else 0, _ptr(self._ws), dev, s))
+        if gscale is not None:
+            with _torch_stream(stream, self._device):
+                gscale.view(-1).copy_(self._ws[6:7])
+        return SolveGradients(gval, gdiag, gscale)
+
+
+def differentiable_stencil_solve(solver, b, x0=None, S=None, coefficients=None, rtol=1e-10, atol=0.0, maxiter=1000, check_every=8,
+                                 adjoint_rtol=None, stream=None):
+    """x (npoints,), the solution of M x = b by solver.solve, as a differentiable function of b, of solver.diag when that is a tensor,
+    and of what the operator is made from: a new tensor with a grad_fn.
+
+    S: the point table.  The forward runs solver's op.update(S.detach()) first (the operator must come from a fit, RuntimeError
+    otherwise), and S receives dL/dS at fixed neighbour lists, with S's full shape.  coefficients=(slots, own): as
+    StencilOperator.set_coefficients takes them (own None for an operator without own entries); the forward writes them into the
+    operator first, and they receive the gradients of value plane `o`'s entries, exact zeros in the other planes and in the padding.
+    Both given: ValueError.  With neither, the operator is not an input, and the backward pass reads it as it is then: an op.update
+    or set_coefficients between forward and backward invalidates the graph, as any in-place change of a saved tensor does (it is not
+    detected).  With either, the backward pass first puts the operator back where the forward had it (op.update(S, check=False), or
+    set_coefficients), so that the steps of a time loop may share one operator and one solver.
+
+    The forward solves from x0 (default zeros; it receives no gradient) to rtol / atol within maxiter iterations; a status other than
+    0 is a RuntimeError that quotes the SolveInfo, and solver.info() afterwards is the forward's.  The backward pass solves
+    M^T lam = dL/dx from zero (solve(transpose=True), relative tolerance `adjoint_rtol or rtol`; atol belongs to the forward alone;
+    RuntimeError when it does not converge), then: b gets lam; diag and the coefficients get StencilSolver.gradients; S gets
+    fit_cloud_geometry_adjoint_device on the fit of F = x with g_j = -scale * lam_j * rows[o].  Only what requires a gradient is
+    computed, and nothing is launched when nothing does.  These are the gradients of the exact solution map (the implicit function
+    theorem), accurate to the residuals of the two solves, not the derivative of the iteration.  `scale` is a Python float of the
+    solver: its gradient is solver.gradients(lam, x, scale=True).  Not capturable: both passes read the solve's scalars on the host
+    (RuntimeError inside a graph capture).  Once differentiable."""
+    if not isinstance(solver, StencilSolver):
+        raise ValueError("solver must be a StencilSolver")
+    solver._live()
+    op = solver._op
+    if S is not None and coefficients is not None:
+        raise ValueError("S and coefficients are two ways to make the operator: pass one of them")
+    slots = own = None
+    if coefficients is not None:
+        if not isinstance(coefficients, (tuple, list)) or len(coefficients) != 2:
+            raise ValueError("coefficients must be (slots, own), own None for an operator without own entries")
+        slots, own = coefficients
+        if slots is None:
+            raise ValueError("coefficients must be (slots, own), own None for an operator without own entries")
+    if S is not None and getattr(op, "_geo", None) is None:
+        raise RuntimeError("the stencil operator was made from coefficients: there is no fit to redo")
+    named = dict(b=b) if x0 is None else dict(b=b, x0=x0)
+    solver._vectors(**named)                         # before anything is detached or cloned
+    solver._tolerances(rtol, atol, maxiter)
+    if adjoint_rtol is not None:
+        solver._tolerances(adjoint_rtol, atol, maxiter)
+    if int(check_every) < 1:
+        raise ValueError("check_every must be >= 1; got %d" % int(check_every))
+    solver._no_capture("differentiable_stencil_solve", stream)
+    diag = solver.diag if hasattr(solver.diag, "dim") else None
+    return _autograd().StencilSolve.apply(b, diag, S, slots, own, x0, solver, float(rtol), float(atol), int(maxiter), int(check_every),
+                                          None if adjoint_rtol is None else float(adjoint_rtol), stream)
 
 
 # ---- batched dense solves (the kernels behind wlsqm.utils.lapackdrivers), device-resident ----
