@@ -615,6 +615,41 @@ int wlsqm_hip_krylov_grads_device(int64_t nrows, int64_t nslices, const int32_t*
                                   const double* lam, const double* x, double* grad_val, double* grad_diag, int want_scale,
                                   void* workspace, int device, void* stream);
 
+/* ---- block-Jacobi preconditioner of those solves (extension; csrc/krylov.hip) ----
+ * P = blockdiag(M_BB)^-1 in place of the inverse diagonal: block B is rows and columns B * block .. B * block + block - 1 of M, block one of
+ * 8, 16, 32 (each divides 64: a block never crosses a slice), the last block cut at nrows and completed by the identity.  Entry (i, j) of a
+ * block is d_i delta_ij + scale * (the sum of row i's entries in column j, in entry order).  nslices must be ceil(nrows / 64).
+ * The block plane: wlsqm_hip_krylov_block_bytes(nrows, block) bytes of device memory, 8-byte aligned,
+ *   W[(slice * block + j) * 64 + lane]   float64   entry (lane % block, j) of the inverse of the block that holds row slice * 64 + lane,
+ * nslices * block * 64 doubles, so that a wave reads column j of its slice as one contiguous run of 512 bytes; rows beyond nrows are
+ * identity rows.  Behind them ceil(nrows / 256) doubles: the counts of unusable blocks of the last factor, one per workgroup.
+ *
+ * wlsqm_hip_krylov_block_factor_device ("krylov-blocks", one launch): gathers every diagonal block from the matrix and inverts it by
+ *   Gauss-Jordan elimination with partial row pivoting (the largest entry of the column among the rows not yet used, the lowest row at a
+ *   tie), one lane per row.  planes_t (nullable): a second plane that receives the transposed inverses, the preconditioner of M^T.  A zero
+ *   or non-finite pivot or a non-finite inverse counts the block as unusable: never a fault, and the next start answers status 4.
+ *   Status 4 of the scalars therefore also means a singular or non-finite diagonal block, found before the first iteration with x as given.
+ * wlsqm_hip_krylov_block_start_device / _bicgstab_device: wlsqm_hip_krylov_start_device / _bicgstab_device with P taken from `planes` as
+ *   the last factor left it (the start does not factor).  The P and S steps apply P in the launch that forms p and s
+ *   ("krylov-update-block"), z_i = sum_j W[.., j, lane] * v_j with j ascending and fma; the other six launches of an iteration are the
+ *   Jacobi route's own kernels.  For M^T pass the transposed matrix and the transposed plane.  The workspace is the same.
+ * wlsqm_hip_krylov_block_precondition_device ("krylov-precondition", one launch): out = P v; v and out must not overlap.
+ * WLSQM_EVALUE as above, and for a block other than 8, 16, 32. */
+int64_t wlsqm_hip_krylov_block_bytes(int64_t nrows, int block);
+int wlsqm_hip_krylov_block_factor_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                         const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                         int block, void* planes, void* planes_t, int device, void* stream);
+int wlsqm_hip_krylov_block_start_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                        const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                        int block, const void* planes, const double* b, const double* x, double rtol, double atol,
+                                        int64_t maxiter, void* workspace, int device, void* stream);
+int wlsqm_hip_krylov_block_bicgstab_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                           const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                           int block, const void* planes, double* x, int64_t niter, void* workspace, int device,
+                                           void* stream);
+int wlsqm_hip_krylov_block_precondition_device(int64_t nrows, int block, const void* planes, const double* v, double* out, int device,
+                                               void* stream);
+
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ---- */
 /* Runs `reps` back-to-back launches of the fit kernel for batch `b` (device-resident, uniform
  * order) on `stream`, bracketed by HIP events on that stream; returns the mean kernel time in

@@ -348,6 +348,185 @@ static void krylov_grads_launch(const KrylovSys& m, const KrylovWork& k, const d
     hipLaunchKernelGGL((krylov_grads_kernel<VALUES, DIAG, SCALE>), dim3((unsigned)k.nwg), dim3(256), 0, s, m, lam, x, gval, gdiag, k.partial);
 }
 
+// ---- the block-Jacobi preconditioner: P = blockdiag(M_BB)^-1, block B the rows B NB .. B NB + NB - 1 -----------
+// The inverses live in a plane W of nslices * NB * 64 doubles, W[(slice * NB + j) * 64 + lane] = entry (lane % NB, j) of the inverse of the
+// block that holds row slice * 64 + lane: a wave's load of column j is one contiguous run of 512 bytes.  NB divides 64, so a block never
+// crosses a slice.  Behind the plane sit ceil(nrows / 256) doubles, the per-workgroup counts of the unusable blocks of the last factor,
+// which every start reduces into status 4 (they outlive the iterations, which the workspace's partials do not).
+
+__host__ __device__ static inline long long krylov_plane_doubles(long long nslices, int nb) { return nslices * nb * 64; }
+
+// Step K of krylov_blocks_kernel's elimination and the steps behind it: K is a template parameter so that every register index is a constant.
+template <int NB, int K>
+__device__ __forceinline__ void krylov_eliminate(double (&a)[NB], double (&inv)[NB], int lane, bool& used, int& step, bool& unusable) {
+    if constexpr (K < NB) {
+        const double mag = __builtin_fabs(a[K]);
+        double key = used ? -1.0 : (mag != mag ? __builtin_inf() : mag);
+        int who = lane;
+#pragma unroll
+        for (int off = 1; off < NB; off <<= 1) {
+            const double okey = __shfl_xor(key, off, 64);
+            const int owho = __shfl_xor(who, off, 64);
+            if (okey > key || (okey == key && owho < who)) { key = okey; who = owho; }
+        }
+        const double pv = __shfl(a[K], who, 64);
+        if (!(pv != 0.0 && __builtin_isfinite(pv))) unusable = true;
+        const double pinv = 1.0 / pv, f = a[K];
+        const bool mine = lane == who;
+        if (mine) { used = true; step = K; }
+#pragma unroll
+        for (int j = K + 1; j < NB; ++j) {
+            const double pj = __shfl(a[j], who, 64) * pinv;
+            a[j] = mine ? pj : __builtin_fma(-f, pj, a[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const double qj = __shfl(inv[j], who, 64) * pinv;
+            inv[j] = mine ? qj : __builtin_fma(-f, qj, inv[j]);
+        }
+        krylov_eliminate<NB, K + 1>(a, inv, lane, used, step, unusable);
+    }
+}
+
+// One wave per slice, one lane per row.  The lane gathers row `lane % NB` of its diagonal block (duplicate columns summed in entry order,
+// as krylov_diag_kernel; rows beyond nrows are identity rows), then the NB lanes of a block invert it by Gauss-Jordan elimination on
+// [B | I] with partial pivoting: at step k the pivot is the largest |entry k| among the rows that have not been a pivot yet, the lowest
+// row winning a tie, a NaN counting as the largest; its row, scaled by 1 / pivot, travels by cross-lane moves (ds_bpermute) and every
+// other row of the block eliminates with fma.  Rows are not swapped while eliminating: the row that was the pivot of step k holds row k
+// of the inverse at the end, and one last cross-lane move puts it into lane k.  Every register index is a constant after unrolling.
+// A zero or non-finite pivot, or a non-finite entry of the inverse, counts the block as unusable.  WT (nullable) receives the
+// transposed inverses in the same layout, counts and all.
+template <int NB>
+__global__ void __launch_bounds__(256) krylov_blocks_kernel(const KrylovSys m, long long nslices, double* W, double* WT) {
+    const int lane = threadIdx.x & 63, l = lane & (NB - 1), b0 = lane - l;
+    const long long s = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long row = s * 64 + lane;
+    double bad = 0.0;
+    if (s * 64 < m.nrows) {                                      // wave-uniform
+        const int wid = __builtin_amdgcn_readfirstlane(m.width[s]);
+        const long long at = m.soff[s] + lane;
+        const bool live = row < m.nrows;
+        int n = live ? m.len[row] : 0;
+        n = n < wid ? n : wid;
+        const long long first = row - l;                         // the block's first row and column
+        double a[NB], inv[NB];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) a[j] = 0.0;
+        for (int e = 0; e < wid; ++e) {                          // wave-uniform
+            if (e < n) {
+                const long long t = (long long)m.col[at + 64LL * e] - first;
+                if (t >= 0 && t < NB) {
+                    const double v = m.val[at + 64LL * e];
+#pragma unroll
+                    for (int j = 0; j < NB; ++j) a[j] += t == j ? v : 0.0;
+                }
+            }
+        }
+        const double d = live ? (m.dvec ? m.dvec[row] : m.dconst) : 1.0;
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const double dj = j == l ? d : 0.0;
+            a[j] = live ? dj + m.c * a[j] : dj;
+            inv[j] = j == l ? 1.0 : 0.0;
+        }
+        bool used = false, unusable = false;
+        int step = 0;
+        krylov_eliminate<NB, 0>(a, inv, lane, used, step, unusable);
+        int src = lane;
+#pragma unroll
+        for (int j = 0; j < NB; ++j)
+            if (__shfl(step, b0 + j, 64) == l) src = b0 + j;
+        double* w = W + (s * NB) * 64 + lane;
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            inv[j] = __shfl(inv[j], src, 64);
+            if (!__builtin_isfinite(inv[j])) unusable = true;
+            w[64LL * j] = inv[j];
+        }
+        if (WT) {
+            double* wt = WT + (s * NB + l) * 64 + b0;            // column l of the transposed block, its rows b0 .. b0 + NB - 1
+#pragma unroll
+            for (int j = 0; j < NB; ++j) wt[j] = inv[j];
+        }
+        bad = unusable ? 1.0 : 0.0;
+    }
+    double* counts = W + krylov_plane_doubles(nslices, NB);
+    block_sums<false>(bad, 0.0, counts, gridDim.x);
+    if (WT && threadIdx.x == 0) WT[krylov_plane_doubles(nslices, NB) + blockIdx.x] = counts[blockIdx.x];
+}
+
+// z_lane = sum_j W[.., j, lane] * v_(first + j), j ascending with fma, v taken from the lanes of the wave that hold it.  Every lane of the
+// wave takes part; a lane beyond nrows passes 0, and its own row of W is an identity row.
+template <int NB>
+__device__ __forceinline__ double krylov_block_apply(const double* w, double v, int lane) {
+    const int b0 = lane & ~(NB - 1);
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < NB; ++j) acc = __builtin_fma(w[64LL * j], __shfl(v, b0 + j, 64), acc);
+    return acc;
+}
+
+// krylov_update_kernel's P and S steps with phat = P p and shat = P s: one launch each, p and s never re-read from memory.
+template <int NB, int MODE>
+__global__ void __launch_bounds__(256) krylov_update_block_kernel(long long nrows, const KrylovWork k, const double* W, const KrylovScalars* sc) {
+    if (sc->done) return;                                        // uniform: the whole grid
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const long long s = i >> 6;
+    if (s * 64 >= nrows) return;                                 // wave-uniform
+    const bool live = i < nrows;
+    double u = 0.0;
+    if (live) {
+        if (MODE == UPDATE_P) {
+            u = k.r[i];
+            if (sc->iterations > 0) {
+                const double omega = sc->omega, beta = (sc->rho / sc->rho_old) * (sc->alpha / omega);
+                u = u + beta * (k.p[i] - omega * k.v[i]);
+            }
+            k.p[i] = u;
+        } else {
+            u = k.r[i] - sc->alpha * k.v[i];
+            k.s[i] = u;
+        }
+    }
+    const double z = krylov_block_apply<NB>(W + (s * NB) * 64 + lane, u, lane);
+    if (live) (MODE == UPDATE_P ? k.phat : k.shat)[i] = z;
+}
+
+template <int NB>
+__global__ void __launch_bounds__(256) krylov_precondition_kernel(long long nrows, const double* W, const double* v, double* out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const long long s = i >> 6;
+    if (s * 64 >= nrows) return;                                 // wave-uniform
+    const bool live = i < nrows;
+    const double z = krylov_block_apply<NB>(W + (s * NB) * 64 + lane, live ? v[i] : 0.0, lane);
+    if (live) out[i] = z;
+}
+
+static int krylov_block_size(const char* who, int block, const void* planes) {
+    if (block != 8 && block != 16 && block != 32) { set_error(std::string(who) + ": block must be 8, 16 or 32"); return WLSQM_EVALUE; }
+    if (!planes) { set_error(std::string(who) + ": null array"); return WLSQM_EVALUE; }
+    return WLSQM_OK;
+}
+
+template <int NB>
+static void krylov_block_iterations(const KrylovSys& m, const KrylovWork& w, const double* W, double* x, int64_t niter, hipStream_t s) {
+    const dim3 grid((unsigned)w.nwg);
+    const KrylovScalars* sc = w.sc;
+    const long long nrows = m.nrows;
+    for (int64_t it = 0; it < niter; ++it) {
+        hipLaunchKernelGGL((krylov_update_block_kernel<NB, UPDATE_P>), grid, dim3(256), 0, s, nrows, w, W, sc);
+        hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_V>), grid, dim3(256), 0, s, m, (const double*)w.phat, (const double*)w.r0, w.v, (double*)nullptr, w.partial, sc, 0);
+        krylov_reduce(REDUCE_ALPHA, w, w.nwg, 1, 0.0, 0.0, 0, s);
+        hipLaunchKernelGGL((krylov_update_block_kernel<NB, UPDATE_S>), grid, dim3(256), 0, s, nrows, w, W, sc);
+        hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_T>), grid, dim3(256), 0, s, m, (const double*)w.shat, (const double*)w.s, w.t, (double*)nullptr, w.partial, sc, 0);
+        krylov_reduce(REDUCE_OMEGA, w, w.nwg, 2, 0.0, 0.0, 0, s);
+        hipLaunchKernelGGL((krylov_update_kernel<UPDATE_X>), grid, dim3(256), 0, s, nrows, w, x, sc);
+        krylov_reduce(REDUCE_RHO, w, w.nwg, 2, 0.0, 0.0, 0, s);
+    }
+}
+
 }  // namespace wlsqm
 
 using namespace wlsqm;
@@ -467,6 +646,118 @@ int wlsqm_hip_krylov_grads_device(int64_t nrows, int64_t nslices, const int32_t*
     if (want_scale) krylov_reduce(REDUCE_NEGATED, k, k.nwg, 1, 0.0, 0.0, 0, s);
     WLSQM_HIP_CHECK(hipGetLastError());
     note_kernel("krylov-grads");
+    return WLSQM_OK;
+}
+
+int64_t wlsqm_hip_krylov_block_bytes(int64_t nrows, int block) {
+    if (nrows < 0 || (block != 8 && block != 16 && block != 32)) return -1;
+    return (int64_t)sizeof(double) * (krylov_plane_doubles((nrows + 63) / 64, block) + (nrows + 255) / 256);
+}
+
+int wlsqm_hip_krylov_block_factor_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                         const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                         int block, void* planes, void* planes_t, int device, void* stream) {
+    KrylovSys m;
+    int rc = krylov_block_size("krylov_block_factor", block, planes);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_system("krylov_block_factor", m, nrows, nslices, len, width, soff, col, val, diag, diag_const, scale, planes);
+    if (rc != WLSQM_OK) return rc;
+    if (nslices != (nrows + 63) / 64) { set_error("krylov_block_factor: nslices must be ceil(nrows / 64)"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)((nrows + 255) / 256));
+    double *W = static_cast<double*>(planes), *WT = static_cast<double*>(planes_t);
+    switch (block) {
+    case 8: hipLaunchKernelGGL(krylov_blocks_kernel<8>, grid, dim3(256), 0, s, m, (long long)nslices, W, WT); break;
+    case 16: hipLaunchKernelGGL(krylov_blocks_kernel<16>, grid, dim3(256), 0, s, m, (long long)nslices, W, WT); break;
+    default: hipLaunchKernelGGL(krylov_blocks_kernel<32>, grid, dim3(256), 0, s, m, (long long)nslices, W, WT); break;
+    }
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-blocks");
+    return WLSQM_OK;
+}
+
+int wlsqm_hip_krylov_block_start_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                        const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                        int block, const void* planes, const double* b, const double* x, double rtol, double atol,
+                                        int64_t maxiter, void* workspace, int device, void* stream) {
+    KrylovSys m;
+    int rc = krylov_block_size("krylov_block_start", block, planes);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_system("krylov_block_start", m, nrows, nslices, len, width, soff, col, val, diag, diag_const, scale, workspace);
+    if (rc != WLSQM_OK) return rc;
+    if (nslices != (nrows + 63) / 64) { set_error("krylov_block_start: nslices must be ceil(nrows / 64)"); return WLSQM_EVALUE; }
+    if (!b || !x) { set_error("krylov_block_start: null array"); return WLSQM_EVALUE; }
+    if (!(rtol >= 0.0) || !(atol >= 0.0) || !std::isfinite(rtol) || !std::isfinite(atol)) {
+        set_error("krylov_block_start: rtol and atol must be finite and >= 0");
+        return WLSQM_EVALUE;
+    }
+    if (maxiter < 0 || maxiter > INT32_MAX) { set_error("krylov_block_start: maxiter must be 0 .. 2^31 - 1"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const KrylovWork w = krylov_work(workspace, nrows, true);
+    const dim3 grid((unsigned)w.nwg);
+    const double* counts = static_cast<const double*>(planes) + krylov_plane_doubles(nslices, block);
+    hipLaunchKernelGGL(krylov_reduce_kernel, dim3(1), dim3(256), 0, s, (int)REDUCE_DIAG, counts, w.nwg, 1, w.sc, rtol, atol, (int)maxiter);
+    hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_RESIDUAL>), grid, dim3(256), 0, s, m, x, b, w.r, w.r0, w.partial, (const KrylovScalars*)w.sc, 0);
+    note_kernel("krylov-spmv-dot");
+    krylov_reduce(REDUCE_RESIDUAL, w, w.nwg, 2, rtol, atol, (int)maxiter, s);
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-reduce");
+    return WLSQM_OK;
+}
+
+int wlsqm_hip_krylov_block_bicgstab_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                           const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                           int block, const void* planes, double* x, int64_t niter, void* workspace, int device,
+                                           void* stream) {
+    KrylovSys m;
+    int rc = krylov_block_size("krylov_block_bicgstab", block, planes);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_system("krylov_block_bicgstab", m, nrows, nslices, len, width, soff, col, val, diag, diag_const, scale, workspace);
+    if (rc != WLSQM_OK) return rc;
+    if (nslices != (nrows + 63) / 64) { set_error("krylov_block_bicgstab: nslices must be ceil(nrows / 64)"); return WLSQM_EVALUE; }
+    if (!x) { set_error("krylov_block_bicgstab: null array"); return WLSQM_EVALUE; }
+    if (niter < 0) { set_error("krylov_block_bicgstab: niter must be >= 0"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK || niter == 0) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const KrylovWork w = krylov_work(workspace, nrows, true);
+    const double* W = static_cast<const double*>(planes);
+    switch (block) {
+    case 8: krylov_block_iterations<8>(m, w, W, x, niter, s); break;
+    case 16: krylov_block_iterations<16>(m, w, W, x, niter, s); break;
+    default: krylov_block_iterations<32>(m, w, W, x, niter, s); break;
+    }
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-update-block");
+    return WLSQM_OK;
+}
+
+int wlsqm_hip_krylov_block_precondition_device(int64_t nrows, int block, const void* planes, const double* v, double* out, int device,
+                                               void* stream) {
+    int rc = krylov_block_size("krylov_block_precondition", block, planes);
+    if (rc != WLSQM_OK) return rc;
+    if (nrows < 1 || (nrows + 255) / 256 > 0x7fffffffLL) { set_error("krylov_block_precondition: nrows must be >= 1"); return WLSQM_EVALUE; }
+    if (!v || !out) { set_error("krylov_block_precondition: null array"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)((nrows + 255) / 256));
+    const double* W = static_cast<const double*>(planes);
+    switch (block) {
+    case 8: hipLaunchKernelGGL(krylov_precondition_kernel<8>, grid, dim3(256), 0, s, (long long)nrows, W, v, out); break;
+    case 16: hipLaunchKernelGGL(krylov_precondition_kernel<16>, grid, dim3(256), 0, s, (long long)nrows, W, v, out); break;
+    default: hipLaunchKernelGGL(krylov_precondition_kernel<32>, grid, dim3(256), 0, s, (long long)nrows, W, v, out); break;
+    }
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-precondition");
     return WLSQM_OK;
 }
 

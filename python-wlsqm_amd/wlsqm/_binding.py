@@ -206,6 +206,19 @@ def lib():
         L.wlsqm_hip_krylov_grads_device.argtypes = ([C.c_int64, C.c_int64] + [C.c_void_p] * 6 + [C.c_double, C.c_double]
                                                     + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p])
         L.wlsqm_hip_krylov_grads_device.restype = C.c_int
+    # the block-Jacobi preconditioner of those solves (wlsqm.hip.BlockJacobi)
+    if hasattr(L, "wlsqm_hip_krylov_block_factor_device"):
+        system = [C.c_int64, C.c_int64] + [C.c_void_p] * 6 + [C.c_double, C.c_double]
+        L.wlsqm_hip_krylov_block_bytes.argtypes = [C.c_int64, C.c_int]
+        L.wlsqm_hip_krylov_block_bytes.restype = C.c_int64
+        L.wlsqm_hip_krylov_block_factor_device.argtypes = system + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_block_start_device.argtypes = system + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                                                   C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_block_bicgstab_device.argtypes = system + [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
+                                                                      C.c_void_p]
+        L.wlsqm_hip_krylov_block_precondition_device.argtypes = [C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        for name in ("factor", "start", "bicgstab", "precondition"):
+            getattr(L, "wlsqm_hip_krylov_block_%s_device" % name).restype = C.c_int
     # batched dense solves (wlsqm.utils.lapackdrivers, wlsqm.hip.*_batched)
     for op in ("getrf", "gesv", "sytrf", "sysv"):
         solve = op in ("gesv", "sysv")

@@ -19,7 +19,7 @@ __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_c
            "differentiable_solve", "differentiable_solve_many",
            "InterpolationPlan", "differentiable_evaluate",
            "StencilOperator", "stencil_rows", "differentiable_stencil_apply", "StencilSolver", "SolveInfo",
-           "SolveGradients", "differentiable_stencil_solve",
+           "SolveGradients", "BlockJacobi", "differentiable_stencil_solve",
            "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
            "getrf_batched", "getrs_batched", "gesv_batched", "sytrf_batched", "sytrs_batched", "sysv_batched", "symmetrize_batched"]
 
@@ -1955,8 +1955,25 @@ and dL/d(scale) (a 0-d device tensor); None for what was not asked for."""
 
 SolveInfo = collections.namedtuple("SolveInfo", "status iterations residual")
 SolveInfo.__doc__ = """What a StencilSolver says of a solve.  status: 0 converged, 1 iteration limit, 2 breakdown (rho = 0 or (r0, v) = 0),
-3 a non-finite scalar, 4 a zero or non-finite Jacobi diagonal, -1 still running (enqueue with fewer iterations than the solve needs
+3 a non-finite scalar, 4 a zero or non-finite Jacobi diagonal or a singular or non-finite block of a BlockJacobi, -1 still running (enqueue with fewer iterations than the solve needs
 always ends in 1).  iterations: those completed.  residual: the recursive ||r||_2 (NaN with status 4: no residual was formed)."""
+
+
+class BlockJacobi:
+    """The block-Jacobi preconditioner of a StencilSolver: P = blockdiag(M_BB)^-1, the exact inverses of the
+    diagonal blocks of `block` consecutive rows (8, 16 or 32), the last block cut at npoints.  It pays where consecutive rows are
+    neighbours in space — a cloud in Morton order (synth.morton_order), as every large workload of this project is; on a cloud in
+    random order the blocks hold next to nothing off their diagonals and it does no better than "jacobi".
+    refresh=True: P is recomputed from the operator's arrays at the start of every solve / enqueue, as the Jacobi diagonal is.
+    refresh=False: P is computed at the first start and again only by solver.refresh() — for time loops on a fixed operator."""
+
+    def __init__(self, block=16, refresh=True):
+        if isinstance(block, bool) or block not in (8, 16, 32):
+            raise ValueError("block must be 8, 16 or 32; got %r" % (block,))
+        self.block, self.refresh = int(block), bool(refresh)
+
+    def __repr__(self):
+        return "BlockJacobi(block=%d, refresh=%r)" % (self.block, self.refresh)
 
 
 class StencilSolver:
@@ -1969,8 +1986,11 @@ class StencilSolver:
     ValueError) — not closed, and without known derivatives (their affine term belongs in b).  The solver reads the operator's arrays
     at every solve: after op.update(...) it solves with the new values, and nothing has to be called on the solver.
     diag: a float, or a contiguous float64 device tensor (npoints,) that is read at every solve (the caller may change it in place).
-    preconditioner: "jacobi" (the inverse of M's diagonal, recomputed at the start of every solve) or None.
-    All workspace, 9 npoints + 2 ceil(npoints / 256) + 16 doubles, is allocated here; close() releases it.
+    preconditioner: "jacobi" (the inverse of M's diagonal, recomputed at the start of every solve), None, or a BlockJacobi (the
+    inverses of the diagonal blocks of 8, 16 or 32 consecutive rows: for large steps on a cloud in Morton order).
+    All workspace, 9 npoints + 2 ceil(npoints / 256) + 16 doubles, is allocated here; close() releases it.  A BlockJacobi adds its
+    plane, 64 block ceil(npoints / 64) + ceil(npoints / 256) doubles, and a second one for M^T at the first transposed use
+    (prepare_transpose).
     solve, enqueue and product take transpose=True for M^T; gradients() and differentiable_stencil_solve carry a loss through the
     solve."""
 
@@ -1985,8 +2005,11 @@ class StencilSolver:
             raise ValueError("the operator depends on known DOFs other than F: their affine term belongs in b, build the operator without them")
         if not 0 <= int(o) < op.nop:
             raise ValueError("the operator has %d value planes; got o = %d" % (op.nop, int(o)))
-        if preconditioner not in ("jacobi", None):
-            raise ValueError("preconditioner must be 'jacobi' or None; got %r" % (preconditioner,))
+        self._block = preconditioner if isinstance(preconditioner, BlockJacobi) else None
+        if self._block is None and preconditioner not in ("jacobi", None):
+            raise ValueError("preconditioner must be 'jacobi' or None, or a BlockJacobi; got %r" % (preconditioner,))
+        self._planes = self._planes_t = None
+        self._factored = self._factored_t = False
         self._op, self._o, self._jacobi = op, int(o), 1 if preconditioner == "jacobi" else 0
         self.npoints, self._device = op.npoints, op._device
         self.scale = float(scale)
@@ -2001,6 +2024,13 @@ class StencilSolver:
             raise ValueError("row j of the operator must be the equation of point j: point_index must be None or the identity")
         nbytes = int(B.lib().wlsqm_hip_krylov_workspace_bytes(self.npoints))
         self._ws = torch.zeros((nbytes // 8,), dtype=torch.float64, device=self._device)
+        if self._block is not None:
+            self._planes = self._new_planes()
+
+    def _new_planes(self):
+        import torch
+        nbytes = int(B.lib().wlsqm_hip_krylov_block_bytes(self.npoints, self._block.block))
+        return torch.zeros((nbytes // 8,), dtype=torch.float64, device=self._device)
 
     def _live(self):
         if getattr(self, "_ws", None) is None:
@@ -2009,14 +2039,14 @@ class StencilSolver:
 
     def close(self):
         """Release the workspace now; harmless when called again.  The operator stays the caller's."""
-        self._ws = self._op = None
+        self._ws = self._op = self._planes = self._planes_t = None
         if hasattr(self.__dict__.get("diag"), "dim"):
             self.diag = None
 
     def memory_used(self):
         """Bytes of device memory the solver holds (the operator's and a diag tensor are the caller's)."""
         self._live()
-        return self._ws.numel() * self._ws.element_size()
+        return sum(t.numel() * t.element_size() for t in (self._ws, self._planes, self._planes_t) if t is not None)
 
     def _vector(self, t, name):
         if not hasattr(t, "dim") or not hasattr(t, "is_cuda"):
@@ -2037,6 +2067,9 @@ class StencilSolver:
         held = dict(named, workspace=self._ws)
         if hasattr(self.diag, "dim"):
             held["diag"] = self.diag
+        for name, t in (("the preconditioner's blocks", self._planes), ("the preconditioner's transposed blocks", self._planes_t)):
+            if t is not None:
+                held[name] = t
         names = list(held)
         for i, a in enumerate(names):
             for b in names[i + 1:]:
@@ -2061,10 +2094,94 @@ class StencilSolver:
                 0.0 if hasattr(d, "dim") else d, self.scale)
 
     def _transposed(self, transpose, stream):
-        """The operator's transposed matrix, built at the first transposed use (prepare_transpose: RuntimeError inside a capture)."""
-        if transpose and self._op._t is None:
-            self._op.prepare_transpose(stream)
+        """The operator's transposed matrix, and a BlockJacobi's transposed plane, built at the first transposed use (prepare_transpose:
+        RuntimeError inside a capture)."""
+        if transpose and (self._op._t is None or (self._block is not None and self._planes_t is None)):
+            self.prepare_transpose(stream)
         return bool(transpose)
+
+    def prepare_transpose(self, stream=None):
+        """Build now what a transposed solve needs: the operator's transposed matrix (op.prepare_transpose) and, with a BlockJacobi, the
+        plane of the transposed inverse blocks.  Without this call the first transposed use builds them, which allocates — RuntimeError
+        when that would happen inside a graph capture.  The plane is filled by the next factor: at the next transposed start, from the
+        operator as it is then (also with refresh=False), and from then on together with the forward plane.  Returns True when this
+        call built something."""
+        import torch
+        self._live()
+        built = False
+        if self._op._t is None:
+            built = self._op.prepare_transpose(stream)
+        if self._block is not None and self._planes_t is None:
+            with _torch_stream(stream, self._device):
+                if self._device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("the solver has no transposed preconditioner blocks yet and the stream is capturing: call "
+                                       "prepare_transpose before the capture")
+                self._planes_t = self._new_planes()
+            self._factored_t = False
+            built = True
+        return built
+
+    def _block_args(self, transpose=False):
+        return self._block.block, _ptr(self._planes_t if transpose else self._planes)
+
+    def _factor(self, dev, s, transpose=False, force=False):
+        """"krylov-blocks" when P is due: at every start with refresh=True, else at the first one, when the transposed plane is new, and
+        from refresh().  One launch on the forward matrix, which fills the transposed plane too when this start needs it or, with
+        refresh=False, whenever it exists (the two stay the inverses of the same blocks)."""
+        bj = self._block
+        if not (force or bj.refresh or not self._factored or (transpose and not self._factored_t)):
+            return
+        both = self._planes_t is not None and (transpose or not bj.refresh or force)
+        B.check(B.lib().wlsqm_hip_krylov_block_factor_device(*self._system(False), bj.block, _ptr(self._planes),
+                                                             _ptr(self._planes_t) if both else None, dev, s))
+        self._factored = True
+        if both:
+            self._factored_t = True
+        elif bj.refresh:
+            self._factored_t = False
+
+    def refresh(self, stream=None):
+        """Recompute a BlockJacobi's P from the operator's arrays as they are on `stream` now: what refresh=False leaves to the caller
+        (after op.update, set_coefficients or a change of diag or scale).  One kernel launch, no allocation, no host read: capturable."""
+        self._live()
+        if self._block is None:
+            raise ValueError("refresh() belongs to a BlockJacobi preconditioner; this solver's is %s, which every solve recomputes"
+                             % ("'jacobi'" if self._jacobi else "None"))
+        s, dev = _stream_and_device(self._planes, stream)
+        self._factor(dev, s, force=True)
+        return self
+
+    def precondition(self, v, out=None, stream=None, transpose=False):
+        """z = P v (P^T v with transpose=True), P the BlockJacobi's block inverses as the next solve would use them: factored first when
+        due (refresh=True: always).  One launch ("krylov-precondition") behind the factor's; v and out (npoints,) float64 contiguous,
+        not overlapping.  ValueError on a solver without a BlockJacobi."""
+        import torch
+        self._live()
+        if self._block is None:
+            raise ValueError("precondition() belongs to a BlockJacobi preconditioner")
+        if out is None:
+            with _torch_stream(stream, self._device):
+                out = torch.empty((self.npoints,), dtype=torch.float64, device=self._device)
+        self._vectors(v=v, out=out)
+        transpose = self._transposed(transpose, stream)
+        s, dev = _stream_and_device(v, stream)
+        self._factor(dev, s, transpose)
+        B.check(B.lib().wlsqm_hip_krylov_block_precondition_device(self.npoints, *self._block_args(transpose), _ptr(v), _ptr(out), dev, s))
+        return out
+
+    def preconditioner_blocks(self, stream=None):
+        """The inverse blocks as a new tensor (nblocks, block, block), nblocks = ceil(npoints / block), factored first when due; the
+        padding of the last block is the identity.  It allocates the result, so it is not for a graph capture."""
+        self._live()
+        if self._block is None:
+            raise ValueError("preconditioner_blocks() belongs to a BlockJacobi preconditioner")
+        nb = self._block.block
+        s, dev = _stream_and_device(self._planes, stream)
+        self._factor(dev, s)
+        nslices = (self.npoints + 63) // 64
+        with _torch_stream(stream, self._device):
+            W = self._planes[:nslices * nb * 64].view(nslices, nb, 64 // nb, nb)          # [slice, j, block of the slice, i]
+            return W.permute(0, 2, 3, 1).reshape(-1, nb, nb)[:(self.npoints + nb - 1) // nb].clone()
 
     def _no_capture(self, what, stream):
         import torch
@@ -2074,10 +2191,19 @@ class StencilSolver:
                                    "and info() after the replay" % what)
 
     def _start(self, b, x, rtol, atol, maxiter, dev, s, transpose=False):
+        if self._block is not None:
+            self._factor(dev, s, transpose)
+            B.check(B.lib().wlsqm_hip_krylov_block_start_device(*self._system(transpose), *self._block_args(transpose), _ptr(b), _ptr(x),
+                                                                rtol, atol, maxiter, _ptr(self._ws), dev, s))
+            return
         B.check(B.lib().wlsqm_hip_krylov_start_device(*self._system(transpose), self._jacobi, _ptr(b), _ptr(x), rtol, atol, maxiter,
                                                       _ptr(self._ws), dev, s))
 
     def _iterate(self, x, niter, dev, s, transpose=False):
+        if self._block is not None:
+            B.check(B.lib().wlsqm_hip_krylov_block_bicgstab_device(*self._system(transpose), *self._block_args(transpose), _ptr(x), niter,
+                                                                   _ptr(self._ws), dev, s))
+            return
         B.check(B.lib().wlsqm_hip_krylov_bicgstab_device(*self._system(transpose), self._jacobi, _ptr(x), niter, _ptr(self._ws), dev, s))
 
     def enqueue(self, b, x, iterations, rtol=1e-10, atol=0.0, stream=None, transpose=False):
