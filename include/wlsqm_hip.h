@@ -650,6 +650,42 @@ int wlsqm_hip_krylov_block_bicgstab_device(int64_t nrows, int64_t nslices, const
 int wlsqm_hip_krylov_block_precondition_device(int64_t nrows, int block, const void* planes, const double* v, double* out, int device,
                                                void* stream);
 
+/* ---- stacked right-hand sides of those solves (extension; csrc/krylov.hip) ----
+ * nfields (1 .. 8) INDEPENDENT BiCGSTAB recurrences on the same M, one per field, in the launches of one: the matrix, and a block plane,
+ * are read once per pass for all of them.  This is not a block Krylov method: every field has its own scalars, its own threshold
+ * max(rtol * ||b_f||_2, atol) and its own stop, breakdown and non-finite checks, and the bits of field f — x, iterations, status, rr —
+ * are those of the single-field functions above on b_f and x_f alone, with every preconditioner.  A field that has stopped is frozen:
+ * no later launch writes its x or its scalars, while the others go on; a non-finite value in one field never reaches another.
+ * b and x are (nfields, nrows) with any strides, element (f, i) at [f * stride_field + i * stride_point] (in doubles); the elements
+ * of x must be distinct in memory.  precond: 0 none, 1 Jacobi, or 8 / 16 / 32: block-Jacobi with `planes` as
+ * wlsqm_hip_krylov_block_factor_device left it (nslices must then be ceil(nrows / 64); `planes` is ignored otherwise).  Status 4
+ * belongs to the matrix: it is set for every field before the first iteration, and x is untouched.
+ * The workspace: wlsqm_hip_krylov_many_workspace_bytes(nrows, nfields) bytes, 16-byte aligned; the size depends on nfields only through
+ * the pitch 2, 4 or 8 (the next one above nfields) at which the solver's own vectors are interleaved, v[i * pitch + f].  Its head is
+ * 8 blocks of 128 bytes, the scalars of field 0 .. 7 in the layout above, then one int32 `done_all` (set when every field has stopped:
+ * every kernel returns at its head then) in a block of 128 bytes: one read of 1152 bytes tells all.
+ * Nothing but kernel launches on `stream` ("krylov-diag", "krylov-spmv-many", "krylov-update-many", "krylov-update-block-many",
+ * "krylov-reduce-many"), as many as one single-field solve takes.  WLSQM_EVALUE as above, and for nfields outside 1 .. 8 or another precond.
+ *
+ * wlsqm_hip_krylov_many_start_device / _bicgstab_device: wlsqm_hip_krylov_start_device / _bicgstab_device for all fields.
+ * wlsqm_hip_krylov_many_product_device: out_f = M in_f with dot0 = (out_f, w_f) and dot1 = (out_f, out_f) in the scalars of field f; in,
+ *   w and out each with strides of their own; it has no preconditioner to name.  Not between a start and the end of its solve. */
+int64_t wlsqm_hip_krylov_many_workspace_bytes(int64_t nrows, int nfields);
+int wlsqm_hip_krylov_many_start_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                       const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                       int nfields, const double* b, int64_t b_stride_field, int64_t b_stride_point, const double* x,
+                                       int64_t x_stride_field, int64_t x_stride_point, int precond, const void* planes, double rtol,
+                                       double atol, int64_t maxiter, void* workspace, int device, void* stream);
+int wlsqm_hip_krylov_many_bicgstab_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                          const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                          int nfields, double* x, int64_t x_stride_field, int64_t x_stride_point, int precond,
+                                          const void* planes, int64_t niter, void* workspace, int device, void* stream);
+int wlsqm_hip_krylov_many_product_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                         const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                         int nfields, const double* in, int64_t in_stride_field, int64_t in_stride_point, const double* w,
+                                         int64_t w_stride_field, int64_t w_stride_point, double* out, int64_t out_stride_field,
+                                         int64_t out_stride_point, void* workspace, int device, void* stream);
+
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ---- */
 /* Runs `reps` back-to-back launches of the fit kernel for batch `b` (device-resident, uniform
  * order) on `stream`, bracketed by HIP events on that stream; returns the mean kernel time in

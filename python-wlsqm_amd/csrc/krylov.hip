@@ -258,19 +258,8 @@ enum { REDUCE_DIAG = 0, REDUCE_RESIDUAL = 1, REDUCE_ALPHA = 2, REDUCE_OMEGA = 3,
 
 __device__ __forceinline__ void krylov_stop(KrylovScalars* sc, int status) { sc->status = status; sc->done = 1; }
 
-// One workgroup: the partials of both planes in index order (thread t takes t, t + 256, ...), then the scalar step of `mode` in one lane.
-__global__ void __launch_bounds__(256) krylov_reduce_kernel(int mode, const double* partial, long long nwg, int planes, KrylovScalars* sc,
-                                                            double rtol, double atol, int maxiter) {
-    if (mode != REDUCE_DIAG && mode != REDUCE_PRODUCT && mode != REDUCE_NEGATED && sc->done) return;      // uniform
-    __shared__ double sums[2];
-    double a = 0.0, b = 0.0;
-    for (long long i = threadIdx.x; i < nwg; i += 256) {
-        a += partial[i];
-        if (planes > 1) b += partial[nwg + i];
-    }
-    block_sums<true>(a, b, sums, 1);                             // blockIdx.x == 0: sums[0], sums[1]
-    if (threadIdx.x != 0) return;
-    const double s0 = sums[0], s1 = sums[1];
+// The scalar step of `mode` on the sums s0 and s1 of its dot products: one lane.
+__device__ __forceinline__ void krylov_scalar_step(int mode, KrylovScalars* sc, double s0, double s1, double rtol, double atol, int maxiter) {
     switch (mode) {
     case REDUCE_DIAG:                                            // the start of a solve: s0 counts the unusable diagonal entries
         sc->rho = sc->rho_old = sc->alpha = sc->omega = 1.0;
@@ -321,6 +310,21 @@ __global__ void __launch_bounds__(256) krylov_reduce_kernel(int mode, const doub
         sc->dot0 = s0; sc->dot1 = s1;
         break;
     }
+}
+
+// One workgroup: the partials of both planes in index order (thread t takes t, t + 256, ...), then the scalar step of `mode` in one lane.
+__global__ void __launch_bounds__(256) krylov_reduce_kernel(int mode, const double* partial, long long nwg, int planes, KrylovScalars* sc,
+                                                            double rtol, double atol, int maxiter) {
+    if (mode != REDUCE_DIAG && mode != REDUCE_PRODUCT && mode != REDUCE_NEGATED && sc->done) return;      // uniform
+    __shared__ double sums[2];
+    double a = 0.0, b = 0.0;
+    for (long long i = threadIdx.x; i < nwg; i += 256) {
+        a += partial[i];
+        if (planes > 1) b += partial[nwg + i];
+    }
+    block_sums<true>(a, b, sums, 1);                             // blockIdx.x == 0: sums[0], sums[1]
+    if (threadIdx.x != 0) return;
+    krylov_scalar_step(mode, sc, sums[0], sums[1], rtol, atol, maxiter);
 }
 
 static int krylov_system(const char* who, KrylovSys& m, int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width,
@@ -525,6 +529,484 @@ static void krylov_block_iterations(const KrylovSys& m, const KrylovWork& w, con
         hipLaunchKernelGGL((krylov_update_kernel<UPDATE_X>), grid, dim3(256), 0, s, nrows, w, x, sc);
         krylov_reduce(REDUCE_RHO, w, w.nwg, 2, 0.0, 0.0, 0, s);
     }
+}
+
+// ---- stacked right-hand sides: R <= 8 independent recurrences on one matrix, one pass over it for all of them --
+// The solver's own vectors are interleaved at the pitch P (2, 4 or 8, the next one above nfields): v[point * P + field], so that the P
+// values of a neighbour are one contiguous load of 8 P bytes.  The caller's b and x stay (nfields, npoints) with any strides.  Every field
+// has its own KrylovScalars; the bits of field r are those of the single-field kernels above on b_r, x_r alone: the same lane per row, the
+// same fma chain, the same trees, per field.  A field that has stopped is frozen: its stores are predicated off (`frozen`, uniform over
+// the grid), the others go on.  The fields nfields .. P - 1 are computed from zeros and stored with the rest: they live in the workspace
+// only.  `done_all` is written by the reduce kernel's one writer and read at the head of every kernel.
+
+constexpr int KRYLOV_MANY_FIELDS = 8;
+
+struct KrylovManyHead {                 // wlsqm/hip.py reads it as 8 x (8 doubles, 4 int32, 6 doubles) and one int32
+    KrylovScalars f[KRYLOV_MANY_FIELDS];
+    int done_all;
+    int pad[31];                        // 128 bytes: what follows stays 16-byte aligned, as the 16-byte loads need
+};
+constexpr long long KRYLOV_MANY_HEAD = sizeof(KrylovManyHead) / sizeof(double);
+constexpr int KRYLOV_MANY_VECTORS = 8;  // r, r0, p, v, s, t, phat, shat at the pitch; dinv is one double per point behind them
+
+__host__ __device__ static inline int krylov_pitch(int nfields) { return nfields <= 2 ? 2 : nfields <= 4 ? 4 : 8; }
+__host__ __device__ static inline long long krylov_many_partials(long long nwg, int pitch) { return (2 * pitch * nwg + 7) / 8 * 8; }
+
+struct KrylovManyWork {
+    KrylovManyHead* head; double* partial; long long nwg;       // partial: planes [sum][field][workgroup], 2 P nwg doubles
+    double *r, *r0, *p, *v, *s, *t, *phat, *shat, *dinv;
+};
+
+static KrylovManyWork krylov_many_work(void* workspace, long long nrows, int pitch, bool preconditioned) {
+    KrylovManyWork w;
+    double* base = static_cast<double*>(workspace);
+    w.head = static_cast<KrylovManyHead*>(workspace);
+    w.nwg = (nrows + 255) / 256;
+    w.partial = base + KRYLOV_MANY_HEAD;
+    double* vec = w.partial + krylov_many_partials(w.nwg, pitch);
+    const long long n = nrows * pitch;
+    w.r = vec; w.r0 = vec + n; w.p = vec + 2 * n; w.v = vec + 3 * n; w.s = vec + 4 * n; w.t = vec + 5 * n;
+    w.phat = preconditioned ? vec + 6 * n : w.p; w.shat = preconditioned ? vec + 7 * n : w.s;
+    w.dinv = vec + 8 * n;
+    return w;
+}
+
+struct KrylovFields {                   // a caller's (nfields, npoints) array: element (field, point) at at[field * sf + point * sp]
+    double* at; long long sf, sp;
+};
+
+typedef double krylov_pair __attribute__((ext_vector_type(2)));
+
+// The P fields of one point of an interleaved vector: 16-byte loads and stores (`at` is 16-byte aligned).
+template <int P>
+__device__ __forceinline__ void krylov_load_fields(const double* at, double (&f)[P]) {
+#pragma unroll
+    for (int q = 0; q < P; q += 2) {
+        const krylov_pair two = *reinterpret_cast<const krylov_pair*>(at + q);
+        f[q] = two.x; f[q + 1] = two.y;
+    }
+}
+
+template <int P>
+__device__ __forceinline__ void krylov_store_fields(double* at, const double (&f)[P], unsigned frozen) {
+    if (frozen == 0) {                                           // uniform
+#pragma unroll
+        for (int q = 0; q < P; q += 2) {
+            krylov_pair two;
+            two.x = f[q]; two.y = f[q + 1];
+            *reinterpret_cast<krylov_pair*>(at + q) = two;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < P; ++q)
+            if (!((frozen >> q) & 1u)) at[q] = f[q];
+    }
+}
+
+// Bit q: field q of the solve has stopped, and nothing of it may be written any more.
+template <int P>
+__device__ __forceinline__ unsigned krylov_frozen(const KrylovManyHead* head, int nfields) {
+    unsigned frozen = 0;
+#pragma unroll
+    for (int q = 0; q < P; ++q)
+        if (q < nfields && head->f[q].done) frozen |= 1u << q;
+    return frozen;
+}
+
+template <int P> struct KrylovPacked {                           // the workspace's layout
+    const double* at;
+    __device__ __forceinline__ void load(long long point, double (&f)[P]) const { krylov_load_fields<P>(at + point * P, f); }
+};
+
+template <int P> struct KrylovStrided {                          // the caller's; the fields beyond nfields read as zeros
+    const double* at; long long sf, sp; int nfields;
+    __device__ __forceinline__ void load(long long point, double (&f)[P]) const {
+#pragma unroll
+        for (int q = 0; q < P; ++q) f[q] = q < nfields ? at[q * sf + point * sp] : 0.0;
+    }
+};
+
+// krylov_row_sum for P fields: col and val are loaded once per entry, each field's sum is its own fma chain in entry order.
+template <int P, class In>
+__device__ __forceinline__ void krylov_row_sums(const int32_t* col, const double* val, const In& x, int wid, int n, double (&acc)[P]) {
+    constexpr int UNROLL = 16 / P;                               // 128 bytes of x in flight per lane and batch, whatever the pitch
+#pragma unroll
+    for (int q = 0; q < P; ++q) acc[q] = 0.0;
+    for (int e = 0; e < wid; e += UNROLL) {                      // wave-uniform
+        if (e + UNROLL <= n) {
+            double xs[UNROLL][P], vs[UNROLL];
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) {
+                const long long c = col[64LL * (e + u)];
+                x.load(c, xs[u]);
+                vs[u] = val[64LL * (e + u)];
+            }
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u)
+#pragma unroll
+                for (int q = 0; q < P; ++q) acc[q] = __builtin_fma(vs[u], xs[u][q], acc[q]);
+        } else {
+            for (int u = 0; u < UNROLL && e + u < n; ++u) {
+                const long long c = col[64LL * (e + u)];
+                const double v = val[64LL * (e + u)];
+                double xs[P];
+                x.load(c, xs);
+#pragma unroll
+                for (int q = 0; q < P; ++q) acc[q] = __builtin_fma(v, xs[q], acc[q]);
+            }
+        }
+    }
+}
+
+// block_sums per field: partial[(plane * P + field) * nwg + blockIdx.x], each sum by block_sums' tree and wave order.
+template <int P, bool TWO>
+__device__ __forceinline__ void block_sums_many(double (&a)[P], double (&b)[P], double* partial, long long nwg) {
+    __shared__ double part[2][P][4];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int q = 0; q < P; ++q) {
+            a[q] += __shfl_down(a[q], off, 64);
+            if (TWO) b[q] += __shfl_down(b[q], off, 64);
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < P; ++q) { part[0][q][wave] = a[q]; if (TWO) part[1][q][wave] = b[q]; }
+    }
+    __syncthreads();
+    if (threadIdx.x < (TWO ? 2 : 1) * P) {
+        const int plane = threadIdx.x / P, q = threadIdx.x % P;
+        const double* w = part[plane][q];
+        partial[(plane * P + q) * nwg + blockIdx.x] = ((w[0] + w[1]) + w[2]) + w[3];
+    }
+}
+
+enum { SPMV_MANY_START = 0, SPMV_MANY_V = 1, SPMV_MANY_T = 2, SPMV_MANY_PRODUCT = 3 };
+
+// krylov_spmv_kernel for P fields, y_q = M in_q:
+//   START:   in = x and w = b the caller's; out = out2 = b - y interleaved, partials (out, out) and (b, b)
+//   V:       all interleaved; out = y, partial (w, out)
+//   T:       all interleaved; out = y, partials (out, w) and (out, out)
+//   PRODUCT: T on the caller's in, w and out, whatever the state of a solve
+template <int P, int MODE>
+__global__ void __launch_bounds__(256) krylov_spmv_many_kernel(const KrylovSys m, int nfields, const KrylovFields in, const KrylovFields w,
+                                                               const KrylovFields out, double* out2, double* partial,
+                                                               const KrylovManyHead* head) {
+    constexpr bool CALLERS_IN = MODE == SPMV_MANY_START || MODE == SPMV_MANY_PRODUCT;
+    if (MODE != SPMV_MANY_PRODUCT && head->done_all) return;     // uniform: the whole grid
+    const unsigned frozen = MODE == SPMV_MANY_PRODUCT ? 0u : krylov_frozen<P>(head, nfields);
+    const int lane = threadIdx.x & 63;
+    const long long s = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long row = s * 64 + lane;
+    double a[P], b[P];
+#pragma unroll
+    for (int q = 0; q < P; ++q) a[q] = b[q] = 0.0;
+    if (s * 64 < m.nrows) {                                      // wave-uniform
+        const int wid = __builtin_amdgcn_readfirstlane(m.width[s]);
+        const long long at = m.soff[s] + lane;
+        int n = row < m.nrows ? m.len[row] : 0;
+        n = n < wid ? n : wid;
+        double sum[P], xi[P], wi[P], y[P];
+        const KrylovStrided<P> xin{in.at, in.sf, in.sp, nfields}, win{w.at, w.sf, w.sp, nfields};
+        const KrylovPacked<P> xpk{in.at}, wpk{w.at};
+        if (CALLERS_IN) krylov_row_sums<P>(m.col + at, m.val + at, xin, wid, n, sum);
+        else krylov_row_sums<P>(m.col + at, m.val + at, xpk, wid, n, sum);
+        if (row < m.nrows) {
+            const double d = m.dvec ? m.dvec[row] : m.dconst;
+            if (CALLERS_IN) { xin.load(row, xi); win.load(row, wi); }
+            else { xpk.load(row, xi); wpk.load(row, wi); }
+#pragma unroll
+            for (int q = 0; q < P; ++q) y[q] = __builtin_fma(m.c, sum[q], d * xi[q]);
+            if (MODE == SPMV_MANY_START) {
+#pragma unroll
+                for (int q = 0; q < P; ++q) {
+                    y[q] = wi[q] - y[q];
+                    a[q] = y[q] * y[q]; b[q] = wi[q] * wi[q];
+                }
+                krylov_store_fields<P>(out.at + row * P, y, frozen);
+                krylov_store_fields<P>(out2 + row * P, y, frozen);
+            } else {
+#pragma unroll
+                for (int q = 0; q < P; ++q) {
+                    a[q] = wi[q] * y[q];
+                    if (MODE != SPMV_MANY_V) b[q] = y[q] * y[q];
+                }
+                if (MODE == SPMV_MANY_PRODUCT) {
+#pragma unroll
+                    for (int q = 0; q < P; ++q)
+                        if (q < nfields) out.at[q * out.sf + row * out.sp] = y[q];
+                } else {
+                    krylov_store_fields<P>(out.at + row * P, y, frozen);
+                }
+            }
+        }
+    }
+    block_sums_many<P, MODE != SPMV_MANY_V>(a, b, partial, gridDim.x);
+}
+
+// p_q = r_q + beta_q (p_q - omega_q v_q) (a field's first iteration: p_q = r_q), with the field's own scalars.
+template <int P>
+__device__ __forceinline__ void krylov_next_p(const KrylovManyWork& k, long long i, double (&p)[P]) {
+    double r[P], po[P], v[P];
+    krylov_load_fields<P>(k.r + i * P, r);
+    krylov_load_fields<P>(k.p + i * P, po);
+    krylov_load_fields<P>(k.v + i * P, v);
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+        const KrylovScalars* sc = &k.head->f[q];
+        p[q] = r[q];
+        if (sc->iterations > 0) {                                // uniform
+            const double omega = sc->omega, beta = (sc->rho / sc->rho_old) * (sc->alpha / omega);
+            p[q] = r[q] + beta * (po[q] - omega * v[q]);
+        }
+    }
+}
+
+// s_q = r_q - alpha_q v_q
+template <int P>
+__device__ __forceinline__ void krylov_next_s(const KrylovManyWork& k, long long i, double (&s)[P]) {
+    double r[P], v[P];
+    krylov_load_fields<P>(k.r + i * P, r);
+    krylov_load_fields<P>(k.v + i * P, v);
+#pragma unroll
+    for (int q = 0; q < P; ++q) s[q] = r[q] - k.head->f[q].alpha * v[q];
+}
+
+// krylov_update_kernel for P fields; dinv (nullable: phat is p and shat is s) is the matrix's and serves every field.
+template <int P, int MODE>
+__global__ void __launch_bounds__(256) krylov_update_many_kernel(long long nrows, const KrylovManyWork k, const double* dinv, int nfields,
+                                                                 const KrylovFields x) {
+    if (k.head->done_all) return;                                // uniform: the whole grid
+    const unsigned frozen = krylov_frozen<P>(k.head, nfields);
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (MODE != UPDATE_X) {
+        if (i >= nrows) return;
+        double u[P];
+        if (MODE == UPDATE_P) krylov_next_p<P>(k, i, u);
+        else krylov_next_s<P>(k, i, u);
+        krylov_store_fields<P>((MODE == UPDATE_P ? k.p : k.s) + i * P, u, frozen);
+        if (dinv) {
+            const double di = dinv[i];
+#pragma unroll
+            for (int q = 0; q < P; ++q) u[q] = di * u[q];
+            krylov_store_fields<P>((MODE == UPDATE_P ? k.phat : k.shat) + i * P, u, frozen);
+        }
+    } else {
+        double a[P], b[P];
+#pragma unroll
+        for (int q = 0; q < P; ++q) a[q] = b[q] = 0.0;
+        if (i < nrows) {
+            double ph[P], sh[P], s[P], t[P], r0[P], r[P];
+            krylov_load_fields<P>(k.phat + i * P, ph);
+            krylov_load_fields<P>(k.shat + i * P, sh);
+            krylov_load_fields<P>(k.s + i * P, s);
+            krylov_load_fields<P>(k.t + i * P, t);
+            krylov_load_fields<P>(k.r0 + i * P, r0);
+#pragma unroll
+            for (int q = 0; q < P; ++q) {
+                const double alpha = k.head->f[q].alpha, omega = k.head->f[q].omega;
+                if (q < nfields && !((frozen >> q) & 1u)) {      // uniform
+                    double* xq = x.at + q * x.sf + i * x.sp;
+                    *xq = *xq + (alpha * ph[q] + omega * sh[q]);
+                }
+                r[q] = s[q] - omega * t[q];
+                a[q] = r0[q] * r[q]; b[q] = r[q] * r[q];
+            }
+            krylov_store_fields<P>(k.r + i * P, r, frozen);
+        }
+        block_sums_many<P, true>(a, b, k.partial, gridDim.x);
+    }
+}
+
+// krylov_update_block_kernel for P fields: a column of W is loaded once and applied to every field, each field's p_(first + j) by its
+// own cross-lane move.
+template <int NB, int P, int MODE>
+__global__ void __launch_bounds__(256) krylov_update_block_many_kernel(long long nrows, const KrylovManyWork k, const double* W, int nfields) {
+    if (k.head->done_all) return;                                // uniform: the whole grid
+    const unsigned frozen = krylov_frozen<P>(k.head, nfields);
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63, b0 = lane & ~(NB - 1);
+    const long long s = i >> 6;
+    if (s * 64 >= nrows) return;                                 // wave-uniform
+    const bool live = i < nrows;
+    double u[P], z[P];
+#pragma unroll
+    for (int q = 0; q < P; ++q) u[q] = z[q] = 0.0;
+    if (live) {
+        if (MODE == UPDATE_P) krylov_next_p<P>(k, i, u);
+        else krylov_next_s<P>(k, i, u);
+        krylov_store_fields<P>((MODE == UPDATE_P ? k.p : k.s) + i * P, u, frozen);
+    }
+    const double* w = W + (s * NB) * 64 + lane;
+#pragma unroll 4                                                 // four columns of W in flight: unrolled further, P = 8 runs out of registers
+    for (int j = 0; j < NB; ++j) {
+        const double wj = w[64LL * j];
+#pragma unroll
+        for (int q = 0; q < P; ++q) z[q] = __builtin_fma(wj, __shfl(u[q], b0 + j, 64), z[q]);
+    }
+    if (live) krylov_store_fields<P>((MODE == UPDATE_P ? k.phat : k.shat) + i * P, z, frozen);
+}
+
+// krylov_reduce_kernel for P fields: one workgroup, each field's partials in krylov_reduce_kernel's order, then one lane runs the scalar
+// step field after field and writes done_all.  REDUCE_DIAG: `partial` is one plane of counts, which belongs to the matrix and so to every
+// field; the heads beyond nfields are set to a solve that has stopped.
+template <int P>
+__global__ void __launch_bounds__(256) krylov_reduce_many_kernel(int mode, const double* partial, long long nwg, int planes,
+                                                                 KrylovManyHead* head, int nfields, double rtol, double atol, int maxiter) {
+    const bool iterating = mode != REDUCE_DIAG && mode != REDUCE_PRODUCT;
+    if (iterating && head->done_all) return;                     // uniform
+    __shared__ double part[2][P][4];
+    // every field's sum is thread t's t, t + 256, ... in that order; the loads of four such steps of all fields are in flight together
+    // (field after field, one load at a time, this kernel took eight times the single-field one's time at P = 8)
+    constexpr int STEPS = 4;
+    double a[P], b[P];
+    bool take[P];
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+        a[q] = b[q] = 0.0;
+        take[q] = mode == REDUCE_DIAG ? q == 0 : q < nfields && !(iterating && head->f[q].done);              // uniform
+    }
+    for (long long i0 = threadIdx.x; i0 < nwg; i0 += 256 * STEPS) {
+        double va[STEPS][P], vb[STEPS][P];
+#pragma unroll
+        for (int u = 0; u < STEPS; ++u) {
+            const long long i = i0 + 256 * u;
+#pragma unroll
+            for (int q = 0; q < P; ++q) {
+                const bool on = take[q] && i < nwg;
+                va[u][q] = on ? partial[q * nwg + i] : 0.0;
+                vb[u][q] = on && planes > 1 ? partial[(P + q) * nwg + i] : 0.0;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < STEPS; ++u) {
+            if (i0 + 256 * u < nwg) {
+#pragma unroll
+                for (int q = 0; q < P; ++q) {
+                    if (take[q]) a[q] += va[u][q];
+                    if (take[q] && planes > 1) b[q] += vb[u][q];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int q = 0; q < P; ++q) {
+            a[q] += __shfl_down(a[q], off, 64);
+            b[q] += __shfl_down(b[q], off, 64);
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < P; ++q) { part[0][q][wave] = a[q]; part[1][q][wave] = b[q]; }
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    if (mode == REDUCE_DIAG) {
+        const double bad = ((part[0][0][0] + part[0][0][1]) + part[0][0][2]) + part[0][0][3];
+        for (int q = 0; q < KRYLOV_MANY_FIELDS; ++q) {
+            KrylovScalars* sc = &head->f[q];
+            krylov_scalar_step(mode, sc, bad, 0.0, rtol, atol, maxiter);
+            if (q >= nfields) { sc->rr = 0.0; krylov_stop(sc, KRYLOV_CONVERGED); }
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < P; ++q) {
+            if (q >= nfields || (iterating && head->f[q].done)) continue;
+            const double s0 = ((part[0][q][0] + part[0][q][1]) + part[0][q][2]) + part[0][q][3];
+            const double s1 = ((part[1][q][0] + part[1][q][1]) + part[1][q][2]) + part[1][q][3];
+            krylov_scalar_step(mode, &head->f[q], s0, s1, rtol, atol, maxiter);
+        }
+    }
+    if (mode == REDUCE_PRODUCT) return;
+    int all = 1;
+    for (int q = 0; q < nfields; ++q) all &= head->f[q].done ? 1 : 0;
+    head->done_all = all;
+}
+
+static bool krylov_many_precond(int precond) { return precond == 0 || precond == 1 || precond == 8 || precond == 16 || precond == 32; }
+
+static int krylov_many_arguments(const char* who, int64_t nrows, int64_t nslices, int nfields, int precond, const void* planes,
+                                 const void* workspace) {
+    if (reinterpret_cast<uintptr_t>(workspace) % 16) { set_error(std::string(who) + ": the workspace must be 16-byte aligned"); return WLSQM_EVALUE; }
+    if (nfields < 1 || nfields > KRYLOV_MANY_FIELDS) { set_error(std::string(who) + ": nfields must be 1 .. 8"); return WLSQM_EVALUE; }
+    if (!krylov_many_precond(precond)) { set_error(std::string(who) + ": precond must be 0, 1, 8, 16 or 32"); return WLSQM_EVALUE; }
+    if (precond > 1) {
+        if (!planes) { set_error(std::string(who) + ": null array"); return WLSQM_EVALUE; }
+        if (nslices != (nrows + 63) / 64) { set_error(std::string(who) + ": nslices must be ceil(nrows / 64)"); return WLSQM_EVALUE; }
+    }
+    return WLSQM_OK;
+}
+
+template <int P>
+static void krylov_many_reduce(int mode, const double* partial, long long nwg, int planes, const KrylovManyWork& w, int nfields, double rtol,
+                               double atol, int maxiter, hipStream_t s) {
+    hipLaunchKernelGGL(krylov_reduce_many_kernel<P>, dim3(1), dim3(256), 0, s, mode, partial, nwg, planes, w.head, nfields, rtol, atol, maxiter);
+}
+
+template <int P>
+static void krylov_many_start(const KrylovSys& m, const KrylovManyWork& w, int nfields, const KrylovFields& b, const KrylovFields& x,
+                              int precond, const void* planes, int64_t nslices, double rtol, double atol, int maxiter, hipStream_t s) {
+    const dim3 grid((unsigned)w.nwg);
+    if (precond == 1) {
+        hipLaunchKernelGGL(krylov_diag_kernel, grid, dim3(256), 0, s, m, w.dinv, w.partial);
+        note_kernel("krylov-diag");
+    }
+    const double* counts = precond > 1 ? static_cast<const double*>(planes) + krylov_plane_doubles(nslices, precond) : w.partial;
+    krylov_many_reduce<P>(REDUCE_DIAG, counts, precond ? w.nwg : 0, 1, w, nfields, rtol, atol, maxiter, s);
+    hipLaunchKernelGGL((krylov_spmv_many_kernel<P, SPMV_MANY_START>), grid, dim3(256), 0, s, m, nfields, x, b, KrylovFields{w.r, 0, 0}, w.r0,
+                       w.partial, (const KrylovManyHead*)w.head);
+    note_kernel("krylov-spmv-many");
+    krylov_many_reduce<P>(REDUCE_RESIDUAL, w.partial, w.nwg, 2, w, nfields, rtol, atol, maxiter, s);
+    note_kernel("krylov-reduce-many");
+}
+
+// NB 0: the Jacobi diagonal (w.dinv) or, with dinv null, no preconditioner.
+template <int P, int NB>
+static void krylov_many_iterations(const KrylovSys& m, const KrylovManyWork& w, int nfields, const KrylovFields& x, const double* dinv,
+                                   const double* W, int64_t niter, hipStream_t s) {
+    const dim3 grid((unsigned)w.nwg), block(256);
+    const KrylovManyHead* head = w.head;
+    const long long nrows = m.nrows;
+    const KrylovFields none{nullptr, 0, 0};
+    for (int64_t it = 0; it < niter; ++it) {
+        if constexpr (NB > 0) hipLaunchKernelGGL((krylov_update_block_many_kernel<NB, P, UPDATE_P>), grid, block, 0, s, nrows, w, W, nfields);
+        else hipLaunchKernelGGL((krylov_update_many_kernel<P, UPDATE_P>), grid, block, 0, s, nrows, w, dinv, nfields, none);
+        hipLaunchKernelGGL((krylov_spmv_many_kernel<P, SPMV_MANY_V>), grid, block, 0, s, m, nfields, KrylovFields{w.phat, 0, 0},
+                           KrylovFields{w.r0, 0, 0}, KrylovFields{w.v, 0, 0}, (double*)nullptr, w.partial, head);
+        krylov_many_reduce<P>(REDUCE_ALPHA, w.partial, w.nwg, 1, w, nfields, 0.0, 0.0, 0, s);
+        if constexpr (NB > 0) hipLaunchKernelGGL((krylov_update_block_many_kernel<NB, P, UPDATE_S>), grid, block, 0, s, nrows, w, W, nfields);
+        else hipLaunchKernelGGL((krylov_update_many_kernel<P, UPDATE_S>), grid, block, 0, s, nrows, w, dinv, nfields, none);
+        hipLaunchKernelGGL((krylov_spmv_many_kernel<P, SPMV_MANY_T>), grid, block, 0, s, m, nfields, KrylovFields{w.shat, 0, 0},
+                           KrylovFields{w.s, 0, 0}, KrylovFields{w.t, 0, 0}, (double*)nullptr, w.partial, head);
+        krylov_many_reduce<P>(REDUCE_OMEGA, w.partial, w.nwg, 2, w, nfields, 0.0, 0.0, 0, s);
+        hipLaunchKernelGGL((krylov_update_many_kernel<P, UPDATE_X>), grid, block, 0, s, nrows, w, dinv, nfields, x);
+        krylov_many_reduce<P>(REDUCE_RHO, w.partial, w.nwg, 2, w, nfields, 0.0, 0.0, 0, s);
+    }
+}
+
+template <int P>
+static void krylov_many_iterate(const KrylovSys& m, const KrylovManyWork& w, int nfields, const KrylovFields& x, int precond, const void* planes,
+                                int64_t niter, hipStream_t s) {
+    const double* W = static_cast<const double*>(planes);
+    switch (precond) {
+    case 8: krylov_many_iterations<P, 8>(m, w, nfields, x, nullptr, W, niter, s); break;
+    case 16: krylov_many_iterations<P, 16>(m, w, nfields, x, nullptr, W, niter, s); break;
+    case 32: krylov_many_iterations<P, 32>(m, w, nfields, x, nullptr, W, niter, s); break;
+    default: krylov_many_iterations<P, 0>(m, w, nfields, x, precond ? w.dinv : nullptr, nullptr, niter, s); break;
+    }
+}
+
+template <int P>
+static void krylov_many_product(const KrylovSys& m, const KrylovManyWork& k, int nfields, const KrylovFields& in, const KrylovFields& w,
+                                const KrylovFields& out, hipStream_t s) {
+    hipLaunchKernelGGL((krylov_spmv_many_kernel<P, SPMV_MANY_PRODUCT>), dim3((unsigned)k.nwg), dim3(256), 0, s, m, nfields, in, w, out,
+                       (double*)nullptr, k.partial, (const KrylovManyHead*)k.head);
+    krylov_many_reduce<P>(REDUCE_PRODUCT, k.partial, k.nwg, 2, k, nfields, 0.0, 0.0, 0, s);
 }
 
 }  // namespace wlsqm
@@ -758,6 +1240,102 @@ int wlsqm_hip_krylov_block_precondition_device(int64_t nrows, int block, const v
     }
     WLSQM_HIP_CHECK(hipGetLastError());
     note_kernel("krylov-precondition");
+    return WLSQM_OK;
+}
+
+int64_t wlsqm_hip_krylov_many_workspace_bytes(int64_t nrows, int nfields) {
+    if (nrows < 0 || nfields < 1 || nfields > KRYLOV_MANY_FIELDS) return -1;
+    const int pitch = krylov_pitch(nfields);
+    return (int64_t)sizeof(double) * (KRYLOV_MANY_HEAD + krylov_many_partials((nrows + 255) / 256, pitch)
+                                      + (int64_t)KRYLOV_MANY_VECTORS * pitch * nrows + nrows);
+}
+
+int wlsqm_hip_krylov_many_start_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                       const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                       int nfields, const double* b, int64_t b_stride_field, int64_t b_stride_point, const double* x,
+                                       int64_t x_stride_field, int64_t x_stride_point, int precond, const void* planes, double rtol,
+                                       double atol, int64_t maxiter, void* workspace, int device, void* stream) {
+    KrylovSys m;
+    int rc = krylov_system("krylov_many_start", m, nrows, nslices, len, width, soff, col, val, diag, diag_const, scale, workspace);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_many_arguments("krylov_many_start", nrows, nslices, nfields, precond, planes, workspace);
+    if (rc != WLSQM_OK) return rc;
+    if (!b || !x) { set_error("krylov_many_start: null array"); return WLSQM_EVALUE; }
+    if (!(rtol >= 0.0) || !(atol >= 0.0) || !std::isfinite(rtol) || !std::isfinite(atol)) {
+        set_error("krylov_many_start: rtol and atol must be finite and >= 0");
+        return WLSQM_EVALUE;
+    }
+    if (maxiter < 0 || maxiter > INT32_MAX) { set_error("krylov_many_start: maxiter must be 0 .. 2^31 - 1"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int pitch = krylov_pitch(nfields);
+    const KrylovManyWork w = krylov_many_work(workspace, nrows, pitch, precond != 0);
+    const KrylovFields bf{const_cast<double*>(b), b_stride_field, b_stride_point}, xf{const_cast<double*>(x), x_stride_field, x_stride_point};
+    switch (pitch) {
+    case 2: krylov_many_start<2>(m, w, nfields, bf, xf, precond, planes, nslices, rtol, atol, (int)maxiter, s); break;
+    case 4: krylov_many_start<4>(m, w, nfields, bf, xf, precond, planes, nslices, rtol, atol, (int)maxiter, s); break;
+    default: krylov_many_start<8>(m, w, nfields, bf, xf, precond, planes, nslices, rtol, atol, (int)maxiter, s); break;
+    }
+    WLSQM_HIP_CHECK(hipGetLastError());
+    return WLSQM_OK;
+}
+
+int wlsqm_hip_krylov_many_bicgstab_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                          const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                          int nfields, double* x, int64_t x_stride_field, int64_t x_stride_point, int precond,
+                                          const void* planes, int64_t niter, void* workspace, int device, void* stream) {
+    KrylovSys m;
+    int rc = krylov_system("krylov_many_bicgstab", m, nrows, nslices, len, width, soff, col, val, diag, diag_const, scale, workspace);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_many_arguments("krylov_many_bicgstab", nrows, nslices, nfields, precond, planes, workspace);
+    if (rc != WLSQM_OK) return rc;
+    if (!x) { set_error("krylov_many_bicgstab: null array"); return WLSQM_EVALUE; }
+    if (niter < 0) { set_error("krylov_many_bicgstab: niter must be >= 0"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK || niter == 0) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int pitch = krylov_pitch(nfields);
+    const KrylovManyWork w = krylov_many_work(workspace, nrows, pitch, precond != 0);
+    const KrylovFields xf{x, x_stride_field, x_stride_point};
+    switch (pitch) {
+    case 2: krylov_many_iterate<2>(m, w, nfields, xf, precond, planes, niter, s); break;
+    case 4: krylov_many_iterate<4>(m, w, nfields, xf, precond, planes, niter, s); break;
+    default: krylov_many_iterate<8>(m, w, nfields, xf, precond, planes, niter, s); break;
+    }
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel(precond > 1 ? "krylov-update-block-many" : "krylov-update-many");
+    return WLSQM_OK;
+}
+
+int wlsqm_hip_krylov_many_product_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                         const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                         int nfields, const double* in, int64_t in_stride_field, int64_t in_stride_point, const double* w,
+                                         int64_t w_stride_field, int64_t w_stride_point, double* out, int64_t out_stride_field,
+                                         int64_t out_stride_point, void* workspace, int device, void* stream) {
+    KrylovSys m;
+    int rc = krylov_system("krylov_many_product", m, nrows, nslices, len, width, soff, col, val, diag, diag_const, scale, workspace);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_many_arguments("krylov_many_product", nrows, nslices, nfields, 0, nullptr, workspace);
+    if (rc != WLSQM_OK) return rc;
+    if (!in || !w || !out) { set_error("krylov_many_product: null array"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int pitch = krylov_pitch(nfields);
+    const KrylovManyWork k = krylov_many_work(workspace, nrows, pitch, false);
+    const KrylovFields inf{const_cast<double*>(in), in_stride_field, in_stride_point}, wf{const_cast<double*>(w), w_stride_field, w_stride_point},
+        outf{out, out_stride_field, out_stride_point};
+    switch (pitch) {
+    case 2: krylov_many_product<2>(m, k, nfields, inf, wf, outf, s); break;
+    case 4: krylov_many_product<4>(m, k, nfields, inf, wf, outf, s); break;
+    default: krylov_many_product<8>(m, k, nfields, inf, wf, outf, s); break;
+    }
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-spmv-many");
     return WLSQM_OK;
 }
 

@@ -219,6 +219,19 @@ def lib():
         L.wlsqm_hip_krylov_block_precondition_device.argtypes = [C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         for name in ("factor", "start", "bicgstab", "precondition"):
             getattr(L, "wlsqm_hip_krylov_block_%s_device" % name).restype = C.c_int
+    # stacked right-hand sides of those solves (StencilSolver(nfields=...).solve_many)
+    if hasattr(L, "wlsqm_hip_krylov_many_start_device"):
+        system = [C.c_int64, C.c_int64] + [C.c_void_p] * 6 + [C.c_double, C.c_double]
+        fields = [C.c_void_p, C.c_int64, C.c_int64]                    # a (nfields, nrows) array, its field and point strides
+        L.wlsqm_hip_krylov_many_workspace_bytes.argtypes = [C.c_int64, C.c_int]
+        L.wlsqm_hip_krylov_many_workspace_bytes.restype = C.c_int64
+        L.wlsqm_hip_krylov_many_start_device.argtypes = (system + [C.c_int] + fields + fields + [C.c_int, C.c_void_p, C.c_double, C.c_double,
+                                                                                                 C.c_int64, C.c_void_p, C.c_int, C.c_void_p])
+        L.wlsqm_hip_krylov_many_bicgstab_device.argtypes = system + [C.c_int] + fields + [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
+                                                                                           C.c_void_p]
+        L.wlsqm_hip_krylov_many_product_device.argtypes = system + [C.c_int] + fields * 3 + [C.c_void_p, C.c_int, C.c_void_p]
+        for name in ("start", "bicgstab", "product"):
+            getattr(L, "wlsqm_hip_krylov_many_%s_device" % name).restype = C.c_int
     # batched dense solves (wlsqm.utils.lapackdrivers, wlsqm.hip.*_batched)
     for op in ("getrf", "gesv", "sytrf", "sysv"):
         solve = op in ("gesv", "sysv")

@@ -19,7 +19,7 @@ __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_c
            "differentiable_solve", "differentiable_solve_many",
            "InterpolationPlan", "differentiable_evaluate",
            "StencilOperator", "stencil_rows", "differentiable_stencil_apply", "StencilSolver", "SolveInfo",
-           "SolveGradients", "BlockJacobi", "differentiable_stencil_solve",
+           "SolveGradients", "BlockJacobi", "differentiable_stencil_solve", "differentiable_stencil_solve_many",
            "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
            "getrf_batched", "getrs_batched", "gesv_batched", "sytrf_batched", "sytrs_batched", "sysv_batched", "symmetrize_batched"]
 
@@ -632,7 +632,7 @@ _AUTOGRAD = None
 
 def _autograd():
     """The torch.autograd.Function classes behind the differentiable_* functions, as a namespace with FitMany, FitCloud, Solve,
-    Evaluate, FitManyGeometry, FitCloudGeometry, StencilApply and StencilSolve (made at first use: the module does not import torch).  Every forward takes its tensor inputs first."""
+    Evaluate, FitManyGeometry, FitCloudGeometry, StencilApply, StencilSolve and StencilSolveMany (made at first use: the module does not import torch).  Every forward takes its tensor inputs first."""
     global _AUTOGRAD
     if _AUTOGRAD is not None:
         return _AUTOGRAD
@@ -885,8 +885,39 @@ def _autograd():
                 return lam, gdiag, gS, gslots, gown
             return gradients(ctx, gout, 5, adjoint)
 
+    class StencilSolveMany(torch.autograd.Function):
+        """StencilSolver.solve_many as a differentiable function of b alone: the backward pass is one solve_many(transpose=True) on the
+        incoming gradient.  The gradients with respect to the operator (S, the coefficients), diag and scale are out of scope for
+        stacked solves: take them field by field through differentiable_stencil_solve."""
+        @staticmethod
+        def forward(ctx, b, x0, solver, rtol, atol, maxiter, check_every, adjoint_rtol, stream):
+            with _torch_stream(stream, solver._device):
+                x = (x0.detach().clone(memory_format=torch.contiguous_format) if x0 is not None
+                     else torch.zeros((solver.nfields, solver.npoints), dtype=torch.float64, device=solver._device))
+            infos = solver.solve_many(b.detach(), x, rtol=rtol, atol=atol, maxiter=maxiter, check_every=check_every, stream=stream)
+            if any(info.status != 0 for info in infos):
+                raise RuntimeError("the forward solve did not converge: %r" % (infos,))
+            ctx.call = (solver, adjoint_rtol if adjoint_rtol is not None else rtol, maxiter, check_every, stream)
+            return x
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gout):
+            def adjoint(g, need_b):
+                solver, rtol, maxiter, check_every, stream = ctx.call
+                solver._no_capture("the backward pass of differentiable_stencil_solve_many", stream)
+                with _torch_stream(stream, solver._device):
+                    lam = torch.zeros((solver.nfields, solver.npoints), dtype=torch.float64, device=solver._device)
+                infos = solver.solve_many(g, lam, rtol=rtol, atol=0.0, maxiter=maxiter, check_every=check_every, stream=stream,
+                                          transpose=True)
+                if any(info.status != 0 for info in infos):
+                    raise RuntimeError("the adjoint solve did not converge: %r" % (infos,))
+                return (lam,)
+            return gradients(ctx, gout, 1, adjoint)
+
     _AUTOGRAD = types.SimpleNamespace(FitMany=FitMany, FitCloud=FitCloud, Solve=Solve, Evaluate=Evaluate, FitManyGeometry=FitManyGeometry,
-                                      FitCloudGeometry=FitCloudGeometry, StencilApply=StencilApply, StencilSolve=StencilSolve)
+                                      FitCloudGeometry=FitCloudGeometry, StencilApply=StencilApply, StencilSolve=StencilSolve,
+                                      StencilSolveMany=StencilSolveMany)
     return _AUTOGRAD
 
 
@@ -1992,10 +2023,17 @@ class StencilSolver:
     plane, 64 block ceil(npoints / 64) + ceil(npoints / 256) doubles, and a second one for M^T at the first transposed use
     (prepare_transpose).
     solve, enqueue and product take transpose=True for M^T; gradients() and differentiable_stencil_solve carry a loss through the
-    solve."""
+    solve.
+    nfields (1 .. 8): how many right-hand sides solve_many, enqueue_many and product_many take at once, as
+    independent solves that share every pass over the matrix.  nfields=1 allocates and runs exactly what a solver without it does;
+    above that the workspace holds 8 vectors at the pitch 2, 4 or 8 (the next one above nfields) and a head per field
+    (wlsqm_hip_krylov_many_workspace_bytes), and solve, enqueue and product still serve single vectors."""
 
-    def __init__(self, op, o=0, diag=1.0, scale=1.0, preconditioner="jacobi"):
+    def __init__(self, op, o=0, diag=1.0, scale=1.0, preconditioner="jacobi", nfields=1):
         self._ws = None
+        if isinstance(nfields, bool) or not isinstance(nfields, int) or not 1 <= nfields <= 8:
+            raise ValueError("nfields must be an int, 1 .. 8; got %r" % (nfields,))
+        self.nfields = nfields
         if not isinstance(op, StencilOperator):
             raise ValueError("op must be a StencilOperator")
         op._live()
@@ -2022,7 +2060,10 @@ class StencilSolver:
         pi = getattr(op, "_point_index", None)
         if pi is not None and not bool((pi[:op.ncases].long() == torch.arange(op.ncases, device=pi.device)).all()):
             raise ValueError("row j of the operator must be the equation of point j: point_index must be None or the identity")
-        nbytes = int(B.lib().wlsqm_hip_krylov_workspace_bytes(self.npoints))
+        if nfields == 1:
+            nbytes = int(B.lib().wlsqm_hip_krylov_workspace_bytes(self.npoints))
+        else:
+            nbytes = int(B.lib().wlsqm_hip_krylov_many_workspace_bytes(self.npoints, nfields))
         self._ws = torch.zeros((nbytes // 8,), dtype=torch.float64, device=self._device)
         if self._block is not None:
             self._planes = self._new_planes()
@@ -2064,6 +2105,10 @@ class StencilSolver:
         self._live()
         for name, t in named.items():
             self._vector(t, name)
+        self._disjoint(named)
+
+    def _disjoint(self, named):
+        """ValueError when one of the tensors `named` overlaps another of them, the diag tensor, the workspace or a block plane."""
         held = dict(named, workspace=self._ws)
         if hasattr(self.diag, "dim"):
             held["diag"] = self.diag
@@ -2282,6 +2327,136 @@ class StencilSolver:
             head = self._ws[:16].cpu().numpy()
         return out, float(head[6]), float(head[7])
 
+    # ---- stacked right-hand sides ----
+
+    def _field_tensor(self, t, name, written):
+        if not hasattr(t, "dim") or not hasattr(t, "is_cuda"):
+            raise ValueError("argument %s must be a device (HIP) tensor" % name)
+        _check(t, name, "float64", 2)
+        if tuple(t.shape) != (self.nfields, self.npoints):
+            raise ValueError("%s must be a float64 device tensor of shape (%d, %d), one row per field of the solver (nfields = %d); got "
+                             "shape %s" % (name, self.nfields, self.npoints, self.nfields, tuple(t.shape)))
+        if t.device != self._device:
+            raise ValueError("all tensors must be on the same device")
+        sf, sp = (abs(st) for st in t.stride())
+        if written and not ((self.nfields == 1 or sf >= self.npoints * sp) and (self.npoints == 1 or sp > 0)
+                            or (self.npoints == 1 or sp >= self.nfields * sf) and (self.nfields == 1 or sf > 0)):
+            raise ValueError("the elements of %s must be distinct in memory; got strides %s" % (name, tuple(t.stride())))
+
+    def _fields(self, written=(), **named):
+        """The checks of the stacked arrays of a call: each one (nfields, npoints) float64 on the operator's device, with any strides
+        (those named in `written`: no two elements in one place), none overlapping another, the diag tensor or the workspace."""
+        self._live()
+        for name, t in named.items():
+            self._field_tensor(t, name, name in written)
+        self._disjoint(named)
+
+    @staticmethod
+    def _strided(t):
+        return _ptr(t), t.stride(0), t.stride(1)
+
+    def _precond_args(self, transpose=False):
+        if self._block is not None:
+            return self._block_args(transpose)
+        return self._jacobi, None
+
+    def _start_many(self, b, x, rtol, atol, maxiter, dev, s, transpose=False):
+        if self._block is not None:
+            self._factor(dev, s, transpose)
+        B.check(B.lib().wlsqm_hip_krylov_many_start_device(*self._system(transpose), self.nfields, *self._strided(b), *self._strided(x),
+                                                           *self._precond_args(transpose), rtol, atol, maxiter, _ptr(self._ws), dev, s))
+
+    def _iterate_many(self, x, niter, dev, s, transpose=False):
+        B.check(B.lib().wlsqm_hip_krylov_many_bicgstab_device(*self._system(transpose), self.nfields, *self._strided(x),
+                                                              *self._precond_args(transpose), niter, _ptr(self._ws), dev, s))
+
+    def enqueue_many(self, b, x, iterations, rtol=1e-10, atol=0.0, stream=None, transpose=False):
+        """enqueue for nfields right-hand sides at once: b and x (nfields, npoints) float64 with any strides, row f of x the initial
+        guess and the solution of M x_f = b_f.  The fields are independent solves — field f's x, iteration count, status and residual
+        are, bit for bit, those of enqueue on b[f], x[f] alone — that share the launches and every pass over the matrix; each stops
+        by its own threshold max(rtol ||b_f||, atol) or breakdown and is left untouched from then on while the others go on.
+        Launches only, as enqueue: capturable, also behind op.update(S, check=False).  info_many() tells later how it went."""
+        self._fields(written=("x",), b=b, x=x)
+        rtol, atol, iterations = self._tolerances(rtol, atol, iterations)
+        if self.nfields == 1:
+            return self.enqueue(b[0], x[0], iterations, rtol=rtol, atol=atol, stream=stream, transpose=transpose)
+        transpose = self._transposed(transpose, stream)
+        s, dev = _stream_and_device(x, stream)
+        self._start_many(b, x, rtol, atol, iterations, dev, s, transpose)
+        self._iterate_many(x, iterations, dev, s, transpose)
+        return self
+
+    def _read_many(self, what, stream):
+        """([SolveInfo per field], all done) from the heads: one read of 8 x 128 + 8 bytes, which synchronises with the stream."""
+        self._live()
+        if self.nfields == 1:
+            info, done = self._read(what, stream)
+            return [info], done
+        self._no_capture(what, stream)
+        with _torch_stream(stream, self._device):
+            head = self._ws[:129].cpu().numpy()
+        infos = []
+        for f in range(self.nfields):
+            h = head[16 * f:16 * f + 16]
+            ints = h[8:10].view("int32")
+            infos.append(SolveInfo(int(ints[1]), int(ints[0]), float(h[4]) ** 0.5))
+        return infos, bool(head[128:129].view("int32")[0])
+
+    def info_many(self, stream=None):
+        """The SolveInfo of every field of the last solve_many / enqueue_many on `stream`, as a list: one read, which synchronises with
+        that stream (RuntimeError inside a graph capture)."""
+        return self._read_many("info_many", stream)[0]
+
+    def solve_many(self, b, x, rtol=1e-10, atol=0.0, maxiter=1000, check_every=8, stream=None, transpose=False):
+        """solve for nfields right-hand sides at once (enqueue_many says what that means): returns the list of SolveInfo, one per field.
+        Enqueues `check_every` iterations, reads the heads (one synchronisation) and repeats until every field has stopped, up to
+        `maxiter` iterations.  RuntimeError inside a graph capture."""
+        self._fields(written=("x",), b=b, x=x)
+        rtol, atol, maxiter = self._tolerances(rtol, atol, maxiter)
+        check_every = int(check_every)
+        if check_every < 1:
+            raise ValueError("check_every must be >= 1; got %d" % check_every)
+        self._no_capture("solve_many", stream)
+        if self.nfields == 1:
+            return [self.solve(b[0], x[0], rtol=rtol, atol=atol, maxiter=maxiter, check_every=check_every, stream=stream, transpose=transpose)]
+        transpose = self._transposed(transpose, stream)
+        s, dev = _stream_and_device(x, stream)
+        self._start_many(b, x, rtol, atol, maxiter, dev, s, transpose)
+        left = maxiter
+        while True:
+            n = min(check_every, left)
+            self._iterate_many(x, n, dev, s, transpose)
+            left -= n
+            infos, done = self._read_many("solve_many", stream)
+            if done or left == 0:
+                return infos
+
+    def product_many(self, v, w=None, out=None, stream=None, transpose=False):
+        """product for nfields vectors at once: (out, [(M v_f, w_f)], [(M v_f, M v_f)]), out (nfields, npoints) = M v per field, each
+        field's numbers bit for bit those of product on v[f], w[f] alone (w default v).  v, w and out take any strides.  One host read;
+        not between an enqueue_many and the end of its solve."""
+        import torch
+        self._live()
+        self._no_capture("product_many", stream)
+        w = v if w is None else w
+        if out is None:
+            with _torch_stream(stream, self._device):
+                out = torch.empty((self.nfields, self.npoints), dtype=torch.float64, device=self._device)
+        if w is v:
+            self._fields(written=("out",), v=v, out=out)
+        else:
+            self._fields(written=("out",), v=v, w=w, out=out)
+        if self.nfields == 1:
+            _, dot_w, dot_v = self.product(v[0], None if w is v else w[0], out=out[0], stream=stream, transpose=transpose)
+            return out, [dot_w], [dot_v]
+        transpose = self._transposed(transpose, stream)
+        s, dev = _stream_and_device(v, stream)
+        B.check(B.lib().wlsqm_hip_krylov_many_product_device(*self._system(transpose), self.nfields, *self._strided(v), *self._strided(w),
+                                                             *self._strided(out), _ptr(self._ws), dev, s))
+        with _torch_stream(stream, self._device):
+            head = self._ws[:128].cpu().numpy()
+        return out, [float(head[16 * f + 6]) for f in range(self.nfields)], [float(head[16 * f + 7]) for f in range(self.nfields)]
+
     def gradients(self, lam, x, values=False, diag=False, scale=False, stream=None):
         """The gradients of a loss L through the solve M x = b, from x and lam, the solution of M^T lam = dL/dx (solve(transpose=True)):
         SolveGradients(values, diag, scale), each None unless asked for with True or with a tensor to write into.
@@ -2388,6 +2563,27 @@ def differentiable_stencil_solve(solver, b, x0=None, S=None, coefficients=None, 
     diag = solver.diag if hasattr(solver.diag, "dim") else None
     return _autograd().StencilSolve.apply(b, diag, S, slots, own, x0, solver, float(rtol), float(atol), int(maxiter), int(check_every),
                                           None if adjoint_rtol is None else float(adjoint_rtol), stream)
+
+
+def differentiable_stencil_solve_many(solver, b, x0=None, rtol=1e-10, atol=0.0, maxiter=1000, check_every=8, adjoint_rtol=None, stream=None):
+    """x (nfields, npoints), row f the solution of M x_f = b_f by solver.solve_many, as a differentiable function of b: a new tensor
+    with a grad_fn.  The forward solves from x0 (default zeros; no gradient) and raises RuntimeError unless
+    every field converges; the backward pass is ONE solve_many(transpose=True) from zero on the incoming gradient (relative tolerance
+    `adjoint_rtol or rtol`, atol 0), and b gets its solution: row f of dL/db is, bit for bit, what differentiable_stencil_solve gives
+    for field f alone.  With respect to b only: the gradients to the operator (S, coefficients), diag and scale of stacked solves are
+    out of scope, and a diag tensor that requires a gradient gets none here.  Not capturable; once differentiable."""
+    if not isinstance(solver, StencilSolver):
+        raise ValueError("solver must be a StencilSolver")
+    named = dict(b=b) if x0 is None else dict(b=b, x0=x0)
+    solver._fields(**named)                          # before anything is detached or cloned
+    solver._tolerances(rtol, atol, maxiter)
+    if adjoint_rtol is not None:
+        solver._tolerances(adjoint_rtol, atol, maxiter)
+    if int(check_every) < 1:
+        raise ValueError("check_every must be >= 1; got %d" % int(check_every))
+    solver._no_capture("differentiable_stencil_solve_many", stream)
+    return _autograd().StencilSolveMany.apply(b, x0, solver, float(rtol), float(atol), int(maxiter), int(check_every),
+                                              None if adjoint_rtol is None else float(adjoint_rtol), stream)
 
 
 # ---- batched dense solves (the kernels behind wlsqm.utils.lapackdrivers), device-resident ----
