@@ -686,6 +686,42 @@ int wlsqm_hip_krylov_many_product_device(int64_t nrows, int64_t nslices, const i
                                          int64_t w_stride_field, int64_t w_stride_point, double* out, int64_t out_stride_field,
                                          int64_t out_stride_point, void* workspace, int device, void* stream);
 
+/* ---- BiCGSTAB(2) for the large steps where BiCGSTAB breaks down (extension; csrc/krylov.hip) ----
+ * The same M x = b, right-preconditioned (A = M P; precond and `planes` as the _many_ functions take them: 0 none, 1 Jacobi, 8 / 16 / 32
+ * the block plane of the last factor), by the method of Sleijpen and Fokkema with l = 2: two BiCG steps, then one residual minimisation
+ * over span(A r, A^2 r), with rt the residual of the start:
+ *   cycle:  rho0 = -omega rho0
+ *     j = 0:  beta = alpha (rt, r) / rho0;  rho0 = (rt, r);  u = r - beta u;  u1 = A u;  alpha = rho0 / (rt, u1);  r -= alpha u1;  r1 = A r
+ *     j = 1:  beta = alpha (rt, r1) / rho0; rho0 = (rt, r1); u = r - beta u, u1 = r1 - beta u1;  u2 = A u1;  alpha = rho0 / (rt, u2)
+ *             r -= alpha u1, r1 -= alpha u2;  r2 = A r1
+ *     MR:     s1 = (r1, r1), c1 = (r, r1), a12 = (r2, r1), a22 = (r2, r2), c2 = (r, r2);  tau = a12 / s1;  s2 = a22 - tau a12
+ *             g2 = (c2 - tau c1) / s2;  g1 = c1 / s1 - tau g2;  omega = g2;  r -= g1 r1 + g2 r2;  u -= g1 u1 + g2 u2
+ *             x += P (alpha_0 u_0 + alpha_1 u_1 + g1 r + g2 r1): the one place where x is written, behind every check of the cycle
+ * A cycle is 4 products in 14 launches and counts as 2 iterations: `iterations`, `maxiter` and the scalars' layout are those of the
+ * functions above (rho is the last (rt, r), rho_old the recurrence's rho0; beta, g1 and g2 follow the int32s as three doubles).  The stop
+ * test, the iteration limit and `done` are taken at the end of a cycle, so a solve may pass an odd maxiter by one.  Status 2: rho0 == 0,
+ * (rt, u1) == 0 or (rt, u2) == 0; 3: a non-finite dot product, alpha, beta or g; 4 as above, before the first cycle.  s1 == 0 takes
+ * g1 = g2 = 0 and s2 == 0 takes g2 = 0, g1 = c1 / s1: omega is then 0 and the next cycle answers status 2 unless the solve has converged.
+ * (rt, u2) == 0 waits in the same way: the cycle holds the step j = 0 by then, so it takes alpha = 0 and rho0 = 0, ends as ever (x receives
+ * alpha_0 u_0 and the minimisation) and leaves status 2 to the next cycle's head; a system of one row converges through this rule.
+ * A solve that stops on status 2 or 3 leaves x at the last finite iterate.  b == 0 with x == 0 converges at 0 iterations without a division.
+ * The dot products are summed in the fixed order of the functions above, without atomics.
+ * The workspace: wlsqm_hip_krylov_l2_workspace_bytes(nrows) bytes, 16-byte aligned: the 128 bytes of scalars, 5 planes of partial sums and
+ * 10 vectors.  Nothing but kernel launches on `stream` ("krylov-diag", "krylov-spmv-dot", "krylov-l2-reduce", "krylov-l2-update",
+ * "krylov-l2-update-block").  WLSQM_EVALUE as for the _many_ functions.
+ *
+ * wlsqm_hip_krylov_l2_start_device: wlsqm_hip_krylov_start_device for this method (at most 4 launches).
+ * wlsqm_hip_krylov_l2_device: `ncycles` cycles behind a start with the same arguments.
+ * wlsqm_hip_krylov_product_device and _grads_device serve this workspace too. */
+int64_t wlsqm_hip_krylov_l2_workspace_bytes(int64_t nrows);
+int wlsqm_hip_krylov_l2_start_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                     const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                     int precond, const void* planes, const double* b, const double* x, double rtol, double atol,
+                                     int64_t maxiter, void* workspace, int device, void* stream);
+int wlsqm_hip_krylov_l2_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                               const int32_t* col, const double* val, const double* diag, double diag_const, double scale, int precond,
+                               const void* planes, double* x, int64_t ncycles, void* workspace, int device, void* stream);
+
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ---- */
 /* Runs `reps` back-to-back launches of the fit kernel for batch `b` (device-resident, uniform
  * order) on `stream`, bracketed by HIP events on that stream; returns the mean kernel time in

@@ -1009,6 +1009,285 @@ static void krylov_many_product(const KrylovSys& m, const KrylovManyWork& k, int
     krylov_many_reduce<P>(REDUCE_PRODUCT, k.partial, k.nwg, 2, k, nfields, 0.0, 0.0, 0, s);
 }
 
+// ---- BiCGSTAB(2): two BiCG steps, then one residual minimisation over span(A r, A^2 r), A = M P ---------------
+// A cycle is 14 launches, 4 products and 5 reduce steps, and counts as 2 iterations:
+//   U0  u = r - beta u (the first cycle: u = r), hat = P u              P1  u1 = M hat, (rt, u1)             R  alpha
+//   U1  r -= alpha u1, dy = alpha u, hat = P r                          P2  r1 = M hat, (rt, r1)             R  beta
+//   U2  u = r - beta u, u1 = r1 - beta u1, hat = P u1                   P3  u2 = M hat, (rt, u2)             R  alpha
+//   U3  r -= alpha u1, r1 -= alpha u2, dy += alpha u, hat = P r1,       P4  r2 = M hat, (r2, r1), (r2, r2),  R  g1, g2, omega
+//       (r1, r1), (r, r1)                                                   (r, r2)
+//   U4  x += P (dy + g1 r + g2 r1), r = r - g1 r1 - g2 r2, u = u - g1 u1 - g2 u2, (rt, r), (r, r)            R  the stop, the next beta
+// P1 .. P3 are krylov_spmv_kernel<SPMV_V>.  x is written by U4 alone, behind every check of the cycle's scalars.  Without a preconditioner
+// hat is not stored and the products read u, r, u1, r1 themselves.  The scalars are KrylovScalars': rho the last (rt, r), rho_old the
+// recurrence's rho0, and beta, g1, g2 in pad[0 .. 2].  The partials are 5 planes of nwg: U3 writes planes 0 and 1, P4 planes 2 .. 4.
+
+constexpr int KRYLOV_L2_VECTORS = 10;   // r, r1, r2, u, u1, u2, rt, dy, hat, dinv
+constexpr int KRYLOV_L2_PLANES = 5;
+
+struct KrylovL2Work {
+    KrylovScalars* sc; double* partial; long long nwg;
+    double *r, *r1, *r2, *u, *u1, *u2, *rt, *dy, *hat, *dinv;   // hat null: no preconditioner; dinv null: none, or blocks
+};
+
+static KrylovL2Work krylov_l2_work(void* workspace, long long nrows, int precond) {
+    KrylovL2Work w;
+    double* base = static_cast<double*>(workspace);
+    w.sc = static_cast<KrylovScalars*>(workspace);
+    w.nwg = (nrows + 255) / 256;
+    w.partial = base + KRYLOV_HEAD;
+    double* vec = w.partial + KRYLOV_L2_PLANES * w.nwg;
+    w.r = vec; w.r1 = vec + nrows; w.r2 = vec + 2 * nrows; w.u = vec + 3 * nrows; w.u1 = vec + 4 * nrows; w.u2 = vec + 5 * nrows;
+    w.rt = vec + 6 * nrows; w.dy = vec + 7 * nrows;
+    w.hat = precond ? vec + 8 * nrows : nullptr; w.dinv = precond == 1 ? vec + 9 * nrows : nullptr;
+    return w;
+}
+
+// block_sums for three sums, into the planes 2 .. 4.
+__device__ __forceinline__ void block_sums_three(double (&a)[3], double* partial, long long nwg) {
+    __shared__ double part[3][4];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) a[q] += __shfl_down(a[q], off, 64);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) part[q][wave] = a[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const double* w = part[threadIdx.x];
+        partial[(2 + threadIdx.x) * nwg + blockIdx.x] = ((w[0] + w[1]) + w[2]) + w[3];
+    }
+}
+
+// P4: r2 = M in, with the partials (r2, r1), (r2, r2) and (r, r2).
+__global__ void __launch_bounds__(256) krylov_l2_spmv_kernel(const KrylovSys m, const double* in, const double* r, const double* r1,
+                                                             double* r2, double* partial, const KrylovScalars* sc) {
+    if (sc->done) return;                                        // uniform: the whole grid
+    const int lane = threadIdx.x & 63;
+    const long long s = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long row = s * 64 + lane;
+    double a[3] = {0.0, 0.0, 0.0};
+    if (s * 64 < m.nrows) {                                      // wave-uniform
+        const int wid = __builtin_amdgcn_readfirstlane(m.width[s]);
+        const long long at = m.soff[s] + lane;
+        int n = row < m.nrows ? m.len[row] : 0;
+        n = n < wid ? n : wid;
+        const double sum = krylov_row_sum(m.col + at, m.val + at, in, wid, n);
+        if (row < m.nrows) {
+            const double d = m.dvec ? m.dvec[row] : m.dconst;
+            const double y = __builtin_fma(m.c, sum, d * in[row]);
+            r2[row] = y;
+            a[0] = y * r1[row]; a[1] = y * y; a[2] = r[row] * y;
+        }
+    }
+    block_sums_three(a, partial, gridDim.x);
+}
+
+// z = P v of this lane's row: the blocks' (every lane of the wave takes part, one beyond nrows with 0), the Jacobi diagonal's, or v.
+template <int NB>
+__device__ __forceinline__ double krylov_l2_precondition(const KrylovL2Work& k, const double* W, long long i, long long s, int lane,
+                                                         bool live, double v) {
+    if constexpr (NB > 0) return krylov_block_apply<NB>(W + (s * NB) * 64 + lane, live ? v : 0.0, lane);
+    else return k.dinv && live ? k.dinv[i] * v : v;
+}
+
+enum { L2_U0 = 0, L2_U1 = 1, L2_U2 = 2, L2_U3 = 3, L2_U4 = 4 };
+
+// The update STEP of the list above, with P the blocks of NB rows in W, or (NB 0) the Jacobi diagonal k.dinv or nothing.
+template <int NB, int STEP>
+__global__ void __launch_bounds__(256) krylov_l2_update_kernel(long long nrows, const KrylovL2Work k, const double* W, double* x) {
+    const KrylovScalars* sc = k.sc;
+    if (sc->done) return;                                        // uniform: the whole grid
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const long long s = i >> 6;
+    const bool live = i < nrows;
+    double a = 0.0, b = 0.0;
+    if (s * 64 < nrows) {                                        // wave-uniform
+        double v = 0.0;                                          // what P is applied to
+        if (live) {
+            if (STEP == L2_U0) {
+                v = k.r[i];
+                if (sc->iterations > 0) v = v - sc->pad[0] * k.u[i];
+                k.u[i] = v;
+            } else if (STEP == L2_U1) {
+                const double alpha = sc->alpha;
+                v = k.r[i] - alpha * k.u1[i];
+                k.r[i] = v;
+                k.dy[i] = alpha * k.u[i];
+            } else if (STEP == L2_U2) {
+                const double beta = sc->pad[0];
+                k.u[i] = k.r[i] - beta * k.u[i];
+                v = k.r1[i] - beta * k.u1[i];
+                k.u1[i] = v;
+            } else if (STEP == L2_U3) {
+                const double alpha = sc->alpha;
+                const double r = k.r[i] - alpha * k.u1[i];
+                v = k.r1[i] - alpha * k.u2[i];
+                k.r[i] = r; k.r1[i] = v;
+                k.dy[i] = k.dy[i] + alpha * k.u[i];
+                a = v * v; b = r * v;
+            } else {
+                const double g1 = sc->pad[1], g2 = sc->pad[2];
+                const double r = k.r[i], r1 = k.r1[i];
+                v = (k.dy[i] + g1 * r) + g2 * r1;
+                const double rn = (r - g1 * r1) - g2 * k.r2[i];
+                k.r[i] = rn;
+                k.u[i] = (k.u[i] - g1 * k.u1[i]) - g2 * k.u2[i];
+                a = k.rt[i] * rn; b = rn * rn;
+            }
+        }
+        const double z = krylov_l2_precondition<NB>(k, W, i, s, lane, live, v);
+        if (live) {
+            if (STEP == L2_U4) x[i] = x[i] + z;
+            else if (k.hat) k.hat[i] = z;
+        }
+    }
+    if (STEP == L2_U3 || STEP == L2_U4) block_sums<true>(a, b, k.partial, gridDim.x);
+}
+
+enum { L2_START = 0, L2_ALPHA = 1, L2_BETA = 2, L2_ALPHA1 = 3, L2_MR = 4, L2_END = 5 };
+
+// The head of the next cycle, taken where its (rt, r) is formed: rho0 = -omega rho0, beta = alpha rho1 / rho0, rho0 = rho1.
+__device__ __forceinline__ void krylov_l2_next_cycle(KrylovScalars* sc, double rho1) {
+    const double rho0 = -sc->omega * sc->rho_old;
+    if (rho0 == 0.0) { krylov_stop(sc, KRYLOV_BREAKDOWN); return; }
+    const double beta = sc->alpha * rho1 / rho0;
+    if (!__builtin_isfinite(beta)) { krylov_stop(sc, KRYLOV_NONFINITE); return; }
+    sc->pad[0] = beta; sc->rho_old = rho1;
+}
+
+// The scalar step of `mode` on the sums of its dot products: one lane.
+__device__ __forceinline__ void krylov_l2_scalar_step(int mode, KrylovScalars* sc, const double (&s)[KRYLOV_L2_PLANES], double rtol, double atol) {
+    switch (mode) {
+    case L2_START: {                                             // s0 = (r, r) = (rt, r), s1 = (b, b), behind REDUCE_DIAG
+        sc->rho = s[0]; sc->rr = s[0];
+        if (!__builtin_isfinite(s[0]) || !__builtin_isfinite(s[1])) { krylov_stop(sc, KRYLOV_NONFINITE); break; }
+        const double rel = rtol * __builtin_sqrt(s[1]), stop = rel > atol ? rel : atol;
+        sc->stop = stop;
+        if (__builtin_sqrt(s[0]) <= stop) { krylov_stop(sc, KRYLOV_CONVERGED); break; }
+        if (sc->maxiter <= 0) { krylov_stop(sc, KRYLOV_MAXITER); break; }
+        sc->rho_old = 1.0; sc->alpha = 0.0; sc->omega = 1.0;
+        sc->pad[0] = sc->pad[1] = sc->pad[2] = 0.0;
+        krylov_l2_next_cycle(sc, s[0]);
+        break;
+    }
+    case L2_ALPHA:                                               // s0 = (rt, u1)
+    case L2_ALPHA1: {                                            // s0 = (rt, u2)
+        if (!__builtin_isfinite(s[0])) { krylov_stop(sc, KRYLOV_NONFINITE); break; }
+        if (s[0] == 0.0) {
+            if (mode == L2_ALPHA) { krylov_stop(sc, KRYLOV_BREAKDOWN); break; }
+            // j = 1: the cycle already holds the step j = 0, which x has not received.  The breakdown waits for the cycle's end: alpha = 0
+            // and rho0 = 0, so that x takes alpha_0 u_0 and the minimisation, and the next cycle's head answers 2 unless that converged
+            // (a system of one row always ends here: its Krylov space has one dimension)
+            sc->alpha = 0.0; sc->rho_old = 0.0;
+            break;
+        }
+        const double alpha = sc->rho_old / s[0];
+        if (!__builtin_isfinite(alpha)) { krylov_stop(sc, KRYLOV_NONFINITE); break; }
+        sc->alpha = alpha;
+        break;
+    }
+    case L2_BETA: {                                              // s0 = (rt, r1)
+        if (!__builtin_isfinite(s[0])) { krylov_stop(sc, KRYLOV_NONFINITE); break; }
+        if (sc->rho_old == 0.0) { krylov_stop(sc, KRYLOV_BREAKDOWN); break; }
+        const double beta = sc->alpha * s[0] / sc->rho_old;
+        if (!__builtin_isfinite(beta)) { krylov_stop(sc, KRYLOV_NONFINITE); break; }
+        sc->pad[0] = beta; sc->rho_old = s[0];
+        break;
+    }
+    case L2_MR: {                                                // s1 = (r1, r1), c1 = (r, r1), a12 = (r2, r1), a22 = (r2, r2), c2 = (r, r2)
+        const double s1 = s[0], c1 = s[1], a12 = s[2], a22 = s[3], c2 = s[4];
+        if (!__builtin_isfinite(s1) || !__builtin_isfinite(c1) || !__builtin_isfinite(a12) || !__builtin_isfinite(a22) || !__builtin_isfinite(c2)) {
+            krylov_stop(sc, KRYLOV_NONFINITE);
+            break;
+        }
+        double g1 = 0.0, g2 = 0.0;
+        if (s1 != 0.0) {
+            const double tau = a12 / s1, s2 = a22 - tau * a12;
+            if (s2 != 0.0) g2 = (c2 - tau * c1) / s2;
+            g1 = c1 / s1 - tau * g2;
+        }
+        if (!__builtin_isfinite(g1) || !__builtin_isfinite(g2)) { krylov_stop(sc, KRYLOV_NONFINITE); break; }
+        sc->pad[1] = g1; sc->pad[2] = g2; sc->omega = g2;
+        break;
+    }
+    default: {                                                   // L2_END: s0 = (rt, r), s1 = (r, r)
+        const int it = sc->iterations + 2;
+        sc->iterations = it; sc->rho = s[0]; sc->rr = s[1];
+        if (!__builtin_isfinite(s[0]) || !__builtin_isfinite(s[1])) krylov_stop(sc, KRYLOV_NONFINITE);
+        else if (__builtin_sqrt(s[1]) <= sc->stop) krylov_stop(sc, KRYLOV_CONVERGED);
+        else if (it >= sc->maxiter) krylov_stop(sc, KRYLOV_MAXITER);
+        else krylov_l2_next_cycle(sc, s[0]);
+        break;
+    }
+    }
+}
+
+// krylov_reduce_kernel for up to five planes: thread t sums t, t + 256, ... of each, then the tree, the waves in order and one lane's step.
+__global__ void __launch_bounds__(256) krylov_l2_reduce_kernel(int mode, const double* partial, long long nwg, KrylovScalars* sc,
+                                                               double rtol, double atol) {
+    if (sc->done) return;                                        // uniform
+    const int planes = mode == L2_MR ? 5 : (mode == L2_START || mode == L2_END) ? 2 : 1;
+    __shared__ double part[KRYLOV_L2_PLANES][4];
+    double a[KRYLOV_L2_PLANES];
+#pragma unroll
+    for (int q = 0; q < KRYLOV_L2_PLANES; ++q) a[q] = 0.0;
+    for (long long i = threadIdx.x; i < nwg; i += 256) {
+#pragma unroll
+        for (int q = 0; q < KRYLOV_L2_PLANES; ++q)
+            if (q < planes) a[q] += partial[q * nwg + i];        // uniform
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int q = 0; q < KRYLOV_L2_PLANES; ++q) a[q] += __shfl_down(a[q], off, 64);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < KRYLOV_L2_PLANES; ++q) part[q][wave] = a[q];
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double sums[KRYLOV_L2_PLANES];
+#pragma unroll
+    for (int q = 0; q < KRYLOV_L2_PLANES; ++q) sums[q] = ((part[q][0] + part[q][1]) + part[q][2]) + part[q][3];
+    krylov_l2_scalar_step(mode, sc, sums, rtol, atol);
+}
+
+template <int NB>
+static void krylov_l2_cycles(const KrylovSys& m, const KrylovL2Work& w, const double* W, double* x, int64_t ncycles, hipStream_t s) {
+    const dim3 grid((unsigned)w.nwg), block(256);
+    const KrylovScalars* sc = w.sc;
+    const long long nrows = m.nrows;
+    const double* rt = w.rt;
+    const double *in_u = w.hat ? w.hat : w.u, *in_r = w.hat ? w.hat : w.r, *in_u1 = w.hat ? w.hat : w.u1, *in_r1 = w.hat ? w.hat : w.r1;
+    double* const none = nullptr;
+    auto reduce = [&](int mode) {
+        hipLaunchKernelGGL(krylov_l2_reduce_kernel, dim3(1), block, 0, s, mode, (const double*)w.partial, w.nwg, w.sc, 0.0, 0.0);
+    };
+    for (int64_t it = 0; it < ncycles; ++it) {
+        hipLaunchKernelGGL((krylov_l2_update_kernel<NB, L2_U0>), grid, block, 0, s, nrows, w, W, none);
+        hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_V>), grid, block, 0, s, m, in_u, rt, w.u1, none, w.partial, sc, 0);
+        reduce(L2_ALPHA);
+        hipLaunchKernelGGL((krylov_l2_update_kernel<NB, L2_U1>), grid, block, 0, s, nrows, w, W, none);
+        hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_V>), grid, block, 0, s, m, in_r, rt, w.r1, none, w.partial, sc, 0);
+        reduce(L2_BETA);
+        hipLaunchKernelGGL((krylov_l2_update_kernel<NB, L2_U2>), grid, block, 0, s, nrows, w, W, none);
+        hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_V>), grid, block, 0, s, m, in_u1, rt, w.u2, none, w.partial, sc, 0);
+        reduce(L2_ALPHA1);
+        hipLaunchKernelGGL((krylov_l2_update_kernel<NB, L2_U3>), grid, block, 0, s, nrows, w, W, none);
+        hipLaunchKernelGGL(krylov_l2_spmv_kernel, grid, block, 0, s, m, in_r1, (const double*)w.r, (const double*)w.r1, w.r2, w.partial, sc);
+        reduce(L2_MR);
+        hipLaunchKernelGGL((krylov_l2_update_kernel<NB, L2_U4>), grid, block, 0, s, nrows, w, W, x);
+        reduce(L2_END);
+    }
+}
+
 }  // namespace wlsqm
 
 using namespace wlsqm;
@@ -1336,6 +1615,74 @@ int wlsqm_hip_krylov_many_product_device(int64_t nrows, int64_t nslices, const i
     }
     WLSQM_HIP_CHECK(hipGetLastError());
     note_kernel("krylov-spmv-many");
+    return WLSQM_OK;
+}
+
+int64_t wlsqm_hip_krylov_l2_workspace_bytes(int64_t nrows) {
+    if (nrows < 0) return -1;
+    return (int64_t)sizeof(double) * (KRYLOV_HEAD + KRYLOV_L2_PLANES * ((nrows + 255) / 256) + KRYLOV_L2_VECTORS * nrows);
+}
+
+int wlsqm_hip_krylov_l2_start_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                     const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                     int precond, const void* planes, const double* b, const double* x, double rtol, double atol,
+                                     int64_t maxiter, void* workspace, int device, void* stream) {
+    KrylovSys m;
+    int rc = krylov_system("krylov_l2_start", m, nrows, nslices, len, width, soff, col, val, diag, diag_const, scale, workspace);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_many_arguments("krylov_l2_start", nrows, nslices, 1, precond, planes, workspace);
+    if (rc != WLSQM_OK) return rc;
+    if (!b || !x) { set_error("krylov_l2_start: null array"); return WLSQM_EVALUE; }
+    if (!(rtol >= 0.0) || !(atol >= 0.0) || !std::isfinite(rtol) || !std::isfinite(atol)) {
+        set_error("krylov_l2_start: rtol and atol must be finite and >= 0");
+        return WLSQM_EVALUE;
+    }
+    if (maxiter < 0 || maxiter > INT32_MAX) { set_error("krylov_l2_start: maxiter must be 0 .. 2^31 - 1"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const KrylovL2Work w = krylov_l2_work(workspace, nrows, precond);
+    const dim3 grid((unsigned)w.nwg);
+    if (precond == 1) {
+        hipLaunchKernelGGL(krylov_diag_kernel, grid, dim3(256), 0, s, m, w.dinv, w.partial);
+        note_kernel("krylov-diag");
+    }
+    const double* counts = precond > 1 ? static_cast<const double*>(planes) + krylov_plane_doubles(nslices, precond) : w.partial;
+    hipLaunchKernelGGL(krylov_reduce_kernel, dim3(1), dim3(256), 0, s, (int)REDUCE_DIAG, counts, precond ? w.nwg : 0LL, 1, w.sc, rtol, atol,
+                       (int)maxiter);
+    hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_RESIDUAL>), grid, dim3(256), 0, s, m, x, b, w.r, w.rt, w.partial, (const KrylovScalars*)w.sc, 0);
+    note_kernel("krylov-spmv-dot");
+    hipLaunchKernelGGL(krylov_l2_reduce_kernel, dim3(1), dim3(256), 0, s, (int)L2_START, (const double*)w.partial, w.nwg, w.sc, rtol, atol);
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-l2-reduce");
+    return WLSQM_OK;
+}
+
+int wlsqm_hip_krylov_l2_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                               const int32_t* col, const double* val, const double* diag, double diag_const, double scale, int precond,
+                               const void* planes, double* x, int64_t ncycles, void* workspace, int device, void* stream) {
+    KrylovSys m;
+    int rc = krylov_system("krylov_l2", m, nrows, nslices, len, width, soff, col, val, diag, diag_const, scale, workspace);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_many_arguments("krylov_l2", nrows, nslices, 1, precond, planes, workspace);
+    if (rc != WLSQM_OK) return rc;
+    if (!x) { set_error("krylov_l2: null array"); return WLSQM_EVALUE; }
+    if (ncycles < 0) { set_error("krylov_l2: ncycles must be >= 0"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK || ncycles == 0) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const KrylovL2Work w = krylov_l2_work(workspace, nrows, precond);
+    const double* W = static_cast<const double*>(planes);
+    switch (precond) {
+    case 8: krylov_l2_cycles<8>(m, w, W, x, ncycles, s); break;
+    case 16: krylov_l2_cycles<16>(m, w, W, x, ncycles, s); break;
+    case 32: krylov_l2_cycles<32>(m, w, W, x, ncycles, s); break;
+    default: krylov_l2_cycles<0>(m, w, nullptr, x, ncycles, s); break;
+    }
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel(precond > 1 ? "krylov-l2-update-block" : "krylov-l2-update");
     return WLSQM_OK;
 }
 

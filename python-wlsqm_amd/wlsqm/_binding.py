@@ -232,6 +232,16 @@ def lib():
         L.wlsqm_hip_krylov_many_product_device.argtypes = system + [C.c_int] + fields * 3 + [C.c_void_p, C.c_int, C.c_void_p]
         for name in ("start", "bicgstab", "product"):
             getattr(L, "wlsqm_hip_krylov_many_%s_device" % name).restype = C.c_int
+    # BiCGSTAB(2) on those systems (StencilSolver(method="bicgstab2"))
+    if hasattr(L, "wlsqm_hip_krylov_l2_start_device"):
+        system = [C.c_int64, C.c_int64] + [C.c_void_p] * 6 + [C.c_double, C.c_double]
+        L.wlsqm_hip_krylov_l2_workspace_bytes.argtypes = [C.c_int64]
+        L.wlsqm_hip_krylov_l2_workspace_bytes.restype = C.c_int64
+        L.wlsqm_hip_krylov_l2_start_device.argtypes = system + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int64,
+                                                                C.c_void_p, C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_l2_start_device.restype = C.c_int
+        L.wlsqm_hip_krylov_l2_device.argtypes = system + [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_l2_device.restype = C.c_int
     # batched dense solves (wlsqm.utils.lapackdrivers, wlsqm.hip.*_batched)
     for op in ("getrf", "gesv", "sytrf", "sysv"):
         solve = op in ("gesv", "sysv")

@@ -1987,7 +1987,7 @@ and dL/d(scale) (a 0-d device tensor); None for what was not asked for."""
 SolveInfo = collections.namedtuple("SolveInfo", "status iterations residual")
 SolveInfo.__doc__ = """What a StencilSolver says of a solve.  status: 0 converged, 1 iteration limit, 2 breakdown (rho = 0 or (r0, v) = 0),
 3 a non-finite scalar, 4 a zero or non-finite Jacobi diagonal or a singular or non-finite block of a BlockJacobi, -1 still running (enqueue with fewer iterations than the solve needs
-always ends in 1).  iterations: those completed.  residual: the recursive ||r||_2 (NaN with status 4: no residual was formed)."""
+always ends in 1).  With method="bicgstab2", 2 is rho0 = 0, (rt, u1) = 0 or (rt, u2) = 0.  iterations: those completed.  residual: the recursive ||r||_2 (NaN with status 4: no residual was formed)."""
 
 
 class BlockJacobi:
@@ -2027,13 +2027,25 @@ class StencilSolver:
     nfields (1 .. 8): how many right-hand sides solve_many, enqueue_many and product_many take at once, as
     independent solves that share every pass over the matrix.  nfields=1 allocates and runs exactly what a solver without it does;
     above that the workspace holds 8 vectors at the pitch 2, 4 or 8 (the next one above nfields) and a head per field
-    (wlsqm_hip_krylov_many_workspace_bytes), and solve, enqueue and product still serve single vectors."""
+    (wlsqm_hip_krylov_many_workspace_bytes), and solve, enqueue and product still serve single vectors.
+    method: "bicgstab" (the default: everything above), or "bicgstab2" for the large steps on which BiCGSTAB breaks down or wanders
+    (tau >= 1, above all in 3D, with a BlockJacobi on a cloud in Morton order): BiCGSTAB(2) of Sleijpen and Fokkema, two BiCG steps and
+    then one residual minimisation over two dimensions.  Every method of the solver serves it, with every
+    preconditioner, transposed solves and differentiable_stencil_solve included; nfields must be 1.  A cycle is 4 products in 14
+    launches and counts as 2 iterations, so `iterations`, `maxiter` and `check_every` mean what they mean for "bicgstab"; the stop is
+    taken at the end of a cycle, so a solve may pass an odd maxiter by one, and enqueue(iterations=k) enqueues ceil(k / 2) cycles.
+    Status 2 is then rho0 = 0, (rt, u1) = 0 or (rt, u2) = 0.  The workspace is 10 npoints + 5 ceil(npoints / 256) + 16 doubles."""
 
-    def __init__(self, op, o=0, diag=1.0, scale=1.0, preconditioner="jacobi", nfields=1):
+    def __init__(self, op, o=0, diag=1.0, scale=1.0, preconditioner="jacobi", nfields=1, method="bicgstab"):
         self._ws = None
         if isinstance(nfields, bool) or not isinstance(nfields, int) or not 1 <= nfields <= 8:
             raise ValueError("nfields must be an int, 1 .. 8; got %r" % (nfields,))
         self.nfields = nfields
+        if method not in ("bicgstab", "bicgstab2"):
+            raise ValueError("method must be 'bicgstab' or 'bicgstab2'; got %r" % (method,))
+        if method == "bicgstab2" and nfields > 1:
+            raise ValueError("method 'bicgstab2' solves one right-hand side at a time: nfields must be 1; got %d" % nfields)
+        self.method, self._l2 = method, method == "bicgstab2"
         if not isinstance(op, StencilOperator):
             raise ValueError("op must be a StencilOperator")
         op._live()
@@ -2060,7 +2072,9 @@ class StencilSolver:
         pi = getattr(op, "_point_index", None)
         if pi is not None and not bool((pi[:op.ncases].long() == torch.arange(op.ncases, device=pi.device)).all()):
             raise ValueError("row j of the operator must be the equation of point j: point_index must be None or the identity")
-        if nfields == 1:
+        if self._l2:
+            nbytes = int(B.lib().wlsqm_hip_krylov_l2_workspace_bytes(self.npoints))
+        elif nfields == 1:
             nbytes = int(B.lib().wlsqm_hip_krylov_workspace_bytes(self.npoints))
         else:
             nbytes = int(B.lib().wlsqm_hip_krylov_many_workspace_bytes(self.npoints, nfields))
@@ -2235,9 +2249,20 @@ class StencilSolver:
                 raise RuntimeError("%s reads the solve's scalars on the host and the stream is capturing: use enqueue inside the capture "
                                    "and info() after the replay" % what)
 
+    def _precond_args(self, transpose=False):
+        """(precond, planes) of the entry points that take every preconditioner: 0 none, 1 Jacobi, or the block size and its plane."""
+        if self._block is not None:
+            return self._block_args(transpose)
+        return self._jacobi, None
+
     def _start(self, b, x, rtol, atol, maxiter, dev, s, transpose=False):
         if self._block is not None:
             self._factor(dev, s, transpose)
+        if self._l2:
+            B.check(B.lib().wlsqm_hip_krylov_l2_start_device(*self._system(transpose), *self._precond_args(transpose), _ptr(b), _ptr(x),
+                                                             rtol, atol, maxiter, _ptr(self._ws), dev, s))
+            return
+        if self._block is not None:
             B.check(B.lib().wlsqm_hip_krylov_block_start_device(*self._system(transpose), *self._block_args(transpose), _ptr(b), _ptr(x),
                                                                 rtol, atol, maxiter, _ptr(self._ws), dev, s))
             return
@@ -2245,6 +2270,10 @@ class StencilSolver:
                                                       _ptr(self._ws), dev, s))
 
     def _iterate(self, x, niter, dev, s, transpose=False):
+        if self._l2:                                                     # a cycle is two iterations: ceil(niter / 2) cycles
+            B.check(B.lib().wlsqm_hip_krylov_l2_device(*self._system(transpose), *self._precond_args(transpose), _ptr(x), (niter + 1) // 2,
+                                                       _ptr(self._ws), dev, s))
+            return
         if self._block is not None:
             B.check(B.lib().wlsqm_hip_krylov_block_bicgstab_device(*self._system(transpose), *self._block_args(transpose), _ptr(x), niter,
                                                                    _ptr(self._ws), dev, s))
@@ -2301,7 +2330,7 @@ class StencilSolver:
         while True:
             n = min(check_every, left)
             self._iterate(x, n, dev, s, transpose)
-            left -= n
+            left -= min(left, n + n % 2) if self._l2 else n
             info, done = self._read("solve", stream)
             if done or left == 0:
                 return info
