@@ -722,6 +722,45 @@ int wlsqm_hip_krylov_l2_device(int64_t nrows, int64_t nslices, const int32_t* le
                                const int32_t* col, const double* val, const double* diag, double diag_const, double scale, int precond,
                                const void* planes, double* x, int64_t ncycles, void* workspace, int device, void* stream);
 
+/* ---- sparse approximate inverse preconditioner of those solves (extension; csrc/krylov.hip) ----
+ * P = Q = diag(qd) + (the plane qv on the matrix's own SELL-64 structure): row i of Q minimises ||q^T M - e_i^T||_2 over the pattern
+ * of row i of M, so Q M ~ I; the solves stay right-preconditioned (A = M Q).  The unknowns of row i are its slots: slot 0 the diagonal,
+ * slot k the stored entry k - 1; a slot whose column an earlier slot names (the own entry of an F-known row, a neighbour named twice)
+ * is dead and its coefficient is 0.0.  With J the columns of the live slots and m_r row r of M:
+ *   G[a][b] = m_J[a] . m_J[b],  rhs[a] = (m_J[a])_i,  G q = rhs  by L D L^T without pivoting.
+ * The planes: wlsqm_hip_krylov_spai_bytes(nrows, total) bytes of device memory, 8-byte aligned, `total` the matrix's stored entries:
+ * qd (nrows doubles), the per-slice counts of the rows whose factorisation met a pivot that is not positive and finite
+ * (ceil(nrows / 64) doubles; such a row of Q is zeros, and every start reduces the counts into status 4 with x untouched), then qv (total).
+ *
+ * wlsqm_hip_krylov_spai_build_device ("krylov-spai", one launch; a second with planes_t): Q from the matrix, diag and scale as they are on
+ *   `stream`.  One wave per slice, its rows in turn; no atomics on anything that is summed, no scratch memory: the bits of Q are a function of
+ *   the arguments.  An own entry (column r in row r) counts as part of the row's diagonal: a row is read as d_r plus its own entries in
+ *   entry order, then its other entries.  max_width: the widest slice of the matrix, at most 65 (WLSQM_EVALUE above): 64 stored entries,
+ *   or 65 where the 65th is the row's own entry (a row that stores anything else there fails: status 4).  planes_t (nullable): the planes of Q^T on
+ *   the transposed structure, filled through npairs (dest, src) pairs of positions (transposed, forward) of the stored entries: the same
+ *   numbers moved, not an approximate inverse of M^T.
+ * wlsqm_hip_krylov_spai_apply_device ("krylov-spai-apply", one launch): out = Q v on the structure that the planes belong to (the forward
+ *   one, or the transposed one with planes_t); v and out must not overlap.
+ * wlsqm_hip_krylov_spai_start_device / _iterate_device: wlsqm_hip_krylov_start_device / _bicgstab_device (l2 == 0: `niter` iterations of
+ *   10 launches, "krylov-spai-update": p and s by the update kernels, phat = Q p and shat = Q s by launches of their own) or
+ *   wlsqm_hip_krylov_l2_start_device / _l2_device (l2 != 0: `niter` cycles of 19 launches, "krylov-spai-l2-update": Q applied 5 times, the
+ *   last one adding to x between the cycle's last update and the reduce that takes the stop) with P = Q from `planes`; the workspaces are
+ *   those methods' own, the matrix M or M^T with the planes of the same structure. */
+int64_t wlsqm_hip_krylov_spai_bytes(int64_t nrows, int64_t total);
+int wlsqm_hip_krylov_spai_build_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                       const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                       int max_width, void* planes, int64_t npairs, const int32_t* pair_dest, const int32_t* pair_src,
+                                       void* planes_t, int device, void* stream);
+int wlsqm_hip_krylov_spai_apply_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                       const int32_t* col, const void* planes, const double* v, double* out, int device, void* stream);
+int wlsqm_hip_krylov_spai_start_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                       const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                       int l2, const void* planes, const double* b, const double* x, double rtol, double atol,
+                                       int64_t maxiter, void* workspace, int device, void* stream);
+int wlsqm_hip_krylov_spai_iterate_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                         const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                         int l2, const void* planes, double* x, int64_t niter, void* workspace, int device, void* stream);
+
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ---- */
 /* Runs `reps` back-to-back launches of the fit kernel for batch `b` (device-resident, uniform
  * order) on `stream`, bracketed by HIP events on that stream; returns the mean kernel time in

@@ -1096,8 +1096,9 @@ __device__ __forceinline__ double krylov_l2_precondition(const KrylovL2Work& k, 
 
 enum { L2_U0 = 0, L2_U1 = 1, L2_U2 = 2, L2_U3 = 3, L2_U4 = 4 };
 
-// The update STEP of the list above, with P the blocks of NB rows in W, or (NB 0) the Jacobi diagonal k.dinv or nothing.
-template <int NB, int STEP>
+// The update STEP of the list above, with P the blocks of NB rows in W, or (NB 0) the Jacobi diagonal k.dinv or nothing.  DEFER: U4 leaves
+// what P is to be applied to in k.hat and x alone (the approximate inverse adds P of it to x by a launch of its own, section 22).
+template <int NB, int STEP, bool DEFER = false>
 __global__ void __launch_bounds__(256) krylov_l2_update_kernel(long long nrows, const KrylovL2Work k, const double* W, double* x) {
     const KrylovScalars* sc = k.sc;
     if (sc->done) return;                                        // uniform: the whole grid
@@ -1142,7 +1143,7 @@ __global__ void __launch_bounds__(256) krylov_l2_update_kernel(long long nrows, 
         }
         const double z = krylov_l2_precondition<NB>(k, W, i, s, lane, live, v);
         if (live) {
-            if (STEP == L2_U4) x[i] = x[i] + z;
+            if (STEP == L2_U4 && !DEFER) x[i] = x[i] + z;
             else if (k.hat) k.hat[i] = z;
         }
     }
@@ -1286,6 +1287,361 @@ static void krylov_l2_cycles(const KrylovSys& m, const KrylovL2Work& w, const do
         hipLaunchKernelGGL((krylov_l2_update_kernel<NB, L2_U4>), grid, block, 0, s, nrows, w, W, x);
         reduce(L2_END);
     }
+}
+
+// ---- the sparse approximate inverse: Q = diag(qd) + (plane qv on the matrix's own structure), Q M ~ I ----------
+// Row i of Q minimises ||q^T M - e_i^T||_2 over the pattern of row i of M.  Its unknowns are the slots: slot 0 the diagonal (column i),
+// slot k the stored entry k - 1 of row i; a slot whose column an earlier slot names is dead, its coefficient 0.0.  With J the columns of
+// the slots and m_r row r of M (d_r at column r, then c val[r, e] at col[r, e]): G[a, b] = m_J[a] . m_J[b], rhs[a] = (m_J[a])_i, G q = rhs
+// by LDL^T without pivoting.
+// The planes: qd (nrows), the per-slice counts of the rows whose factorisation failed (ceil(nrows / 64)), qv (the matrix's `total`).
+//
+// An own entry (column r in row r) is part of the row's diagonal: every row is read as d_r plus its own entries in entry order, then its
+// other entries.  A row may store 65 entries where the 65th is its own entry (64 neighbours of an F-known point); otherwise 64.
+// krylov_spai_kernel: one wave per slice, its 64 rows one after the other; lane l owns slot l + 1 and keeps row J[l + 1] of M in registers.
+//   columns: every column of the rows of J gets a cell of an LDS table by open addressing (atomicCAS on the key).  The cell numbers serve
+//            matching only: no sum runs in their order.
+//   row b, dense: its owner stores d at the cell of its diagonal and every entry at its cell; an entry whose column the row named before
+//            (the own entry of an F-known row, a neighbour named twice) is added onto the cell afterwards, in entry order.
+//   G[a, b], b <= a: lane a's fma chain over ITS entries as stored, the diagonal first, against the dense row b.  rhs[b] = dense b at i.
+//   LDL^T in LDS, right-looking, lane a updating row a; the forward substitution rides on it; then the division and the backward pass.
+// A pivot that is not positive and finite, a slot that names no row, or a non-finite coefficient counts the row as failed: its row of Q
+// is zeros, and every start reduces the counts into status 4.  No atomics on anything that is summed, no scratch memory.
+
+constexpr int KRYLOV_SPAI_CAP = 65;     // stored entries per row: 64, and behind them the row's own entry
+
+__host__ __device__ constexpr int krylov_spai_cells(int W) { return ((W + 1) * (W + 1) * 9 / 8 + 63) / 64 * 64; }   // > 1 + W + W^2 columns
+
+struct KrylovSpai {
+    double *qd, *counts, *qv;
+};
+
+static KrylovSpai krylov_spai_planes(const void* planes, long long nrows) {
+    double* base = static_cast<double*>(const_cast<void*>(planes));
+    return KrylovSpai{base, base + nrows, base + nrows + (nrows + 63) / 64};
+}
+
+// The cell of column c: the first free one at or behind its hash, or the one that holds it already.
+template <int CELLS>
+__device__ __forceinline__ int krylov_spai_cell(int32_t* keys, int32_t c) {
+    unsigned at = (unsigned)(((unsigned long long)((unsigned)c * 2654435761u) * (unsigned)CELLS) >> 32);
+    for (;;) {
+        const int32_t old = atomicCAS(&keys[at], -1, c);
+        if (old == -1 || old == c) return (int)at;
+        at = at + 1 == (unsigned)CELLS ? 0u : at + 1;
+    }
+}
+
+template <int W>
+__global__ void __launch_bounds__(64) krylov_spai_kernel(const KrylovSys m, double* qd, double* qv, double* counts) {
+    constexpr int CELLS = krylov_spai_cells(W);
+    __shared__ int32_t keys[CELLS];
+    __shared__ unsigned long long cells[CELLS];                  // the dense row (a double's bits), and the marks of the rows that named a cell
+    __shared__ double G[(W + 1) * (W + 2) / 2];                  // the lower triangle, row a at a (a + 1) / 2
+    const int lane = threadIdx.x;
+    const long long s = blockIdx.x;
+    const long long first = s * 64, last = first + 64 < m.nrows ? first + 64 : m.nrows;
+    const int wid = m.width[s];
+    const long long soff = m.soff[s];
+    const unsigned long long bit = 1ull << lane;
+    auto dense = [&](int cell) { return __longlong_as_double((long long)cells[cell]); };
+    auto put = [&](int cell, double v) { cells[cell] = (unsigned long long)__double_as_longlong(v); };
+    int failed = 0;
+    for (long long i = first; i < last; ++i) {                   // uniform
+        int ni = m.len[i];
+        ni = __builtin_amdgcn_readfirstlane(ni < wid ? ni : wid);
+        const bool extra = W == 64 && ni > 64;                   // a 65th entry: the own entry behind 64 neighbours, or the row fails
+        ni = ni < W ? ni : W;
+        const long long at_i = soff + (i - first) + 64LL * lane;
+        const bool mine = lane < ni;
+        const long long r = mine ? (long long)m.col[at_i] : -1;
+        double ti = mine ? m.c * m.val[at_i] : 0.0;
+        double di = m.dvec ? m.dvec[i] : m.dconst;
+        bool wild = mine && (r < 0 || r >= m.nrows);
+        // own entries (column i) belong to the diagonal: added onto d_i in entry order, in every row
+        for (unsigned long long left = __ballot(mine && r == i); left; left &= left - 1) di += __shfl(ti, __builtin_ctzll(left), 64);
+        if (extra) {
+            if (m.col[at_i - 64LL * lane + 64LL * 64] == i) di += m.c * m.val[at_i - 64LL * lane + 64LL * 64];
+            else wild = true;
+        }
+        if (mine && r == i) ti = 0.0;
+        bool dead = mine && r == i;
+        for (int l = 0; l < ni; ++l) {                           // uniform
+            const long long rl = __shfl(r, l, 64);
+            if (l < lane && rl == r) dead = true;
+        }
+        const bool live = mine && !dead && !wild;
+        const unsigned long long livemask = __ballot(live), deadmask = __ballot(mine && !live && !wild && r != i);
+        for (int t = lane; t < CELLS; t += 64) { keys[t] = -1; cells[t] = 0ull; }
+        const int a = lane + 1, row_a = a * (a + 1) / 2;
+        if (mine)
+            for (int b = 0; b <= a; ++b) G[row_a + b] = b == a && !live ? 1.0 : 0.0;     // a dead slot is an identity row
+        __syncthreads();
+        // the cells of the columns, and lane l's row J[l + 1] into its registers
+        const int cell_i = krylov_spai_cell<CELLS>(keys, (int32_t)i);
+        const int cell_d = mine && !wild ? krylov_spai_cell<CELLS>(keys, (int32_t)r) : cell_i;
+        int n = 0;
+        long long at_r = 0;
+        double dr = 0.0;
+        bool extra_r = false;
+        if (live) {
+            const int wr = m.width[r >> 6];
+            n = m.len[r];
+            n = n < wr ? n : wr;
+            extra_r = W == 64 && n > 64;
+            n = n < W ? n : W;
+            at_r = m.soff[r >> 6] + (r & 63);
+            dr = m.dvec ? m.dvec[r] : m.dconst;
+        }
+        int nmax = n;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(nmax, off, 64); nmax = o > nmax ? o : nmax; }
+        nmax = __builtin_amdgcn_readfirstlane(nmax);
+        double tv[W];
+        int cell[W];
+        unsigned long long use = 0ull;                           // bit e: entry e is a neighbour's (not an own entry, which dr takes)
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            tv[e] = 0.0; cell[e] = cell_i;
+            if (e < nmax) {                                      // uniform
+                if (e < n) {
+                    const int32_t c = m.col[at_r + 64LL * e];
+                    const double t = m.c * m.val[at_r + 64LL * e];
+                    if (c == r) {
+                        dr += t;
+                    } else {
+                        tv[e] = t;
+                        cell[e] = krylov_spai_cell<CELLS>(keys, c);
+                        use |= 1ull << e;
+                    }
+                }
+            }
+        }
+        bool lost = false;
+        if (extra_r) {
+            if (m.col[at_r + 64LL * 64] == r) dr += m.c * m.val[at_r + 64LL * 64];
+            else lost = true;
+        }
+        if (__ballot(lost) != 0ull) wild = true;                 // uniform from here: the row fails
+        __syncthreads();
+        // which of the lane's entries name a column that its row named before (the diagonal first): bit e of again
+        unsigned long long again = 0ull;
+        if (live) atomicOr(&cells[cell_d], bit);
+#pragma unroll
+        for (int e = 0; e < W; ++e)
+            if (e < nmax && ((use >> e) & 1ull) && (atomicOr(&cells[cell[e]], bit) & bit)) again |= 1ull << e;
+        __syncthreads();
+        for (int t = lane; t < CELLS; t += 64) cells[t] = 0ull;
+        __syncthreads();
+        // slot 0, row i itself: d_i, the entries of the live slots, then those of the dead ones in entry order
+        if (lane == 0) put(cell_i, di);
+        __syncthreads();
+        if (live) put(cell_d, ti);
+        __syncthreads();
+        for (unsigned long long left = deadmask; left; left &= left - 1) {        // uniform
+            if (lane == __builtin_ctzll(left)) put(cell_d, dense(cell_d) + ti);
+            __syncthreads();
+        }
+        const double rhs0 = dense(cell_i);
+        {
+            double acc = 0.0;
+            if (live) {
+                acc = __builtin_fma(dr, dense(cell_d), acc);
+#pragma unroll
+                for (int e = 0; e < W; ++e)
+                    if (e < nmax) acc = __builtin_fma(tv[e], dense(cell[e]), acc);
+                G[row_a] = acc;
+            }
+            const double xl = mine ? dense(cell_d) : 0.0;
+            double g00 = __builtin_fma(di, rhs0, 0.0);
+            for (int l = 0; l < ni; ++l) g00 = __builtin_fma(__shfl(ti, l, 64), __shfl(xl, l, 64), g00);
+            if (lane == 0) G[0] = g00;
+        }
+        __syncthreads();
+        if (mine) cells[cell_d] = 0ull;
+        if (lane == 0) cells[cell_i] = 0ull;
+        __syncthreads();
+        // the live slots, one after the other: the owner spreads its row, every lane at or behind it forms its G[a, b]
+        double rhs = 0.0;
+        for (unsigned long long left = livemask; left; left &= left - 1) {        // uniform
+            const int lb = __builtin_ctzll(left);
+            if (lane == lb) {
+                put(cell_d, dr);
+#pragma unroll
+                for (int e = 0; e < W; ++e)
+                    if (e < nmax && ((use & ~again) >> e) & 1ull) put(cell[e], tv[e]);
+#pragma unroll
+                for (int e = 0; e < W; ++e)
+                    if (e < nmax && ((again >> e) & 1ull)) put(cell[e], dense(cell[e]) + tv[e]);
+                rhs = dense(cell_i);
+            }
+            __syncthreads();
+            if (live && lane >= lb) {
+                double acc = __builtin_fma(dr, dense(cell_d), 0.0);
+#pragma unroll
+                for (int e = 0; e < W; ++e)
+                    if (e < nmax) acc = __builtin_fma(tv[e], dense(cell[e]), acc);
+                G[row_a + lb + 1] = acc;
+            }
+            __syncthreads();
+            if (lane == lb) {
+                cells[cell_d] = 0ull;
+#pragma unroll
+                for (int e = 0; e < W; ++e)
+                    if (e < nmax && ((use >> e) & 1ull)) cells[cell[e]] = 0ull;
+            }
+            __syncthreads();
+        }
+        // G = L D L^T in place, L y = rhs with it, then z = D^-1 y and L^T q = z
+        bool bad = __ballot(wild) != 0ull;
+        double y = rhs, y0 = rhs0;
+        for (int k = 0; k <= ni && !bad; ++k) {                  // uniform
+            const double dk = G[k * (k + 1) / 2 + k];
+            if (!(dk > 0.0 && __builtin_isfinite(dk))) { bad = true; break; }
+            const double yk = k == 0 ? y0 : __shfl(y, k - 1, 64);
+            double lak = 0.0;
+            if (mine && a > k) {
+                lak = G[row_a + k] / dk;
+                for (int b = k + 1; b <= a; ++b) G[row_a + b] = __builtin_fma(-lak, G[b * (b + 1) / 2 + k], G[row_a + b]);
+                y = __builtin_fma(-lak, yk, y);
+            }
+            __syncthreads();
+            if (mine && a > k) G[row_a + k] = lak;
+            __syncthreads();
+        }
+        double q = 0.0, q0 = 0.0;
+        if (!bad) {                                              // uniform
+            q = mine ? y / G[row_a + a] : 0.0;
+            q0 = y0 / G[0];
+            for (int k = ni; k >= 1; --k) {                      // uniform: slot k is final, the slots before it take it off
+                const double qk = __shfl(q, k - 1, 64);
+                const int row_k = k * (k + 1) / 2;
+                if (mine && a < k) q = __builtin_fma(-G[row_k + a], qk, q);
+                q0 = __builtin_fma(-G[row_k], qk, q0);
+            }
+            if (__ballot(!__builtin_isfinite(q)) != 0ull || !__builtin_isfinite(q0)) bad = true;
+        }
+        if (lane == 0) qd[i] = bad ? 0.0 : q0;
+        if (mine) qv[at_i] = bad || !live ? 0.0 : q;
+        if (extra && lane == 0) qv[at_i + 64LL * 64] = 0.0;
+        failed += bad ? 1 : 0;
+        __syncthreads();
+    }
+    if (lane == 0) counts[s] = (double)failed;
+}
+
+// The transposed planes: qd and the counts as they are, qv through the operator's (dest, src) pairs into the transposed structure.
+__global__ void __launch_bounds__(256) krylov_spai_transpose_kernel(long long npairs, const int32_t* dest, const int32_t* src, long long head,
+                                                                    const double* planes, double* planes_t) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t < head) planes_t[t] = planes[t];
+    if (t < npairs) planes_t[head + dest[t]] = planes[head + src[t]];
+}
+
+// out = Q in, or (acc) acc += Q in: krylov_spmv_kernel's row sum on the plane qv with the diagonal qd and c = 1, no dot product.
+__global__ void __launch_bounds__(256) krylov_spai_apply_kernel(const KrylovSys q, const double* in, double* out, double* acc,
+                                                                const KrylovScalars* sc, int always) {
+    if (!always && sc->done) return;                             // uniform: the whole grid
+    const int lane = threadIdx.x & 63;
+    const long long s = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long row = s * 64 + lane;
+    if (s * 64 >= q.nrows) return;                               // wave-uniform
+    const int wid = __builtin_amdgcn_readfirstlane(q.width[s]);
+    const long long at = q.soff[s] + lane;
+    int n = row < q.nrows ? q.len[row] : 0;
+    n = n < wid ? n : wid;
+    const double sum = krylov_row_sum(q.col + at, q.val + at, in, wid, n);
+    if (row < q.nrows) {
+        const double z = __builtin_fma(q.c, sum, q.dvec[row] * in[row]);
+        if (acc) acc[row] = acc[row] + z;
+        else out[row] = z;
+    }
+}
+
+static KrylovSys krylov_spai_system(const KrylovSys& m, const KrylovSpai& p) {
+    KrylovSys q = m;
+    q.val = p.qv; q.dvec = p.qd; q.dconst = 0.0; q.c = 1.0;
+    return q;
+}
+
+static void krylov_spai_apply(const KrylovSys& q, long long nwg, const double* in, double* out, double* acc, const KrylovScalars* sc,
+                              int always, hipStream_t s) {
+    hipLaunchKernelGGL(krylov_spai_apply_kernel, dim3((unsigned)nwg), dim3(256), 0, s, q, in, out, acc, sc, always);
+}
+
+// An iteration of BiCGSTAB with P = Q: krylov_update_kernel without a diagonal, and phat = Q p, shat = Q s by launches of their own.
+static void krylov_spai_iterations(const KrylovSys& m, const KrylovSys& q, const KrylovWork& w, double* x, int64_t niter, hipStream_t s) {
+    const dim3 grid((unsigned)w.nwg), block(256);
+    const KrylovScalars* sc = w.sc;
+    const long long nrows = m.nrows;
+    double* const none = nullptr;
+    for (int64_t it = 0; it < niter; ++it) {
+        hipLaunchKernelGGL((krylov_update_kernel<UPDATE_P>), grid, block, 0, s, nrows, w, x, sc);
+        krylov_spai_apply(q, w.nwg, w.p, w.phat, none, sc, 0, s);
+        hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_V>), grid, block, 0, s, m, (const double*)w.phat, (const double*)w.r0, w.v, none, w.partial, sc, 0);
+        krylov_reduce(REDUCE_ALPHA, w, w.nwg, 1, 0.0, 0.0, 0, s);
+        hipLaunchKernelGGL((krylov_update_kernel<UPDATE_S>), grid, block, 0, s, nrows, w, x, sc);
+        krylov_spai_apply(q, w.nwg, w.s, w.shat, none, sc, 0, s);
+        hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_T>), grid, block, 0, s, m, (const double*)w.shat, (const double*)w.s, w.t, none, w.partial, sc, 0);
+        krylov_reduce(REDUCE_OMEGA, w, w.nwg, 2, 0.0, 0.0, 0, s);
+        hipLaunchKernelGGL((krylov_update_kernel<UPDATE_X>), grid, block, 0, s, nrows, w, x, sc);
+        krylov_reduce(REDUCE_RHO, w, w.nwg, 2, 0.0, 0.0, 0, s);
+    }
+}
+
+// A cycle of BiCGSTAB(2) with P = Q, 19 launches: every update leaves what P is applied to in `pre` (the workspace's tenth vector), an
+// apply forms hat = Q pre for the product behind it, and the last one adds Q pre to x: between U4, which every check of the cycle's
+// scalars precedes, and the reduce that takes the stop.
+static void krylov_spai_l2_cycles(const KrylovSys& m, const KrylovSys& q, const KrylovL2Work& w, double* pre, double* x, int64_t ncycles,
+                                  hipStream_t s) {
+    const dim3 grid((unsigned)w.nwg), block(256);
+    const KrylovScalars* sc = w.sc;
+    const long long nrows = m.nrows;
+    const double *rt = w.rt, *hat = w.hat, *W = nullptr;
+    double* const none = nullptr;
+    KrylovL2Work u = w;                                          // the update kernels' view: their `hat` is pre, and no diagonal
+    u.hat = pre; u.dinv = nullptr;
+    auto reduce = [&](int mode) {
+        hipLaunchKernelGGL(krylov_l2_reduce_kernel, dim3(1), block, 0, s, mode, (const double*)w.partial, w.nwg, w.sc, 0.0, 0.0);
+    };
+    auto apply = [&](double* acc) { krylov_spai_apply(q, w.nwg, pre, w.hat, acc, sc, 0, s); };
+    for (int64_t it = 0; it < ncycles; ++it) {
+        hipLaunchKernelGGL((krylov_l2_update_kernel<0, L2_U0>), grid, block, 0, s, nrows, u, W, none);
+        apply(none);
+        hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_V>), grid, block, 0, s, m, hat, rt, w.u1, none, w.partial, sc, 0);
+        reduce(L2_ALPHA);
+        hipLaunchKernelGGL((krylov_l2_update_kernel<0, L2_U1>), grid, block, 0, s, nrows, u, W, none);
+        apply(none);
+        hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_V>), grid, block, 0, s, m, hat, rt, w.r1, none, w.partial, sc, 0);
+        reduce(L2_BETA);
+        hipLaunchKernelGGL((krylov_l2_update_kernel<0, L2_U2>), grid, block, 0, s, nrows, u, W, none);
+        apply(none);
+        hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_V>), grid, block, 0, s, m, hat, rt, w.u2, none, w.partial, sc, 0);
+        reduce(L2_ALPHA1);
+        hipLaunchKernelGGL((krylov_l2_update_kernel<0, L2_U3>), grid, block, 0, s, nrows, u, W, none);
+        apply(none);
+        hipLaunchKernelGGL(krylov_l2_spmv_kernel, grid, block, 0, s, m, hat, (const double*)w.r, (const double*)w.r1, w.r2, w.partial, sc);
+        reduce(L2_MR);
+        hipLaunchKernelGGL((krylov_l2_update_kernel<0, L2_U4, true>), grid, block, 0, s, nrows, u, W, none);
+        apply(x);
+        reduce(L2_END);
+    }
+}
+
+static int krylov_spai_arguments(const char* who, int64_t nrows, int64_t nslices, const void* planes) {
+    if (!planes) { set_error(std::string(who) + ": null array"); return WLSQM_EVALUE; }
+    if (nslices != (nrows + 63) / 64) { set_error(std::string(who) + ": nslices must be ceil(nrows / 64)"); return WLSQM_EVALUE; }
+    return WLSQM_OK;
+}
+
+static int krylov_tolerances(const char* who, const void* b, const void* x, double rtol, double atol, int64_t maxiter) {
+    if (!b || !x) { set_error(std::string(who) + ": null array"); return WLSQM_EVALUE; }
+    if (!(rtol >= 0.0) || !(atol >= 0.0) || !std::isfinite(rtol) || !std::isfinite(atol)) {
+        set_error(std::string(who) + ": rtol and atol must be finite and >= 0");
+        return WLSQM_EVALUE;
+    }
+    if (maxiter < 0 || maxiter > INT32_MAX) { set_error(std::string(who) + ": maxiter must be 0 .. 2^31 - 1"); return WLSQM_EVALUE; }
+    return WLSQM_OK;
 }
 
 }  // namespace wlsqm
@@ -1683,6 +2039,130 @@ int wlsqm_hip_krylov_l2_device(int64_t nrows, int64_t nslices, const int32_t* le
     }
     WLSQM_HIP_CHECK(hipGetLastError());
     note_kernel(precond > 1 ? "krylov-l2-update-block" : "krylov-l2-update");
+    return WLSQM_OK;
+}
+
+int64_t wlsqm_hip_krylov_spai_bytes(int64_t nrows, int64_t total) {
+    if (nrows < 0 || total < 0) return -1;
+    return (int64_t)sizeof(double) * (nrows + (nrows + 63) / 64 + total);
+}
+
+int wlsqm_hip_krylov_spai_build_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                       const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                       int max_width, void* planes, int64_t npairs, const int32_t* pair_dest, const int32_t* pair_src,
+                                       void* planes_t, int device, void* stream) {
+    KrylovSys m;
+    int rc = krylov_spai_arguments("krylov_spai_build", nrows, nslices, planes);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_system("krylov_spai_build", m, nrows, nslices, len, width, soff, col, val, diag, diag_const, scale, planes);
+    if (rc != WLSQM_OK) return rc;
+    if (max_width < 0 || max_width > KRYLOV_SPAI_CAP) {
+        set_error("krylov_spai_build: max_width must be 0 .. 65, the widest slice of the matrix");
+        return WLSQM_EVALUE;
+    }
+    if (planes_t && (npairs < 0 || (npairs > 0 && (!pair_dest || !pair_src)))) { set_error("krylov_spai_build: null array"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const KrylovSpai p = krylov_spai_planes(planes, nrows);
+    const dim3 grid((unsigned)nslices);
+    if (max_width <= 16) hipLaunchKernelGGL(krylov_spai_kernel<16>, grid, dim3(64), 0, s, m, p.qd, p.qv, p.counts);
+    else if (max_width <= 28) hipLaunchKernelGGL(krylov_spai_kernel<28>, grid, dim3(64), 0, s, m, p.qd, p.qv, p.counts);
+    else if (max_width <= 44) hipLaunchKernelGGL(krylov_spai_kernel<44>, grid, dim3(64), 0, s, m, p.qd, p.qv, p.counts);
+    else hipLaunchKernelGGL(krylov_spai_kernel<64>, grid, dim3(64), 0, s, m, p.qd, p.qv, p.counts);
+    if (planes_t) {
+        const long long head = nrows + nslices, most = head > npairs ? head : npairs;
+        hipLaunchKernelGGL(krylov_spai_transpose_kernel, dim3((unsigned)((most + 255) / 256)), dim3(256), 0, s, (long long)npairs, pair_dest,
+                           pair_src, head, (const double*)planes, static_cast<double*>(planes_t));
+    }
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-spai");
+    return WLSQM_OK;
+}
+
+int wlsqm_hip_krylov_spai_apply_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                       const int32_t* col, const void* planes, const double* v, double* out, int device, void* stream) {
+    KrylovSys m;
+    int rc = krylov_spai_arguments("krylov_spai_apply", nrows, nslices, planes);
+    if (rc != WLSQM_OK) return rc;
+    const KrylovSpai p = krylov_spai_planes(planes, nrows < 0 ? 0 : nrows);
+    rc = krylov_system("krylov_spai_apply", m, nrows, nslices, len, width, soff, col, p.qv, p.qd, 0.0, 1.0, planes);
+    if (rc != WLSQM_OK) return rc;
+    if (!v || !out) { set_error("krylov_spai_apply: null array"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    krylov_spai_apply(m, (nrows + 255) / 256, v, out, nullptr, nullptr, 1, (hipStream_t)stream);
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-spai-apply");
+    return WLSQM_OK;
+}
+
+int wlsqm_hip_krylov_spai_start_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                       const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                       int l2, const void* planes, const double* b, const double* x, double rtol, double atol,
+                                       int64_t maxiter, void* workspace, int device, void* stream) {
+    KrylovSys m;
+    int rc = krylov_spai_arguments("krylov_spai_start", nrows, nslices, planes);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_system("krylov_spai_start", m, nrows, nslices, len, width, soff, col, val, diag, diag_const, scale, workspace);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_tolerances("krylov_spai_start", b, x, rtol, atol, maxiter);
+    if (rc != WLSQM_OK) return rc;
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const KrylovSpai p = krylov_spai_planes(planes, nrows);
+    const long long nwg = (nrows + 255) / 256;
+    const dim3 grid((unsigned)nwg);
+    KrylovScalars* sc = static_cast<KrylovScalars*>(workspace);
+    hipLaunchKernelGGL(krylov_reduce_kernel, dim3(1), dim3(256), 0, s, (int)REDUCE_DIAG, (const double*)p.counts, (long long)nslices, 1, sc, rtol,
+                       atol, (int)maxiter);
+    if (l2) {
+        const KrylovL2Work w = krylov_l2_work(workspace, nrows, 1);
+        hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_RESIDUAL>), grid, dim3(256), 0, s, m, x, b, w.r, w.rt, w.partial, (const KrylovScalars*)sc, 0);
+        note_kernel("krylov-spmv-dot");
+        hipLaunchKernelGGL(krylov_l2_reduce_kernel, dim3(1), dim3(256), 0, s, (int)L2_START, (const double*)w.partial, w.nwg, sc, rtol, atol);
+        WLSQM_HIP_CHECK(hipGetLastError());
+        note_kernel("krylov-l2-reduce");
+        return WLSQM_OK;
+    }
+    const KrylovWork w = krylov_work(workspace, nrows, true);
+    hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_RESIDUAL>), grid, dim3(256), 0, s, m, x, b, w.r, w.r0, w.partial, (const KrylovScalars*)sc, 0);
+    note_kernel("krylov-spmv-dot");
+    krylov_reduce(REDUCE_RESIDUAL, w, w.nwg, 2, rtol, atol, (int)maxiter, s);
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-reduce");
+    return WLSQM_OK;
+}
+
+int wlsqm_hip_krylov_spai_iterate_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                         const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                         int l2, const void* planes, double* x, int64_t niter, void* workspace, int device, void* stream) {
+    KrylovSys m;
+    int rc = krylov_spai_arguments("krylov_spai_iterate", nrows, nslices, planes);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_system("krylov_spai_iterate", m, nrows, nslices, len, width, soff, col, val, diag, diag_const, scale, workspace);
+    if (rc != WLSQM_OK) return rc;
+    if (!x) { set_error("krylov_spai_iterate: null array"); return WLSQM_EVALUE; }
+    if (niter < 0) { set_error("krylov_spai_iterate: niter must be >= 0"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK || niter == 0) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const KrylovSys q = krylov_spai_system(m, krylov_spai_planes(planes, nrows));
+    if (l2) {
+        KrylovL2Work w = krylov_l2_work(workspace, nrows, 1);
+        krylov_spai_l2_cycles(m, q, w, w.dinv, x, niter, s);
+    } else {
+        KrylovWork w = krylov_work(workspace, nrows, true);
+        w.dinv = nullptr;                                        // the update kernels form p and s only
+        krylov_spai_iterations(m, q, w, x, niter, s);
+    }
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel(l2 ? "krylov-spai-l2-update" : "krylov-spai-update");
     return WLSQM_OK;
 }
 

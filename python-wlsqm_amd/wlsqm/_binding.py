@@ -242,6 +242,19 @@ def lib():
         L.wlsqm_hip_krylov_l2_start_device.restype = C.c_int
         L.wlsqm_hip_krylov_l2_device.argtypes = system + [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
         L.wlsqm_hip_krylov_l2_device.restype = C.c_int
+    # the sparse approximate inverse preconditioner of those solves (wlsqm.hip.ApproximateInverse)
+    if hasattr(L, "wlsqm_hip_krylov_spai_build_device"):
+        system = [C.c_int64, C.c_int64] + [C.c_void_p] * 6 + [C.c_double, C.c_double]
+        L.wlsqm_hip_krylov_spai_bytes.argtypes = [C.c_int64, C.c_int64]
+        L.wlsqm_hip_krylov_spai_bytes.restype = C.c_int64
+        L.wlsqm_hip_krylov_spai_build_device.argtypes = system + [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                                  C.c_void_p]
+        L.wlsqm_hip_krylov_spai_apply_device.argtypes = [C.c_int64, C.c_int64] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_spai_start_device.argtypes = system + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int64,
+                                                                  C.c_void_p, C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_spai_iterate_device.argtypes = system + [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+        for name in ("build", "apply", "start", "iterate"):
+            getattr(L, "wlsqm_hip_krylov_spai_%s_device" % name).restype = C.c_int
     # batched dense solves (wlsqm.utils.lapackdrivers, wlsqm.hip.*_batched)
     for op in ("getrf", "gesv", "sytrf", "sysv"):
         solve = op in ("gesv", "sysv")

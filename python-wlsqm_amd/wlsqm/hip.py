@@ -19,7 +19,7 @@ __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_c
            "differentiable_solve", "differentiable_solve_many",
            "InterpolationPlan", "differentiable_evaluate",
            "StencilOperator", "stencil_rows", "differentiable_stencil_apply", "StencilSolver", "SolveInfo",
-           "SolveGradients", "BlockJacobi", "differentiable_stencil_solve", "differentiable_stencil_solve_many",
+           "SolveGradients", "BlockJacobi", "ApproximateInverse", "differentiable_stencil_solve", "differentiable_stencil_solve_many",
            "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
            "getrf_batched", "getrs_batched", "gesv_batched", "sytrf_batched", "sytrs_batched", "sysv_batched", "symmetrize_batched"]
 
@@ -1986,7 +1986,7 @@ and dL/d(scale) (a 0-d device tensor); None for what was not asked for."""
 
 SolveInfo = collections.namedtuple("SolveInfo", "status iterations residual")
 SolveInfo.__doc__ = """What a StencilSolver says of a solve.  status: 0 converged, 1 iteration limit, 2 breakdown (rho = 0 or (r0, v) = 0),
-3 a non-finite scalar, 4 a zero or non-finite Jacobi diagonal or a singular or non-finite block of a BlockJacobi, -1 still running (enqueue with fewer iterations than the solve needs
+3 a non-finite scalar, 4 a zero or non-finite Jacobi diagonal, a singular or non-finite block of a BlockJacobi or a singular row of an ApproximateInverse, -1 still running (enqueue with fewer iterations than the solve needs
 always ends in 1).  With method="bicgstab2", 2 is rho0 = 0, (rt, u1) = 0 or (rt, u2) = 0.  iterations: those completed.  residual: the recursive ||r||_2 (NaN with status 4: no residual was formed)."""
 
 
@@ -2005,6 +2005,22 @@ class BlockJacobi:
 
     def __repr__(self):
         return "BlockJacobi(block=%d, refresh=%r)" % (self.block, self.refresh)
+
+
+class ApproximateInverse:
+    """The sparse approximate inverse preconditioner of a StencilSolver: P = Q, the matrix on M's own pattern whose
+    row i minimises ||q^T M - e_i^T||_2, so that Q M ~ I: one small dense least-squares problem per row ("krylov-spai"), applied as one
+    more sparse product on the operator's structure.  Unlike the blocks it couples every row with all its neighbours, whatever the
+    order of the cloud: for the large steps (tau ~ 1, above all in 3D) that neither "jacobi" nor a BlockJacobi reaches.  An iteration
+    costs about twice a Jacobi iteration.  Rows of up to 64 neighbours (and their own entry); one right-hand side (nfields = 1); both methods.
+    refresh: what it means for a BlockJacobi: True recomputes Q at the start of every solve / enqueue, False computes it at the first
+    start and again only by solver.refresh()."""
+
+    def __init__(self, refresh=True):
+        self.refresh = bool(refresh)
+
+    def __repr__(self):
+        return "ApproximateInverse(refresh=%r)" % (self.refresh,)
 
 
 class StencilSolver:
@@ -2034,7 +2050,12 @@ class StencilSolver:
     preconditioner, transposed solves and differentiable_stencil_solve included; nfields must be 1.  A cycle is 4 products in 14
     launches and counts as 2 iterations, so `iterations`, `maxiter` and `check_every` mean what they mean for "bicgstab"; the stop is
     taken at the end of a cycle, so a solve may pass an odd maxiter by one, and enqueue(iterations=k) enqueues ceil(k / 2) cycles.
-    Status 2 is then rho0 = 0, (rt, u1) = 0 or (rt, u2) = 0.  The workspace is 10 npoints + 5 ceil(npoints / 256) + 16 doubles."""
+    Status 2 is then rho0 = 0, (rt, u1) = 0 or (rt, u2) = 0.  The workspace is 10 npoints + 5 ceil(npoints / 256) + 16 doubles.
+    preconditioner=ApproximateInverse(): the sparse approximate inverse Q on the matrix's own pattern, with
+    either method: 10 launches per iteration, 19 per cycle (Q is applied by launches of its own).  It adds its planes, npoints +
+    ceil(npoints / 64) + the operator's stored entries doubles, and those of Q^T (the same numbers moved into the transposed
+    structure) at the first transposed use.  refresh(), precondition(v) and preconditioner_matrix() serve it; a row whose least-squares
+    problem is singular is status 4.  Rows of more than 64 neighbours and nfields > 1 are refused here (ValueError)."""
 
     def __init__(self, op, o=0, diag=1.0, scale=1.0, preconditioner="jacobi", nfields=1, method="bicgstab"):
         self._ws = None
@@ -2056,9 +2077,12 @@ class StencilSolver:
         if not 0 <= int(o) < op.nop:
             raise ValueError("the operator has %d value planes; got o = %d" % (op.nop, int(o)))
         self._block = preconditioner if isinstance(preconditioner, BlockJacobi) else None
-        if self._block is None and preconditioner not in ("jacobi", None):
-            raise ValueError("preconditioner must be 'jacobi' or None, or a BlockJacobi; got %r" % (preconditioner,))
-        self._planes = self._planes_t = None
+        self._spai = preconditioner if isinstance(preconditioner, ApproximateInverse) else None
+        if self._block is None and self._spai is None and preconditioner not in ("jacobi", None):
+            raise ValueError("preconditioner must be 'jacobi' or None, or a BlockJacobi or an ApproximateInverse; got %r" % (preconditioner,))
+        if self._spai is not None and nfields > 1:
+            raise ValueError("an ApproximateInverse preconditions one right-hand side at a time: nfields must be 1; got %d" % nfields)
+        self._planes = self._planes_t = self._planes_t_of = None
         self._factored = self._factored_t = False
         self._op, self._o, self._jacobi = op, int(o), 1 if preconditioner == "jacobi" else 0
         self.npoints, self._device = op.npoints, op._device
@@ -2072,6 +2096,10 @@ class StencilSolver:
         pi = getattr(op, "_point_index", None)
         if pi is not None and not bool((pi[:op.ncases].long() == torch.arange(op.ncases, device=pi.device)).all()):
             raise ValueError("row j of the operator must be the equation of point j: point_index must be None or the identity")
+        if self._spai is not None:                                      # one host read: the widest slice and the longest row
+            self._max_width, most = torch.stack([op._m["width"].max().long(), op._nk.max().long()]).tolist()
+            if most > 64:                                               # the own entry of an F-known row may come on top: 65 stored entries
+                raise ValueError("an ApproximateInverse serves rows of up to 64 neighbours; the operator's longest row has %d" % most)
         if self._l2:
             nbytes = int(B.lib().wlsqm_hip_krylov_l2_workspace_bytes(self.npoints))
         elif nfields == 1:
@@ -2079,12 +2107,15 @@ class StencilSolver:
         else:
             nbytes = int(B.lib().wlsqm_hip_krylov_many_workspace_bytes(self.npoints, nfields))
         self._ws = torch.zeros((nbytes // 8,), dtype=torch.float64, device=self._device)
-        if self._block is not None:
+        if self._block is not None or self._spai is not None:
             self._planes = self._new_planes()
 
-    def _new_planes(self):
+    def _new_planes(self, transpose=False):
         import torch
-        nbytes = int(B.lib().wlsqm_hip_krylov_block_bytes(self.npoints, self._block.block))
+        if self._spai is not None:
+            nbytes = int(B.lib().wlsqm_hip_krylov_spai_bytes(self.npoints, (self._op._t if transpose else self._op._m)["total"]))
+        else:
+            nbytes = int(B.lib().wlsqm_hip_krylov_block_bytes(self.npoints, self._block.block))
         return torch.zeros((nbytes // 8,), dtype=torch.float64, device=self._device)
 
     def _live(self):
@@ -2094,7 +2125,7 @@ class StencilSolver:
 
     def close(self):
         """Release the workspace now; harmless when called again.  The operator stays the caller's."""
-        self._ws = self._op = self._planes = self._planes_t = None
+        self._ws = self._op = self._planes = self._planes_t = self._planes_t_of = None
         if hasattr(self.__dict__.get("diag"), "dim"):
             self.diag = None
 
@@ -2155,9 +2186,13 @@ class StencilSolver:
     def _transposed(self, transpose, stream):
         """The operator's transposed matrix, and a BlockJacobi's transposed plane, built at the first transposed use (prepare_transpose:
         RuntimeError inside a capture)."""
-        if transpose and (self._op._t is None or (self._block is not None and self._planes_t is None)):
+        if transpose and (self._op._t is None or (self._block is not None and self._planes_t is None) or self._stale_transposed()):
             self.prepare_transpose(stream)
         return bool(transpose)
+
+    def _stale_transposed(self):
+        """An ApproximateInverse's transposed planes are missing, or belong to a transposed matrix that the operator has dropped."""
+        return self._spai is not None and (self._planes_t is None or self._planes_t_of is not self._op._tpair)
 
     def prepare_transpose(self, stream=None):
         """Build now what a transposed solve needs: the operator's transposed matrix (op.prepare_transpose) and, with a BlockJacobi, the
@@ -2178,6 +2213,18 @@ class StencilSolver:
                 self._planes_t = self._new_planes()
             self._factored_t = False
             built = True
+        if self._stale_transposed():
+            if self._op._tpair is None:
+                raise ValueError("the operator's transposed matrix is too large for its index pairs (2^31 stored entries): an "
+                                 "ApproximateInverse cannot carry its values into it")
+            with _torch_stream(stream, self._device):
+                if self._device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("the solver has no transposed approximate inverse yet and the stream is capturing: call "
+                                       "prepare_transpose before the capture")
+                self._planes_t = self._new_planes(transpose=True)
+            self._planes_t_of = self._op._tpair
+            self._factored_t = False
+            built = True
         return built
 
     def _block_args(self, transpose=False):
@@ -2187,12 +2234,20 @@ class StencilSolver:
         """"krylov-blocks" when P is due: at every start with refresh=True, else at the first one, when the transposed plane is new, and
         from refresh().  One launch on the forward matrix, which fills the transposed plane too when this start needs it or, with
         refresh=False, whenever it exists (the two stay the inverses of the same blocks)."""
-        bj = self._block
+        bj = self._block if self._block is not None else self._spai
         if not (force or bj.refresh or not self._factored or (transpose and not self._factored_t)):
             return
         both = self._planes_t is not None and (transpose or not bj.refresh or force)
-        B.check(B.lib().wlsqm_hip_krylov_block_factor_device(*self._system(False), bj.block, _ptr(self._planes),
-                                                             _ptr(self._planes_t) if both else None, dev, s))
+        if self._spai is not None:          # "krylov-spai": Q from the forward matrix, and its values moved into the transposed planes
+            both = both and not self._stale_transposed()
+            pair = self._op._tpair if both else None
+            B.check(B.lib().wlsqm_hip_krylov_spai_build_device(*self._system(False), self._max_width, _ptr(self._planes),
+                                                               int(pair.shape[1]) if both else 0, _ptr(pair[0]) if both else None,
+                                                               _ptr(pair[1]) if both else None, _ptr(self._planes_t) if both else None,
+                                                               dev, s))
+        else:
+            B.check(B.lib().wlsqm_hip_krylov_block_factor_device(*self._system(False), bj.block, _ptr(self._planes),
+                                                                 _ptr(self._planes_t) if both else None, dev, s))
         self._factored = True
         if both:
             self._factored_t = True
@@ -2200,10 +2255,11 @@ class StencilSolver:
             self._factored_t = False
 
     def refresh(self, stream=None):
-        """Recompute a BlockJacobi's P from the operator's arrays as they are on `stream` now: what refresh=False leaves to the caller
-        (after op.update, set_coefficients or a change of diag or scale).  One kernel launch, no allocation, no host read: capturable."""
+        """Recompute a BlockJacobi's or an ApproximateInverse's P from the operator's arrays as they are on `stream` now: what
+        refresh=False leaves to the caller (after op.update, set_coefficients or a change of diag or scale).  One kernel launch (two
+        with an ApproximateInverse's transposed planes), no allocation, no host read: capturable."""
         self._live()
-        if self._block is None:
+        if self._block is None and self._spai is None:
             raise ValueError("refresh() belongs to a BlockJacobi preconditioner; this solver's is %s, which every solve recomputes"
                              % ("'jacobi'" if self._jacobi else "None"))
         s, dev = _stream_and_device(self._planes, stream)
@@ -2213,10 +2269,11 @@ class StencilSolver:
     def precondition(self, v, out=None, stream=None, transpose=False):
         """z = P v (P^T v with transpose=True), P the BlockJacobi's block inverses as the next solve would use them: factored first when
         due (refresh=True: always).  One launch ("krylov-precondition") behind the factor's; v and out (npoints,) float64 contiguous,
-        not overlapping.  ValueError on a solver without a BlockJacobi."""
+        not overlapping.  With an ApproximateInverse: z = Q v ("krylov-spai-apply"), Q^T v on the transposed structure.  ValueError on a
+        solver with neither."""
         import torch
         self._live()
-        if self._block is None:
+        if self._block is None and self._spai is None:
             raise ValueError("precondition() belongs to a BlockJacobi preconditioner")
         if out is None:
             with _torch_stream(stream, self._device):
@@ -2225,6 +2282,10 @@ class StencilSolver:
         transpose = self._transposed(transpose, stream)
         s, dev = _stream_and_device(v, stream)
         self._factor(dev, s, transpose)
+        if self._spai is not None:                                       # "krylov-spai-apply": out = Q v, or Q^T v on the transposed structure
+            B.check(B.lib().wlsqm_hip_krylov_spai_apply_device(*self._system(transpose)[:6], *self._spai_args(transpose)[1:], _ptr(v),
+                                                               _ptr(out), dev, s))
+            return out
         B.check(B.lib().wlsqm_hip_krylov_block_precondition_device(self.npoints, *self._block_args(transpose), _ptr(v), _ptr(out), dev, s))
         return out
 
@@ -2242,6 +2303,57 @@ class StencilSolver:
             W = self._planes[:nslices * nb * 64].view(nslices, nb, 64 // nb, nb)          # [slice, j, block of the slice, i]
             return W.permute(0, 2, 3, 1).reshape(-1, nb, nb)[:(self.npoints + nb - 1) // nb].clone()
 
+    def _spai_args(self, transpose=False):
+        return int(self._l2), _ptr(self._planes_t if transpose else self._planes)
+
+    def _spai_parts(self, transpose=False):
+        """(m, qd, qv): the structure that Q (or Q^T) lies on, its diagonal and its plane as views of the solver's planes."""
+        n = self.npoints
+        planes = self._planes_t if transpose else self._planes
+        return (self._op._t if transpose else self._op._m), planes[:n], planes[n + (n + 63) // 64:]
+
+    def preconditioner_matrix(self, transpose=False, stream=None):
+        """An ApproximateInverse's Q (Q^T with transpose=True, from the planes that a transposed solve applies) as a new
+        torch.sparse_csr_tensor (npoints, npoints), built first when due (refresh=True: always).  The entries are coalesced: a dead
+        slot — one whose column an earlier slot of its row names, coefficient exactly 0.0 — is dropped into the live one of its
+        column; preconditioner_coefficients() shows them apart.  It allocates and reads on the host: not for a graph capture."""
+        import torch
+        self._live()
+        if self._spai is None:
+            raise ValueError("preconditioner_matrix() belongs to an ApproximateInverse preconditioner")
+        self._no_capture("preconditioner_matrix", stream)
+        transpose = self._transposed(transpose, stream)
+        s, dev = _stream_and_device(self._planes, stream)
+        self._factor(dev, s, transpose)
+        m, qd, qv = self._spai_parts(transpose)
+        n = self.npoints
+        with _torch_stream(stream, self._device):
+            lens = m["len"].long()
+            j, e = torch.arange(n, device=self._device), torch.arange(int(lens.max()), device=self._device)
+            live = e[None, :] < lens[:, None]
+            src = ((m["soff"][j // 64] + j % 64)[:, None] + 64 * e[None, :])[live]
+            rows = torch.cat([j, j[:, None].expand(n, e.shape[0])[live]])
+            cols = torch.cat([j, m["col"][src].long()])
+            coo = torch.sparse_coo_tensor(torch.stack([rows, cols]), torch.cat([qd, qv[src]]), (n, n))
+            import warnings
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", UserWarning)
+                return coo.coalesce().to_sparse_csr()
+
+    def preconditioner_coefficients(self, stream=None):
+        """(qd (npoints,), slots (npoints, K), own (npoints,)): an ApproximateInverse's Q slot by slot, as the operator's
+        coefficients() lays a value plane out: built first when due; exact zeros in the dead slots and in the padding."""
+        self._live()
+        if self._spai is None:
+            raise ValueError("preconditioner_coefficients() belongs to an ApproximateInverse preconditioner")
+        self._no_capture("preconditioner_coefficients", stream)
+        s, dev = _stream_and_device(self._planes, stream)
+        self._factor(dev, s)
+        m, qd, qv = self._spai_parts()
+        with _torch_stream(stream, self._device):
+            slots, own = self._op.unpack(qv)
+            return qd.clone(), slots, own
+
     def _no_capture(self, what, stream):
         import torch
         with _torch_stream(stream, self._device):
@@ -2256,8 +2368,12 @@ class StencilSolver:
         return self._jacobi, None
 
     def _start(self, b, x, rtol, atol, maxiter, dev, s, transpose=False):
-        if self._block is not None:
+        if self._block is not None or self._spai is not None:
             self._factor(dev, s, transpose)
+        if self._spai is not None:
+            B.check(B.lib().wlsqm_hip_krylov_spai_start_device(*self._system(transpose), *self._spai_args(transpose), _ptr(b), _ptr(x),
+                                                               rtol, atol, maxiter, _ptr(self._ws), dev, s))
+            return
         if self._l2:
             B.check(B.lib().wlsqm_hip_krylov_l2_start_device(*self._system(transpose), *self._precond_args(transpose), _ptr(b), _ptr(x),
                                                              rtol, atol, maxiter, _ptr(self._ws), dev, s))
@@ -2270,6 +2386,10 @@ class StencilSolver:
                                                       _ptr(self._ws), dev, s))
 
     def _iterate(self, x, niter, dev, s, transpose=False):
+        if self._spai is not None:                                       # iterations, or ceil(niter / 2) cycles
+            B.check(B.lib().wlsqm_hip_krylov_spai_iterate_device(*self._system(transpose), *self._spai_args(transpose), _ptr(x),
+                                                                 (niter + 1) // 2 if self._l2 else niter, _ptr(self._ws), dev, s))
+            return
         if self._l2:                                                     # a cycle is two iterations: ceil(niter / 2) cycles
             B.check(B.lib().wlsqm_hip_krylov_l2_device(*self._system(transpose), *self._precond_args(transpose), _ptr(x), (niter + 1) // 2,
                                                        _ptr(self._ws), dev, s))
