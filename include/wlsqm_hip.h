@@ -327,6 +327,32 @@ int wlsqm_hip_nearest_device(int dimension, int64_t ndata, const double* S, int6
  * 2^27 cells in all.  Host arithmetic only: needs no device.  WLSQM_EVALUE for a box outside the searches' domain. */
 int wlsqm_hip_grid_shape_host(int dimension, int64_t npoints, const double* lo, const double* hi, int32_t* g, double* cell);
 
+/* Extension: the Morton order of the device-resident cloud S[npoints, dimension] (csrc/order.hip states the order; DESIGN.md
+ * section 23).  perm[npoints] (int32, device): new position i holds old point perm[i], the stable ascending sort of the keys
+ * (ties go to the smaller old index); inverse[npoints] (int32, device): inverse[perm[i]] = i; keys_sorted[npoints] (int64,
+ * device, nullable): the keys in ascending order; box[2][3] (HOST doubles): the bounding box, lo then hi, that the keys were
+ * taken under.  2D / 3D: 31 / 21 bits per axis of floor((x - lo) / (hi - lo) * 2^B), interleaved (axis 0 lowest); 1D: the
+ * exact order of the doubles.  1 <= npoints < 2^31; S in the domain of wlsqm_hip_knn_device (the same WLSQM_EVALUE and words
+ * otherwise).  Allocates and frees its temporaries; synchronises `stream` before returning. */
+int wlsqm_hip_spatial_order_device(int dimension, int64_t npoints, const double* S, int64_t* keys_sorted, int32_t* perm,
+                                   int32_t* inverse, double* box, int device, void* stream);
+/* Extension: the keys of ANY device-resident points X[n, dimension] under the box lo[dimension] .. hi[dimension] (host arrays;
+ * the box of wlsqm_hip_spatial_order_device places new points in an existing order): keys[n] (int64, device).  Points outside
+ * the box clamp to its ends; a NaN coordinate gives the largest key of the dimension (2^62 - 1, 2^63 - 1; 1D: 2^63 - 1).
+ * Asynchronous, allocates nothing, legal during stream capture. */
+int wlsqm_hip_spatial_keys_device(int dimension, int64_t n, const double* X, const double* lo, const double* hi, int64_t* keys,
+                                  int device, void* stream);
+/* Extension: renumber neighbour lists.  out[i, k] = inverse[hoods[r, k]] for k < nk[r], where r = row_perm[i] (row_perm
+ * nullable: r = i; a permutation of 0 .. ncases - 1 otherwise) and nk is nullable (every slot is live).  hoods[ncases, K] at a
+ * pitch of row_stride >= K, out[ncases, K] at a pitch of K, inverse[npoints], all int32 on the device.  The padding slots
+ * k >= nk[r] get own[i] (own nullable: i), the way wlsqm_hip_ball_device pads its rows.  A live entry outside
+ * 0 .. npoints - 1 is never dereferenced: it is written as -1 and counted in *bad (a device int32 that the CALLER has set,
+ * nullable), and so is every slot of a row whose row_perm entry is no row.  Asynchronous, allocates nothing, legal during
+ * stream capture. */
+int wlsqm_hip_relabel_hoods_device(int64_t ncases, int K, const int32_t* hoods, int64_t row_stride, const int32_t* nk,
+                                   const int32_t* row_perm, const int32_t* inverse, int64_t npoints, const int32_t* own,
+                                   int32_t* out, int32_t* bad, int device, void* stream);
+
 /* Extension: build the stored solution operator of the prepared geometry now (8 x 16 x K' bytes per case, K' = the neighbour
  * slots rounded up to a multiple of 8; shared with guests), so that later stacked solves only enqueue work — e.g. before a stream
  * capture.  Without this call the first wlsqm_hip_expert_solve_many[_device] that wants the operator builds it and synchronises

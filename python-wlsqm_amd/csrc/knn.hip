@@ -39,15 +39,7 @@
 
 namespace wlsqm {
 
-__device__ __forceinline__ unsigned long long key_of(double v) {      // order-preserving map double -> uint64
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-static inline double value_of(unsigned long long k) {
-    const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    double v; memcpy(&v, &u, 8); return v;
-}
-
+// (key_of / value_of, the order-preserving map double <-> uint64: wlsqm_grid.hpp)
 // Grid-stride partial extrema per lane, met per wave by shuffles and per block through LDS: one pair of atomics per block
 // and axis (one per WAVE and axis serialises ~60k same-address atomics in L2 for 1M points: 0.71 ms instead of ~0.03).
 __global__ __launch_bounds__(256) void knn_bbox_kernel(const double* __restrict__ S, long long n, int dim,

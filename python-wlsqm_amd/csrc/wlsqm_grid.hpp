@@ -2,10 +2,26 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "wlsqm_internal.hpp"
 
 namespace wlsqm {
+
+// order-preserving map double -> uint64 and back: what the bounding-box kernel's atomic min / max compare
+__device__ __forceinline__ unsigned long long key_of(double v) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+inline double value_of(unsigned long long k) {
+    const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    double v; memcpy(&v, &u, 8); return v;
+}
+
+// Bounding box of S[n, dim] (knn.hip; shared with order.hip): mm[m] = the least key_of over axis m, mm[3 + m] the greatest, met by atomics
+// on what the caller has set to ~0 and 0.  A NaN wins either way, so that it is reported.  Any grid of 256-lane workgroups; the host stub
+// that a launch from another translation unit goes through is the one knn.hip's unit registers (one library, no relocatable device code).
+__global__ __launch_bounds__(256) void knn_bbox_kernel(const double* __restrict__ S, long long n, int dim, unsigned long long* mm /*[2][3]*/);
 
 struct KnnGrid {
     double lo[3], inv_cell[3], cell[3];

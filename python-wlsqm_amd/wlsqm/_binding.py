@@ -124,6 +124,14 @@ def lib():
     if hasattr(L, "wlsqm_hip_grid_shape_host"):                      # (older builds of the library, as above)
         L.wlsqm_hip_grid_shape_host.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.wlsqm_hip_grid_shape_host.restype = C.c_int
+    # the Morton order of a cloud and the renumbering of neighbour lists (csrc/order.hip)
+    L.wlsqm_hip_spatial_order_device.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                 C.c_void_p]
+    L.wlsqm_hip_spatial_keys_device.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.wlsqm_hip_relabel_hoods_device.argtypes = [C.c_int64, C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 3 \
+        + [C.c_int, C.c_void_p]
+    for name in ("spatial_order", "spatial_keys", "relabel_hoods"):
+        getattr(L, "wlsqm_hip_%s_device" % name).restype = C.c_int
     L.wlsqm_hip_expert_interpolate_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
                                                        C.c_void_p]
     L.wlsqm_hip_expert_interpolate_continuous.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_int,

@@ -20,7 +20,7 @@ __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_c
            "InterpolationPlan", "differentiable_evaluate",
            "StencilOperator", "stencil_rows", "differentiable_stencil_apply", "StencilSolver", "SolveInfo",
            "SolveGradients", "BlockJacobi", "ApproximateInverse", "differentiable_stencil_solve", "differentiable_stencil_solve_many",
-           "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
+           "SpatialOrder", "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
            "getrf_batched", "getrs_batched", "gesv_batched", "sytrf_batched", "sytrs_batched", "sysv_batched", "symmetrize_batched"]
 
 
@@ -365,7 +365,7 @@ def fit_cloud_device(dimension, order, S, F, hoods, fi, nk, knowns, weighting_me
     per case; fi (ncases, >= no) in/out.  Only the slots k < nk[j] of a hoods row are dereferenced (the padding of a ragged
     row may hold anything, e.g. -1 or npoints as scipy pads); those must be valid point numbers.  Asynchronous on `stream`
     unless want_iterations=True (returns the maximum refinement count; otherwise 0).  4 nk bytes of indices per fit instead of 8 nk (dim+1) bytes of gathered
-    coordinates; order the points along a space-filling curve (synth.morton_order) so that the gathers hit L2."""
+    coordinates; order the points along a space-filling curve (wlsqm.hip.SpatialOrder) so that the gathers hit L2."""
     a = _cloud_args(dimension, order, S, F, hoods, fi, nk, knowns, weighting_method, point_index)
     s, dev = _stream_and_device(fi, stream)
     ss = (int(sens.stride(0)), int(sens.stride(1))) if sens is not None else (0, 0)
@@ -1090,6 +1090,223 @@ def grid_shape(dimension, npoints, lo, hi):
     cell = np.ones(dimension, np.float64)
     B.check(B.lib().wlsqm_hip_grid_shape_host(dimension, int(npoints), lo.ctypes.data, hi.ctypes.data, g.ctypes.data, cell.ctypes.data))
     return g, cell
+
+
+# ---- the Morton order of a cloud, and everything renumbered with it (csrc/order.hip) ----
+
+def _cloud_dim(S):
+    """The dimension of a cloud S (npoints,) or (npoints, dim), checked as knn checks it."""
+    if not hasattr(S, "dim") or not hasattr(S, "is_cuda"):
+        raise ValueError("argument S must be a device (HIP) tensor")
+    if S.dim() == 1:
+        dim = 1
+    elif S.dim() == 2 and 1 <= S.shape[1] <= 3:
+        dim = int(S.shape[1])
+    else:
+        raise ValueError("S must be (npoints,) or (npoints, dim) with dim 1..3")
+    _check(S, "S", "float64", S.dim())
+    if not S.is_contiguous():
+        raise ValueError("S must be contiguous")
+    return dim
+
+
+class SpatialOrder:
+    """The Morton order of a device-resident cloud S (npoints, dim) [1D: (npoints,)], dim 1..3: what the
+    index-based fits, StencilOperator.apply, the Krylov kernels and a BlockJacobi want the points to be numbered by, for a cloud that
+    comes in any other order — with the renumbering of everything that names points.
+
+    2D / 3D: per axis q = min(floor(((x - lo) / (hi - lo)) * 2^B), 2^B - 1) with B = 31 / 21 bits (0 on an axis without extent), the
+    bits of the axes interleaved (axis 0 lowest) into a non-negative int64 key; 1D: the exact order of the doubles.  `perm` is the
+    stable ascending sort of the keys (ties go to the smaller old index): new position i holds old point perm[i], and
+    inverse[perm[i]] = i.  The order is monotone per axis and does not change when the cloud is scaled by a power of two;
+    tests/_order_ref.py states it in numpy and the device reproduces it bit for bit.
+
+    S in the domain of knn (a NaN or an infinity raises ValueError, as does a box whose squared diagonal overflows); npoints >= 1.
+    The constructor synchronises `stream` (after the bounding box, and again at its end: everything the order holds is complete when
+    it returns, so its methods may run on any stream) and keeps no reference to S.
+
+    npoints, dimension, bits (31, 21; 64 in 1D), lo, hi (host tuples: the bounding box); perm, inverse (int64 device tensors, for
+    torch indexing), keys (int64, ascending).
+
+    Reorder the CLOUD (order.cloud, order.take for the fields) before building what must follow a moving cloud: an operator from
+    order.operator has no geometry and no update()."""
+
+    def __init__(self, S, stream=None):
+        import torch
+        dim = _cloud_dim(S)
+        n = int(S.shape[0])
+        if n < 1:
+            raise ValueError("npoints must be >= 1")
+        self._perm32 = torch.empty((n,), dtype=torch.int32, device=S.device)
+        self._inverse32 = torch.empty((n,), dtype=torch.int32, device=S.device)
+        self.keys = torch.empty((n,), dtype=torch.int64, device=S.device)
+        box = (C.c_double * 6)()
+        s, dev = _stream_and_device(S, stream)
+        B.check(B.lib().wlsqm_hip_spatial_order_device(dim, n, _ptr(S), _ptr(self.keys), _ptr(self._perm32), _ptr(self._inverse32), box,
+                                                       dev, s))
+        with _torch_stream(stream, S.device):
+            self.perm, self.inverse = self._perm32.long(), self._inverse32.long()
+            # what the later calls read, on whatever stream they are given: made here, and complete when the constructor returns
+            self._bad = torch.zeros((1,), dtype=torch.int32, device=S.device)
+            self._minus = torch.full((n,), -1, dtype=torch.int32, device=S.device)
+            torch.cuda.current_stream(S.device).synchronize()
+        self.npoints, self.dimension, self.bits = n, dim, {1: 64, 2: 31, 3: 21}[dim]
+        self.lo, self.hi = tuple(box[m] for m in range(dim)), tuple(box[3 + m] for m in range(dim))
+        self._device = S.device
+
+    def __repr__(self):
+        return "SpatialOrder(npoints=%d, dimension=%d)" % (self.npoints, self.dimension)
+
+    def keys_of(self, X, out=None, stream=None):
+        """The keys (int64 device tensor, one per point) of other points X (n, dim) [1D: (n,)] under this order's box: where
+        torch.searchsorted(order.keys, ...) places them.  Points outside the box clamp to its ends; a NaN coordinate gives the
+        largest key.  Asynchronous; with `out` it allocates nothing and may be captured."""
+        import torch
+        if _cloud_dim(X) != self.dimension:
+            raise ValueError("X must have %d coordinates per point, as the cloud of the order" % self.dimension)
+        n = int(X.shape[0])
+        if out is None:
+            out = torch.empty((n,), dtype=torch.int64, device=X.device)
+        else:
+            _check(out, "out", "int64", 1)
+            if int(out.shape[0]) != n or not out.is_contiguous():
+                raise ValueError("out must be a contiguous int64 device tensor of shape (%d,)" % n)
+        _same_device(X, out)
+        lo, hi = (C.c_double * 3)(*self.lo), (C.c_double * 3)(*self.hi)
+        s, dev = _stream_and_device(X, stream)
+        B.check(B.lib().wlsqm_hip_spatial_keys_device(self.dimension, n, _ptr(X), lo, hi, _ptr(out), dev, s))
+        return out
+
+    def _along(self, t, dim, name):
+        if not hasattr(t, "dim") or not hasattr(t, "index_select"):
+            raise ValueError("argument %s must be a device (HIP) tensor" % name)
+        if t.dim() < 1 or not -t.dim() <= int(dim) < t.dim() or int(t.shape[dim]) != self.npoints:
+            raise ValueError("%s must have npoints = %d entries along dim %d; got shape %s" % (name, self.npoints, int(dim), tuple(t.shape)))
+        if t.device != self._device:
+            raise ValueError("all tensors must be on the same device")
+
+    def take(self, t, dim=0, out=None):
+        """t carried from the old order to the new one along `dim` (any dtype; npoints entries along dim): t.index_select(dim, perm)."""
+        import torch
+        self._along(t, dim, "t")
+        return torch.index_select(t, int(dim), self.perm) if out is None else torch.index_select(t, int(dim), self.perm, out=out)
+
+    def restore(self, t, dim=0, out=None):
+        """The way back: t.index_select(dim, inverse), so that restore(take(t)) is t bit for bit."""
+        import torch
+        self._along(t, dim, "t")
+        return torch.index_select(t, int(dim), self.inverse) if out is None else torch.index_select(t, int(dim), self.inverse, out=out)
+
+    def _relabel(self, lists, nk, row_perm, own, check, out, stream, name):
+        import torch
+        ncases, K = int(lists.shape[0]), int(lists.shape[1])
+        if nk is not None:
+            _check(nk, "nk", "int32", 1)
+            if nk.stride(0) != 1:
+                raise ValueError("nk, knowns, weighting_method must have unit stride")
+            _rows(ncases, nk=nk)
+        if out is None:
+            out = torch.empty((ncases, K), dtype=torch.int32, device=lists.device)
+        else:
+            _check(out, "out", "int32", 2)
+            if tuple(out.shape) != (ncases, K) or not out.is_contiguous():
+                raise ValueError("out must be a contiguous int32 device tensor of shape (%d, %d)" % (ncases, K))
+            if _overlap(out, lists):
+                raise ValueError("out must not overlap %s" % name)
+        _same_device(self.perm, lists, nk, out)
+        with _torch_stream(stream, self._device):
+            if check:
+                self._bad.zero_()
+            s, dev = _stream_and_device(lists, stream)
+            B.check(B.lib().wlsqm_hip_relabel_hoods_device(ncases, K, _ptr(lists), int(lists.stride(0)) if ncases > 1 else K, _ptr(nk),
+                                                           _ptr(row_perm), _ptr(self._inverse32), self.npoints, _ptr(own), _ptr(out),
+                                                           _ptr(self._bad) if check else None, dev, s))
+            if check and int(self._bad.item()):
+                raise ValueError("a live entry names a point outside 0 .. npoints - 1 = %d" % (self.npoints - 1))
+        return out
+
+    def hoods(self, hoods, nk=None, check=True, out=None, stream=None):
+        """Neighbour lists in which case j is centred on point j — hoods (npoints, K) int32 with a contiguous last axis, nk (npoints,)
+        int32 or None (every slot is live) — in the new order: out[i, k] = inverse[hoods[perm[i], k]] for k < nk[perm[i]], and the
+        padding holds the row's own new number i, as ball pads its rows.  One kernel ("order-relabel").  The counts go with
+        order.take(nk).  check=True reads one int back and raises ValueError when a live entry names no point; check=False reads
+        nothing (such an entry becomes -1) and, with `out`, may be captured."""
+        _check(hoods, "hoods", "int32", 2)
+        if hoods.stride(1) != 1:
+            raise ValueError("hoods must have a contiguous last axis")
+        if int(hoods.shape[0]) != self.npoints:
+            raise ValueError("hoods must have npoints = %d rows (case j centred on point j); got %d" % (self.npoints, int(hoods.shape[0])))
+        return self._relabel(hoods, nk, self._perm32, None, check, out, stream, "hoods")
+
+    def relabel(self, index, nk=None, check=True, out=None, stream=None):
+        """An int32 device tensor of point numbers, (n,) or (n, K) with a contiguous last axis — a point_index, the lists of a subset of
+        the cases — renumbered in place of its entries, rows unmoved: out = inverse[index].  With nk (n,) the slots k >= nk[j] of a 2D
+        tensor are padding and become -1.  check as for hoods(); an index of more than npoints rows with nk allocates its padding in
+        the call (every other form allocates nothing beside `out`)."""
+        import torch
+        if not hasattr(index, "dim") or index.dim() not in (1, 2):
+            raise ValueError("index must be (n,) or (n, K)")
+        _check(index, "index", "int32", index.dim())
+        if index.stride(-1) != 1 and int(index.shape[-1]) > 1:
+            raise ValueError("index must have a contiguous last axis")
+        if index.dim() == 1:
+            if nk is not None:
+                raise ValueError("nk goes with a 2D index")
+            if out is not None:
+                _check(out, "out", "int32", 1)
+                if tuple(out.shape) != tuple(index.shape) or not out.is_contiguous():
+                    raise ValueError("out must be a contiguous int32 device tensor of shape (%d,)" % int(index.shape[0]))
+            r = self._relabel(index.view(-1, 1), None, None, None, check, out.view(-1, 1) if out is not None else None, stream, "index")
+            return out if out is not None else r.view(-1)
+        own = None
+        if nk is not None:
+            own = self._minus
+            if int(own.shape[0]) < int(index.shape[0]):                  # more rows than the cloud has points: the padding of this call
+                with _torch_stream(stream, self._device):
+                    own = torch.full((int(index.shape[0]),), -1, dtype=torch.int32, device=self._device)
+        return self._relabel(index, nk, None, own, check, out, stream, "index")
+
+    def cloud(self, S, hoods, nk, knowns, weighting_method, stream=None):
+        """(S, hoods, nk, knowns, weighting_method) of an index-based cloud without point_index, all in the new order: what
+        fit_cloud_device, StencilOperator and knn-built lists take.  take four times and hoods once."""
+        with _torch_stream(stream, self._device):
+            return (self.take(S).contiguous(), self.hoods(hoods, nk, stream=stream), self.take(nk), self.take(knowns),
+                    self.take(weighting_method))
+
+    def operator(self, op, stream=None):
+        """P A P^T of a square StencilOperator whose row j names point j (ncases == npoints == order.npoints, no point_index;
+        anything else raises ValueError), for every value plane: a new operator whose row i is the old row perm[i] with its columns
+        renumbered.  The order of the entries inside a row is kept, so a row's sum has the same bits: op2.apply(order.take(F))
+        restored is op.apply(F) bit for bit.  Built through op.coefficients(), the renumbered lists and
+        StencilOperator.from_coefficients.  The transposed product sums a column's entries in case order, which the renumbering changes:
+        op2.apply_transpose agrees with op's within the rounding of a sum in another order, not bit for bit.  An operator of a fit keeps
+        its dimension, order and known_coef (rows carried to the new order), so op2.apply(order.take(F), known=order.take(known)) serves
+        known derivatives as op.apply(F, known=known) does, bit for bit.  The result has no geometry and so no update(): reorder the
+        cloud with order.cloud before building an operator that must follow a moving cloud."""
+        import torch
+        if not isinstance(op, StencilOperator):
+            raise ValueError("op must be a StencilOperator")
+        op._live()
+        if op._point_index is not None or op.ncases != op.npoints or op.npoints != self.npoints:
+            raise ValueError("order.operator takes a square operator whose row j names point j, of npoints = %d; got ncases = %d, "
+                             "npoints = %d%s" % (self.npoints, op.ncases, op.npoints, ", with a point_index" if op._point_index is not None else ""))
+        _same_device(self.perm, op._val)
+        with _torch_stream(stream, self._device):
+            slots, own = op.coefficients()
+            live, dest, _ = op._slot_positions()
+            lists = torch.zeros((op.ncases, op.K), dtype=torch.int32, device=self._device)
+            lists[live] = op._m["col"][dest]
+            nk = op._nk.to(torch.int32)
+            mask = op._own_mask
+            new = StencilOperator.from_coefficients(self.hoods(lists, nk, stream=stream), self.take(nk), self.take(slots, dim=1), op.npoints,
+                                                    own=self.take(own, dim=1) if mask is not None else None,
+                                                    own_mask=self.take(mask) if mask is not None else None, stream=stream)
+            if op.known_coef is not None:
+                # (ncases, no) per operator: what apply(known=) contracts with the known values of every case
+                new.known_coef = self.take(op.known_coef, dim=1)
+                new.has_known_derivatives = op.has_known_derivatives
+            new.dimension, new.order, new.no = op.dimension, op.order, op.no
+        return new
 
 
 # ---- interpolation plans: search once, evaluate many times (csrc/interp_plan.hip) ----
@@ -1993,7 +2210,7 @@ always ends in 1).  With method="bicgstab2", 2 is rho0 = 0, (rt, u1) = 0 or (rt,
 class BlockJacobi:
     """The block-Jacobi preconditioner of a StencilSolver: P = blockdiag(M_BB)^-1, the exact inverses of the
     diagonal blocks of `block` consecutive rows (8, 16 or 32), the last block cut at npoints.  It pays where consecutive rows are
-    neighbours in space — a cloud in Morton order (synth.morton_order), as every large workload of this project is; on a cloud in
+    neighbours in space — a cloud in Morton order (wlsqm.hip.SpatialOrder), as every large workload of this project is; on a cloud in
     random order the blocks hold next to nothing off their diagonals and it does no better than "jacobi".
     refresh=True: P is recomputed from the operator's arrays at the start of every solve / enqueue, as the Jacobi diagonal is.
     refresh=False: P is computed at the first start and again only by solver.refresh() — for time loops on a fixed operator."""
@@ -2034,7 +2251,8 @@ class StencilSolver:
     at every solve: after op.update(...) it solves with the new values, and nothing has to be called on the solver.
     diag: a float, or a contiguous float64 device tensor (npoints,) that is read at every solve (the caller may change it in place).
     preconditioner: "jacobi" (the inverse of M's diagonal, recomputed at the start of every solve), None, or a BlockJacobi (the
-    inverses of the diagonal blocks of 8, 16 or 32 consecutive rows: for large steps on a cloud in Morton order).
+    inverses of the diagonal blocks of 8, 16 or 32 consecutive rows: for large steps on a cloud in Morton order, which
+    wlsqm.hip.SpatialOrder produces for a cloud, its lists or a finished operator).
     All workspace, 9 npoints + 2 ceil(npoints / 256) + 16 doubles, is allocated here; close() releases it.  A BlockJacobi adds its
     plane, 64 block ceil(npoints / 64) + ceil(npoints / 256) doubles, and a second one for M^T at the first transposed use
     (prepare_transpose).
