@@ -787,6 +787,35 @@ int wlsqm_hip_krylov_spai_iterate_device(int64_t nrows, int64_t nslices, const i
                                          const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
                                          int l2, const void* planes, double* x, int64_t niter, void* workspace, int device, void* stream);
 
+/* ---- coupled fields: implicit solves with m unknowns per point (extension; csrc/krylov.hip) ----
+ * BiCGSTAB on M x = b with block (a, b) of M = D_ab + sum_o coupling[a][b][o] * A_o, 1 <= m <= 4 unknowns per point, A_o the nop <= 8
+ * value planes of a SQUARE matrix in the SELL-64 layout above (`val` points at plane 0, plane o at val + o * total).  coupling: HOST
+ * array of m * m * nop doubles, [(a * m + b) * nop + o]; it travels to the kernels as an argument.  D_ab is a diagonal matrix:
+ * diag != NULL: a device array (m, m, npoints), D_ab,i = diag[(a * m + b) * npoints + i]; else diag_const, a HOST array of m * m constants.
+ * The unknowns, b and every product are interleaved: x[i * m + a] is component a at point i, so that a neighbour's unknowns are 8 m
+ * contiguous bytes; for m = 2 and 4 they are moved by 16-byte loads, and b, x, in, w, out and the workspace must be 16-byte aligned
+ * (WLSQM_EVALUE otherwise).  The product's order of operations is stated at the head of that part of csrc/krylov.hip.
+ * jacobi != 0: right-preconditioned with the inverse of M's scalar diagonal, D_aa,i + sum_o coupling[a][a][o] * (the sum of row i's entries
+ * in column i of plane o, in entry order), recomputed by every start.
+ * The workspace, the scalars at its head, the statuses, the early exit on `done` and the fixed order of every sum are those of
+ * wlsqm_hip_krylov_start_device at nrows = m * npoints: wlsqm_hip_krylov_system_workspace_bytes(npoints, m) is
+ * wlsqm_hip_krylov_workspace_bytes(m * npoints) (-1 for m outside 1 .. 4).  Kernel launches only ("krylov-system-diag",
+ * "krylov-system-spmv", "krylov-update", "krylov-reduce"): 4 for a start, 8 per iteration, 2 for a product.  WLSQM_EVALUE as there, and
+ * for m outside 1 .. 4 or nop outside 1 .. 8. */
+int64_t wlsqm_hip_krylov_system_workspace_bytes(int64_t npoints, int m);
+int wlsqm_hip_krylov_system_start_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                         const int32_t* col, const double* val, int64_t total, int nop, int m, const double* coupling,
+                                         const double* diag, const double* diag_const, int jacobi, const double* b, const double* x,
+                                         double rtol, double atol, int64_t maxiter, void* workspace, int device, void* stream);
+int wlsqm_hip_krylov_system_bicgstab_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                            const int32_t* col, const double* val, int64_t total, int nop, int m, const double* coupling,
+                                            const double* diag, const double* diag_const, int jacobi, double* x, int64_t niter,
+                                            void* workspace, int device, void* stream);
+int wlsqm_hip_krylov_system_product_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                           const int32_t* col, const double* val, int64_t total, int nop, int m, const double* coupling,
+                                           const double* diag, const double* diag_const, const double* in, const double* w, double* out,
+                                           void* workspace, int device, void* stream);
+
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ---- */
 /* Runs `reps` back-to-back launches of the fit kernel for batch `b` (device-resident, uniform
  * order) on `stream`, bracketed by HIP events on that stream; returns the mean kernel time in

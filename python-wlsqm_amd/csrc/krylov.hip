@@ -1644,6 +1644,289 @@ static int krylov_tolerances(const char* who, const void* b, const void* x, doub
     return WLSQM_OK;
 }
 
+// ---- coupled fields: m unknowns per point, block (a, b) of M = D_ab + sum_o coupling[a][b][o] A_o ------------------
+// The unknowns are interleaved, x[point * m + a], so that a neighbour's m values are one contiguous load of 8 m bytes (16-byte loads
+// for m = 2 and 4, which the entry points check the alignment for).  One wave per slice, one lane per point, m accumulators per lane.
+// The order of operations, which tests/_krylov_system_ref.py states in numpy: per stored entry, in entry order,
+//   t_ab  = coupling[a][b][0] * val_0, then t_ab = fma(coupling[a][b][o], val_o, t_ab) for o = 1 .. nop - 1
+//   acc_a = fma(t_ab, x_b, acc_a) for b = 0 .. m - 1
+// and at the end of the row  y_a = acc_a + s_a,  s_a = D_a0 x_0, then s_a = fma(D_ab, x_b, s_a) for b = 1 .. m - 1, x the point's own.
+// The lane's terms of a dot product are added for a = 0 .. m - 1 in turn and then go through block_sums' tree.  The vectors of the
+// recurrence are KrylovWork's at nrows = m npoints, and the update and reduce kernels above serve them unchanged: the product's
+// launches write ceil(npoints / 256) partials per plane, the updates' ceil(m npoints / 256), and each reduce is handed the count of
+// the launch that wrote.
+
+constexpr int KRYLOV_SYSTEM_FIELDS = 4;     // m <= 4
+constexpr int KRYLOV_SYSTEM_PLANES = 8;     // nop <= 8: the coupling table is at most 4 * 4 * 8 = 128 doubles
+
+struct KrylovCoupled {
+    long long npoints, total;
+    const int32_t* len; const int32_t* width; const long long* soff;
+    const int32_t* col; const double* val;                      // plane o at val + o * total
+    const double* dten;                                          // D_ab,i = dten ? dten[(a * m + b) * npoints + i] : dconst[a * m + b]
+    double dconst[KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS];
+    double coupling[KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_PLANES];   // [(a * m + b) * nop + o]
+};
+
+// The m unknowns of one point of an interleaved vector.
+template <int M>
+__device__ __forceinline__ void krylov_load_point(const double* at, double (&f)[M]) {
+    if constexpr (M % 2 == 0) {
+        krylov_load_fields<M>(at, f);
+    } else {
+#pragma unroll
+        for (int b = 0; b < M; ++b) f[b] = at[b];
+    }
+}
+
+// One stored entry: its nop values vs and the neighbour's unknowns xs into the lane's m sums.
+template <int M, int NOP>
+__device__ __forceinline__ void krylov_system_entry(const KrylovCoupled& q, const double (&vs)[NOP], const double (&xs)[M], double (&acc)[M]) {
+#pragma unroll
+    for (int a = 0; a < M; ++a) {
+#pragma unroll
+        for (int b = 0; b < M; ++b) {
+            double t = q.coupling[(a * M + b) * NOP] * vs[0];
+#pragma unroll
+            for (int o = 1; o < NOP; ++o) t = __builtin_fma(q.coupling[(a * M + b) * NOP + o], vs[o], t);
+            acc[a] = __builtin_fma(t, xs[b], acc[a]);
+        }
+    }
+}
+
+template <int M, int NOP>
+__device__ __forceinline__ void krylov_system_row_sums(const KrylovCoupled& q, long long at, const double* x, int wid, int n, double (&acc)[M]) {
+    constexpr int UNROLL = 4;
+    const int32_t* col = q.col + at;
+    const double* val = q.val + at;
+#pragma unroll
+    for (int a = 0; a < M; ++a) acc[a] = 0.0;
+    for (int e = 0; e < wid; e += UNROLL) {                      // wave-uniform
+        if (e + UNROLL <= n) {
+            double xs[UNROLL][M], vs[UNROLL][NOP];
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) {
+                const long long c = col[64LL * (e + u)];
+                krylov_load_point<M>(x + c * M, xs[u]);
+#pragma unroll
+                for (int o = 0; o < NOP; ++o) vs[u][o] = val[o * q.total + 64LL * (e + u)];
+            }
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) krylov_system_entry<M, NOP>(q, vs[u], xs[u], acc);
+        } else {
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) {
+                if (e + u < n) {
+                    const long long c = col[64LL * (e + u)];
+                    double xs[M], vs[NOP];
+                    krylov_load_point<M>(x + c * M, xs);
+#pragma unroll
+                    for (int o = 0; o < NOP; ++o) vs[o] = val[o * q.total + 64LL * (e + u)];
+                    krylov_system_entry<M, NOP>(q, vs, xs, acc);
+                }
+            }
+        }
+    }
+}
+
+enum { SYSTEM_RESIDUAL = 0, SYSTEM_V = 1, SYSTEM_T = 2, SYSTEM_PRODUCT = 3 };
+
+// y = M in.  `mode` is uniform over the grid:
+//   RESIDUAL: out = out2 = b - y (w is b), partials (out, out) and (b, b)
+//   V:        out = y, partial (w, out)                  (the second plane is written and not read)
+//   T:        out = y, partials (out, w) and (out, out)
+//   PRODUCT:  T whatever the state of a solve
+template <int M, int NOP>
+__global__ void __launch_bounds__(256) krylov_system_spmv_kernel(const KrylovCoupled q, int mode, const double* in, const double* w, double* out,
+                                                                 double* out2, double* partial, const KrylovScalars* sc) {
+    if (mode != SYSTEM_PRODUCT && sc->done) return;              // uniform: the whole grid
+    const int lane = threadIdx.x & 63;
+    const long long s = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long row = s * 64 + lane;
+    double pa = 0.0, pb = 0.0;
+    if (s * 64 < q.npoints) {                                    // wave-uniform
+        const int wid = __builtin_amdgcn_readfirstlane(q.width[s]);
+        const long long at = q.soff[s] + lane;
+        int n = row < q.npoints ? q.len[row] : 0;
+        n = n < wid ? n : wid;
+        double acc[M];
+        krylov_system_row_sums<M, NOP>(q, at, in, wid, n, acc);
+        if (row < q.npoints) {
+            double xi[M], y[M], wi[M];
+            krylov_load_point<M>(in + row * M, xi);
+            krylov_load_point<M>(w + row * M, wi);
+#pragma unroll
+            for (int a = 0; a < M; ++a) {
+                double sa = 0.0;
+#pragma unroll
+                for (int b = 0; b < M; ++b) {
+                    const double d = q.dten ? q.dten[(a * M + b) * q.npoints + row] : q.dconst[a * M + b];
+                    sa = b == 0 ? d * xi[0] : __builtin_fma(d, xi[b], sa);
+                }
+                y[a] = acc[a] + sa;
+            }
+            if (mode == SYSTEM_RESIDUAL) {
+#pragma unroll
+                for (int a = 0; a < M; ++a) {
+                    const double r = wi[a] - y[a];
+                    out[row * M + a] = r; out2[row * M + a] = r;
+                    pa += r * r; pb += wi[a] * wi[a];
+                }
+            } else {
+#pragma unroll
+                for (int a = 0; a < M; ++a) {
+                    out[row * M + a] = y[a];
+                    pa += wi[a] * y[a]; pb += y[a] * y[a];
+                }
+            }
+        }
+    }
+    block_sums<true>(pa, pb, partial, gridDim.x);
+}
+
+// dinv[i * m + a] = 1 / (D_aa,i + sum_o coupling[a][a][o] own_o), own_o the sum of row i's entries in column i of plane o in entry order
+// (plain sums, two roundings per term, o ascending from coupling[a][a][0] * own_0); the partial counts the points with an unusable entry.
+template <int M, int NOP>
+__global__ void __launch_bounds__(256) krylov_system_diag_kernel(const KrylovCoupled q, double* dinv, double* partial) {
+    const int lane = threadIdx.x & 63;
+    const long long s = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long row = s * 64 + lane;
+    double bad = 0.0;
+    if (s * 64 < q.npoints) {                                    // wave-uniform
+        const int wid = __builtin_amdgcn_readfirstlane(q.width[s]);
+        const long long at = q.soff[s] + lane;
+        int n = row < q.npoints ? q.len[row] : 0;
+        n = n < wid ? n : wid;
+        double own[NOP];
+#pragma unroll
+        for (int o = 0; o < NOP; ++o) own[o] = 0.0;
+        for (int e = 0; e < wid; ++e) {                          // wave-uniform
+            if (e < n && q.col[at + 64LL * e] == row) {
+#pragma unroll
+                for (int o = 0; o < NOP; ++o) own[o] += q.val[o * q.total + at + 64LL * e];
+            }
+        }
+        if (row < q.npoints) {
+            bool unusable = false;
+#pragma unroll
+            for (int a = 0; a < M; ++a) {
+                double t = q.coupling[(a * M + a) * NOP] * own[0];
+#pragma unroll
+                for (int o = 1; o < NOP; ++o) t = t + q.coupling[(a * M + a) * NOP + o] * own[o];
+                const double diag = (q.dten ? q.dten[(a * M + a) * q.npoints + row] : q.dconst[a * M + a]) + t;
+                const bool ok = diag != 0.0 && __builtin_isfinite(diag);
+                dinv[row * M + a] = ok ? 1.0 / diag : 0.0;
+                unusable = unusable || !ok;
+            }
+            bad = unusable ? 1.0 : 0.0;
+        }
+    }
+    block_sums<false>(bad, 0.0, partial, gridDim.x);
+}
+
+enum { SYSTEM_CALL_START = 0, SYSTEM_CALL_ITERATE = 1, SYSTEM_CALL_PRODUCT = 2 };
+
+struct KrylovSystemCall {
+    int what, jacobi, maxiter;
+    KrylovCoupled q;
+    KrylovWork w;                                               // at nrows = m npoints
+    const double *in, *other;                                   // start: x and b; product: in and w
+    double* x;                                                  // iterate: x; product: out
+    double rtol, atol;
+    int64_t niter;
+    hipStream_t s;
+};
+
+template <int M, int NOP>
+static void krylov_system_run(const KrylovSystemCall& c) {
+    const KrylovWork& w = c.w;
+    const long long nwgp = (c.q.npoints + 255) / 256, nrows = c.q.npoints * M;
+    const dim3 pgrid((unsigned)nwgp), ugrid((unsigned)w.nwg), block(256);
+    const KrylovScalars* sc = w.sc;
+    hipStream_t s = c.s;
+    double* const none = nullptr;
+    if (c.what == SYSTEM_CALL_START) {
+        if (c.jacobi) {
+            hipLaunchKernelGGL((krylov_system_diag_kernel<M, NOP>), pgrid, block, 0, s, c.q, w.dinv, w.partial);
+            note_kernel("krylov-system-diag");
+        }
+        krylov_reduce(REDUCE_DIAG, w, c.jacobi ? nwgp : 0, 1, c.rtol, c.atol, c.maxiter, s);
+        hipLaunchKernelGGL((krylov_system_spmv_kernel<M, NOP>), pgrid, block, 0, s, c.q, (int)SYSTEM_RESIDUAL, c.in, c.other, w.r, w.r0, w.partial, sc);
+        note_kernel("krylov-system-spmv");
+        krylov_reduce(REDUCE_RESIDUAL, w, nwgp, 2, c.rtol, c.atol, c.maxiter, s);
+        note_kernel("krylov-reduce");
+    } else if (c.what == SYSTEM_CALL_ITERATE) {
+        for (int64_t it = 0; it < c.niter; ++it) {
+            hipLaunchKernelGGL((krylov_update_kernel<UPDATE_P>), ugrid, block, 0, s, nrows, w, c.x, sc);
+            hipLaunchKernelGGL((krylov_system_spmv_kernel<M, NOP>), pgrid, block, 0, s, c.q, (int)SYSTEM_V, (const double*)w.phat, (const double*)w.r0, w.v, none, w.partial, sc);
+            krylov_reduce(REDUCE_ALPHA, w, nwgp, 1, 0.0, 0.0, 0, s);
+            hipLaunchKernelGGL((krylov_update_kernel<UPDATE_S>), ugrid, block, 0, s, nrows, w, c.x, sc);
+            hipLaunchKernelGGL((krylov_system_spmv_kernel<M, NOP>), pgrid, block, 0, s, c.q, (int)SYSTEM_T, (const double*)w.shat, (const double*)w.s, w.t, none, w.partial, sc);
+            krylov_reduce(REDUCE_OMEGA, w, nwgp, 2, 0.0, 0.0, 0, s);
+            hipLaunchKernelGGL((krylov_update_kernel<UPDATE_X>), ugrid, block, 0, s, nrows, w, c.x, sc);
+            krylov_reduce(REDUCE_RHO, w, w.nwg, 2, 0.0, 0.0, 0, s);
+        }
+        note_kernel("krylov-update");
+    } else {
+        hipLaunchKernelGGL((krylov_system_spmv_kernel<M, NOP>), pgrid, block, 0, s, c.q, (int)SYSTEM_PRODUCT, c.in, c.other, c.x, none, w.partial, sc);
+        krylov_reduce(REDUCE_PRODUCT, w, nwgp, 2, 0.0, 0.0, 0, s);
+        note_kernel("krylov-system-spmv");
+    }
+}
+
+template <int M>
+static void krylov_system_planes(int nop, const KrylovSystemCall& c) {
+    switch (nop) {
+    case 1: krylov_system_run<M, 1>(c); break;
+    case 2: krylov_system_run<M, 2>(c); break;
+    case 3: krylov_system_run<M, 3>(c); break;
+    case 4: krylov_system_run<M, 4>(c); break;
+    case 5: krylov_system_run<M, 5>(c); break;
+    case 6: krylov_system_run<M, 6>(c); break;
+    case 7: krylov_system_run<M, 7>(c); break;
+    default: krylov_system_run<M, 8>(c); break;
+    }
+}
+
+// The checks and the kernel argument that the three entry points share, then the call's launches.
+static int krylov_system_call(const char* who, KrylovSystemCall& c, int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                              const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                              const double* coupling, const double* diag, const double* diag_const, void* workspace, int device) {
+    const std::string name(who);
+    if (m < 1 || m > KRYLOV_SYSTEM_FIELDS) { set_error(name + ": m must be 1 .. 4"); return WLSQM_EVALUE; }
+    if (nop < 1 || nop > KRYLOV_SYSTEM_PLANES) { set_error(name + ": nop must be 1 .. 8"); return WLSQM_EVALUE; }
+    if (npoints < 1 || nslices < 0 || npoints > 64 * nslices || total < 0 || (npoints * m + 255) / 256 > 0x7fffffffLL) {
+        set_error(name + ": npoints must be 1 .. 64 * nslices");
+        return WLSQM_EVALUE;
+    }
+    if (!len || !width || !soff || !col || !val || !coupling || !workspace || (!diag && !diag_const) || !c.in || !c.other || !c.x) {
+        set_error(name + ": null array");
+        return WLSQM_EVALUE;
+    }
+    if (m % 2 == 0 && (((uintptr_t)c.in | (uintptr_t)c.other | (uintptr_t)c.x | (uintptr_t)workspace) & 15)) {
+        set_error(name + ": with m = 2 or 4 the vectors and the workspace must be 16-byte aligned");
+        return WLSQM_EVALUE;
+    }
+    KrylovCoupled& q = c.q;
+    q.npoints = npoints; q.total = total;
+    q.len = len; q.width = width; q.soff = reinterpret_cast<const long long*>(soff);
+    q.col = col; q.val = val; q.dten = diag;
+    for (int i = 0; i < KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS; ++i) q.dconst[i] = (!diag && i < m * m) ? diag_const[i] : 0.0;
+    for (int i = 0; i < KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_PLANES; ++i) q.coupling[i] = i < m * m * nop ? coupling[i] : 0.0;
+    DeviceScope scope;
+    const int rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    c.w = krylov_work(workspace, npoints * m, c.jacobi != 0);
+    switch (m) {
+    case 1: krylov_system_planes<1>(nop, c); break;
+    case 2: krylov_system_planes<2>(nop, c); break;
+    case 3: krylov_system_planes<3>(nop, c); break;
+    default: krylov_system_planes<4>(nop, c); break;
+    }
+    WLSQM_HIP_CHECK(hipGetLastError());
+    return WLSQM_OK;
+}
+
 }  // namespace wlsqm
 
 using namespace wlsqm;
@@ -2164,6 +2447,50 @@ int wlsqm_hip_krylov_spai_iterate_device(int64_t nrows, int64_t nslices, const i
     WLSQM_HIP_CHECK(hipGetLastError());
     note_kernel(l2 ? "krylov-spai-l2-update" : "krylov-spai-update");
     return WLSQM_OK;
+}
+
+int64_t wlsqm_hip_krylov_system_workspace_bytes(int64_t npoints, int m) {
+    if (npoints < 0 || m < 1 || m > KRYLOV_SYSTEM_FIELDS) return -1;
+    return wlsqm_hip_krylov_workspace_bytes(npoints * m);
+}
+
+int wlsqm_hip_krylov_system_start_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                         const int32_t* col, const double* val, int64_t total, int nop, int m, const double* coupling,
+                                         const double* diag, const double* diag_const, int jacobi, const double* b, const double* x,
+                                         double rtol, double atol, int64_t maxiter, void* workspace, int device, void* stream) {
+    int rc = krylov_tolerances("krylov_system_start", b, x, rtol, atol, maxiter);
+    if (rc != WLSQM_OK) return rc;
+    KrylovSystemCall c;
+    c.what = SYSTEM_CALL_START; c.jacobi = jacobi; c.maxiter = (int)maxiter;
+    c.in = x; c.other = b; c.x = const_cast<double*>(x);        // the start reads x
+    c.rtol = rtol; c.atol = atol; c.niter = 0; c.s = (hipStream_t)stream;
+    return krylov_system_call("krylov_system_start", c, npoints, nslices, len, width, soff, col, val, total, nop, m, coupling, diag,
+                              diag_const, workspace, device);
+}
+
+int wlsqm_hip_krylov_system_bicgstab_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                            const int32_t* col, const double* val, int64_t total, int nop, int m, const double* coupling,
+                                            const double* diag, const double* diag_const, int jacobi, double* x, int64_t niter,
+                                            void* workspace, int device, void* stream) {
+    if (niter < 0) { set_error("krylov_system_bicgstab: niter must be >= 0"); return WLSQM_EVALUE; }
+    KrylovSystemCall c;
+    c.what = SYSTEM_CALL_ITERATE; c.jacobi = jacobi; c.maxiter = 0;
+    c.in = x; c.other = x; c.x = x;
+    c.rtol = c.atol = 0.0; c.niter = niter; c.s = (hipStream_t)stream;
+    return krylov_system_call("krylov_system_bicgstab", c, npoints, nslices, len, width, soff, col, val, total, nop, m, coupling, diag,
+                              diag_const, workspace, device);
+}
+
+int wlsqm_hip_krylov_system_product_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                           const int32_t* col, const double* val, int64_t total, int nop, int m, const double* coupling,
+                                           const double* diag, const double* diag_const, const double* in, const double* w, double* out,
+                                           void* workspace, int device, void* stream) {
+    KrylovSystemCall c;
+    c.what = SYSTEM_CALL_PRODUCT; c.jacobi = 0; c.maxiter = 0;
+    c.in = in; c.other = w; c.x = out;
+    c.rtol = c.atol = 0.0; c.niter = 0; c.s = (hipStream_t)stream;
+    return krylov_system_call("krylov_system_product", c, npoints, nslices, len, width, soff, col, val, total, nop, m, coupling, diag,
+                              diag_const, workspace, device);
 }
 
 }  // extern "C"

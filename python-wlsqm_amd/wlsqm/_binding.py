@@ -263,6 +263,18 @@ def lib():
         L.wlsqm_hip_krylov_spai_iterate_device.argtypes = system + [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
         for name in ("build", "apply", "start", "iterate"):
             getattr(L, "wlsqm_hip_krylov_spai_%s_device" % name).restype = C.c_int
+    # coupled fields on one cloud (wlsqm.hip.StencilSystemSolver)
+    if hasattr(L, "wlsqm_hip_krylov_system_start_device"):
+        # the SELL-64 arrays, total, nop, m, coupling (host), diag (device), diag_const (host)
+        coupled = [C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 3
+        L.wlsqm_hip_krylov_system_workspace_bytes.argtypes = [C.c_int64, C.c_int]
+        L.wlsqm_hip_krylov_system_workspace_bytes.restype = C.c_int64
+        L.wlsqm_hip_krylov_system_start_device.argtypes = coupled + [C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int64,
+                                                                    C.c_void_p, C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_system_bicgstab_device.argtypes = coupled + [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_system_product_device.argtypes = coupled + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        for name in ("start", "bicgstab", "product"):
+            getattr(L, "wlsqm_hip_krylov_system_%s_device" % name).restype = C.c_int
     # batched dense solves (wlsqm.utils.lapackdrivers, wlsqm.hip.*_batched)
     for op in ("getrf", "gesv", "sytrf", "sysv"):
         solve = op in ("gesv", "sysv")

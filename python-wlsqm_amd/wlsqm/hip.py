@@ -18,7 +18,7 @@ __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_c
            "fit_cloud_geometry_adjoint_device", "differentiable_fit_many", "differentiable_fit_cloud",
            "differentiable_solve", "differentiable_solve_many",
            "InterpolationPlan", "differentiable_evaluate",
-           "StencilOperator", "stencil_rows", "differentiable_stencil_apply", "StencilSolver", "SolveInfo",
+           "StencilOperator", "stencil_rows", "differentiable_stencil_apply", "StencilSolver", "StencilSystemSolver", "SolveInfo",
            "SolveGradients", "BlockJacobi", "ApproximateInverse", "differentiable_stencil_solve", "differentiable_stencil_solve_many",
            "SpatialOrder", "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
            "getrf_batched", "getrs_batched", "gesv_batched", "sytrf_batched", "sytrs_batched", "sysv_batched", "symmetrize_batched"]
@@ -2879,6 +2879,252 @@ class StencilSolver:
             with _torch_stream(stream, self._device):
                 gscale.view(-1).copy_(self._ws[6:7])
         return SolveGradients(gval, gdiag, gscale)
+
+
+class StencilSystemSolver:
+    """Solves M x = b for m coupled fields on one cloud (1 <= m <= 4): block (a, b) of M is
+    D_ab + sum_o coupling[a, b, o] A_o, A_o the value planes of a square StencilOperator, by the device-resident BiCGSTAB of
+    StencilSolver: eight launches per iteration, the product one pass over the operator's own planes (4 + 8 nop bytes per neighbour,
+    whatever m is) that gathers a neighbour's m unknowns as one contiguous load.  No atomics: the bits of x and of the iteration count
+    are a function of the inputs, and eager and captured runs agree.
+
+    op: as StencilSolver takes it — square, row j the equation of point j, not closed, without known derivatives — with at most 8 planes.
+    coupling: host array-like of float64 (m, m, nop), every entry finite; read here, once.
+    diag: a float d (D = d I_m), a host (m, m) array-like of constants, or a contiguous float64 device tensor (m, m, npoints), each
+    D_ab a diagonal matrix; a tensor is read at every solve (the caller may change it in place).
+    preconditioner: "jacobi", the inverse of the scalar diagonal of M — for unknown (i, a): D_aa,i + sum_o coupling[a, a, o] (the sum of
+    row i's own entries in plane o) — or None.  Nothing else: blocks over points are the follow-up that section 24 argues for.
+
+    Unknowns and right-hand sides are contiguous float64 device tensors (npoints, m): x[i, a] is component a at point i.  For m = 2 and 4
+    they are moved by 16-byte loads and must be 16-byte aligned, as every tensor that torch allocates is.
+    The workspace is StencilSolver's at m npoints rows, 9 m npoints + 2 ceil(m npoints / 256) + 16 doubles, allocated here.
+    Out of scope (section 24): method="bicgstab2", BlockJacobi and ApproximateInverse, transposed solves and autograd, nfields, a
+    per-point coupling, m > 4, wlsqm.sharded."""
+
+    def __init__(self, op, coupling, diag=0.0, preconditioner="jacobi"):
+        import numpy as np
+        import torch
+        self._ws = None
+        if not isinstance(op, StencilOperator):
+            raise ValueError("op must be a StencilOperator")
+        op._live()
+        if op.ncases != op.npoints:
+            raise ValueError("the operator must be square: it has %d rows (cases) for %d points" % (op.ncases, op.npoints))
+        if op.has_known_derivatives:
+            raise ValueError("the operator depends on known DOFs other than F: their affine term belongs in b, build the operator without them")
+        if preconditioner is not None and not (isinstance(preconditioner, str) and preconditioner == "jacobi"):
+            raise ValueError("preconditioner must be 'jacobi' or None for coupled fields; got %r" % (preconditioner,))
+        self._jacobi = 1 if preconditioner == "jacobi" else 0
+        if hasattr(coupling, "is_cuda") and coupling.is_cuda:
+            raise ValueError("coupling must be a host array (m, m, nop); got a device tensor")
+        cp = np.ascontiguousarray(np.asarray(coupling, dtype=np.float64))
+        if cp.ndim != 3 or cp.shape[0] != cp.shape[1] or not 1 <= cp.shape[0] <= 4 or cp.shape[2] != op.nop:
+            raise ValueError("coupling must have shape (m, m, nop) with 1 <= m <= 4 and nop = %d, the operator's value planes; got shape %s"
+                             % (op.nop, tuple(cp.shape)))
+        if op.nop > 8:
+            raise ValueError("coupled fields take an operator of at most 8 value planes; it has %d" % op.nop)
+        if not np.isfinite(cp).all():
+            raise ValueError("every entry of coupling must be finite")
+        m = int(cp.shape[0])
+        self.m, self.nop, self.npoints, self._device = m, op.nop, op.npoints, op._device
+        self.coupling = cp
+        if hasattr(diag, "dim"):
+            if not hasattr(diag, "is_cuda"):
+                raise ValueError("argument diag must be a device (HIP) tensor")
+            _check(diag, "diag", "float64", 3)
+            if tuple(diag.shape) != (m, m, self.npoints) or not diag.is_contiguous():
+                raise ValueError("diag must be a contiguous float64 device tensor of shape (%d, %d, %d); got shape %s with strides %s"
+                                 % (m, m, self.npoints, tuple(diag.shape), tuple(diag.stride())))
+            _same_device(op._m["col"], diag)
+            self.diag, dc = diag, np.zeros((m, m))
+        else:
+            dc = np.asarray(diag, dtype=np.float64)
+            if dc.ndim == 0:
+                dc = float(dc) * np.eye(m)
+            if dc.shape != (m, m):
+                raise ValueError("diag must be a float, a host array (%d, %d) or a device tensor (%d, %d, %d); got shape %s"
+                                 % (m, m, m, m, self.npoints, tuple(dc.shape)))
+            if not np.isfinite(dc).all():
+                raise ValueError("every entry of diag must be finite")
+            self.diag = dc = np.ascontiguousarray(dc)
+        self._cp = (C.c_double * cp.size)(*cp.ravel().tolist())
+        self._dc = (C.c_double * (m * m))(*dc.ravel().tolist())
+        pi = getattr(op, "_point_index", None)
+        if pi is not None and not bool((pi[:op.ncases].long() == torch.arange(op.ncases, device=pi.device)).all()):
+            raise ValueError("row j of the operator must be the equation of point j: point_index must be None or the identity")
+        self._op = op
+        self.x = None
+        nbytes = int(B.lib().wlsqm_hip_krylov_system_workspace_bytes(self.npoints, m))
+        self._ws = torch.zeros((nbytes // 8,), dtype=torch.float64, device=self._device)
+
+    def _live(self):
+        if getattr(self, "_ws", None) is None:
+            raise RuntimeError("the stencil system solver has been closed")
+        return self._op._live()
+
+    def close(self):
+        """Release the workspace now; harmless when called again.  The operator and a diag tensor stay the caller's."""
+        self._ws = self._op = self.x = None
+        if hasattr(self.__dict__.get("diag"), "dim"):
+            self.diag = None
+
+    def memory_used(self):
+        """Bytes of device memory the solver holds: the workspace."""
+        self._live()
+        return self._ws.numel() * self._ws.element_size()
+
+    def refresh(self, stream=None):
+        """The Jacobi diagonal is recomputed from the operator's arrays and the diag tensor as they are on the stream by the start of
+        every solve and enqueue, a captured one included: after op.update or an in-place change of diag there is nothing left to call.
+        refresh() says so in code that is written for a preconditioner which needs it; it checks that the solver is live."""
+        self._live()
+        return self
+
+    def _vector(self, t, name):
+        if not hasattr(t, "dim") or not hasattr(t, "is_cuda"):
+            raise ValueError("argument %s must be a device (HIP) tensor" % name)
+        _check(t, name, "float64", 2)
+        if tuple(t.shape) != (self.npoints, self.m) or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float64 device tensor of shape (%d, %d), the m unknowns of a point side by side; got "
+                             "shape %s with strides %s" % (name, self.npoints, self.m, tuple(t.shape), tuple(t.stride())))
+        _same_device(self._ws, t)
+        if self.m % 2 == 0 and t.data_ptr() % 16:
+            raise ValueError("%s must be 16-byte aligned for m = %d" % (name, self.m))
+
+    def _vectors(self, **named):
+        self._live()
+        for name, t in named.items():
+            self._vector(t, name)
+        held = dict(named, workspace=self._ws)
+        if hasattr(self.diag, "dim"):
+            held["diag"] = self.diag
+        names = list(held)
+        for i, a in enumerate(names):
+            for b in names[i + 1:]:
+                if a in named and _overlap(held[a], held[b]):
+                    raise ValueError("%s overlaps %s in memory" % (a, b))
+
+    def _system(self):
+        m = self._op._m
+        d = self.diag
+        return (m["nrows"], int(m["width"].shape[0]), _ptr(m["len"]), _ptr(m["width"]), _ptr(m["soff"]), _ptr(m["col"]), _ptr(self._op._val),
+                m["total"], self.nop, self.m, C.cast(self._cp, C.c_void_p), _ptr(d) if hasattr(d, "dim") else None,
+                C.cast(self._dc, C.c_void_p))
+
+    _no_capture = StencilSolver._no_capture
+    _tolerances = staticmethod(StencilSolver._tolerances)
+
+    def _start(self, b, x, rtol, atol, maxiter, dev, s):
+        B.check(B.lib().wlsqm_hip_krylov_system_start_device(*self._system(), self._jacobi, _ptr(b), _ptr(x), rtol, atol, maxiter,
+                                                             _ptr(self._ws), dev, s))
+
+    def _iterate(self, x, niter, dev, s):
+        B.check(B.lib().wlsqm_hip_krylov_system_bicgstab_device(*self._system(), self._jacobi, _ptr(x), niter, _ptr(self._ws), dev, s))
+
+    def enqueue(self, b, x, iterations, rtol=1e-10, atol=0.0, stream=None):
+        """The start of a solve and `iterations` iterations as kernel launches on `stream` and nothing else, as StencilSolver.enqueue:
+        no allocation, no host read, capturable behind op.update(S, check=False).  x (npoints, m) holds the initial guess and receives
+        the solution; info() tells later how it went."""
+        self._vectors(b=b, x=x)
+        rtol, atol, iterations = self._tolerances(rtol, atol, iterations)
+        s, dev = _stream_and_device(x, stream)
+        self._start(b, x, rtol, atol, iterations, dev, s)
+        self._iterate(x, iterations, dev, s)
+        self.x = x
+        return self
+
+    def _read(self, what, stream):
+        self._live()
+        self._no_capture(what, stream)
+        with _torch_stream(stream, self._device):
+            head = self._ws[:16].cpu().numpy()
+        ints = head[8:10].view("int32")
+        return SolveInfo(int(ints[1]), int(ints[0]), float(head[4]) ** 0.5), bool(ints[2])
+
+    def info(self, stream=None):
+        """SolveInfo of the last solve enqueued on `stream`: one read of 128 bytes, which synchronises with that stream."""
+        return self._read("info", stream)[0]
+
+    def solve(self, b, x0=None, rtol=1e-10, atol=0.0, maxiter=1000, check_every=8, stream=None):
+        """The solution of M x = b; returns SolveInfo(status, iterations, residual).  x0 (npoints, m) is what StencilSolver.solve calls
+        x: it holds the initial guess and receives the solution in place.  x0=None starts from zero in a new tensor.  Either way
+        `solver.x` names the tensor that holds the solution afterwards.  The outcome is read every `check_every` iterations; the stop
+        is taken on the device after every iteration.  RuntimeError inside a graph capture."""
+        import torch
+        self._live()
+        self._no_capture("solve", stream)
+        if x0 is None:
+            with _torch_stream(stream, self._device):
+                x0 = torch.zeros((self.npoints, self.m), dtype=torch.float64, device=self._device)
+        x = x0
+        self._vectors(b=b, x=x)
+        rtol, atol, maxiter = self._tolerances(rtol, atol, maxiter)
+        check_every = int(check_every)
+        if check_every < 1:
+            raise ValueError("check_every must be >= 1; got %d" % check_every)
+        s, dev = _stream_and_device(x, stream)
+        self._start(b, x, rtol, atol, maxiter, dev, s)
+        self.x = x
+        left = maxiter
+        while True:
+            n = min(check_every, left)
+            self._iterate(x, n, dev, s)
+            left -= n
+            info, done = self._read("solve", stream)
+            if done or left == 0:
+                return info
+
+    def product(self, v, w=None, out=None, stream=None):
+        """(M v, (M v, w), (M v, M v)): the solve's own fused product and the dot products of its pass (w default v), all (npoints, m).
+        One host read of the two sums; not between an enqueue and the end of its solve."""
+        import torch
+        self._live()
+        self._no_capture("product", stream)
+        w = v if w is None else w
+        if out is None:
+            with _torch_stream(stream, self._device):
+                out = torch.empty((self.npoints, self.m), dtype=torch.float64, device=self._device)
+        if w is v:
+            self._vectors(v=v, out=out)
+        else:
+            self._vectors(v=v, w=w, out=out)
+        s, dev = _stream_and_device(v, stream)
+        B.check(B.lib().wlsqm_hip_krylov_system_product_device(*self._system(), _ptr(v), _ptr(w), _ptr(out), _ptr(self._ws), dev, s))
+        with _torch_stream(stream, self._device):
+            head = self._ws[:16].cpu().numpy()
+        return out, float(head[6]), float(head[7])
+
+    def matrix(self):
+        """M as a new torch.sparse_csr_tensor of m npoints rows in the interleaved numbering (row i m + a: component a at point i), built
+        with torch operations from the operator's planes, coupling and diag as they are now: columns sorted, duplicates summed, the
+        blocks whose coupling is all zeros left out.  For checks and as the baseline of a flattened solve; not for a graph capture."""
+        import torch
+        self._live()
+        op, m, n = self._op, self.m, self.npoints
+        src, row = op._entries()
+        col = op._m["col"][src].long()
+        rows, cols, vals = [], [], []
+        cp = torch.from_numpy(self.coupling).to(self._device)
+        for a in range(m):
+            for b in range(m):
+                if self.coupling[a, b].any():
+                    rows.append(row * m + a)
+                    cols.append(col * m + b)
+                    vals.append((cp[a, b][:, None] * op._val[:, src]).sum(dim=0))
+                tensor = hasattr(self.diag, "dim")
+                if tensor or self.diag[a, b] != 0.0:
+                    i = torch.arange(n, device=self._device)
+                    rows.append(i * m + a)
+                    cols.append(i * m + b)
+                    vals.append(self.diag[a, b] if tensor else torch.full((n,), float(self.diag[a, b]), dtype=torch.float64, device=self._device))
+        if not rows:
+            rows = cols = [torch.zeros((0,), dtype=torch.int64, device=self._device)]
+            vals = [torch.zeros((0,), dtype=torch.float64, device=self._device)]
+        coo = torch.sparse_coo_tensor(torch.stack([torch.cat(rows), torch.cat(cols)]), torch.cat(vals), (m * n, m * n))
+        import warnings
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)
+            return coo.coalesce().to_sparse_csr()
 
 
 def differentiable_stencil_solve(solver, b, x0=None, S=None, coefficients=None, rtol=1e-10, atol=0.0, maxiter=1000, check_every=8,
