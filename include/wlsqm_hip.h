@@ -816,6 +816,36 @@ int wlsqm_hip_krylov_system_product_device(int64_t npoints, int64_t nslices, con
                                            const double* diag, const double* diag_const, const double* in, const double* w, double* out,
                                            void* workspace, int device, void* stream);
 
+/* ---- coupled fields: transposed solves and gradients (extension; csrc/krylov.hip) ----
+ * The three calls above for M^T, whose block (a, b) is D_ba + sum_o coupling[b][a][o] * A_o^T: len .. val are the arrays of the TRANSPOSED
+ * planes (total their stored entries), while coupling, diag and diag_const are the forward system's own, unchanged: the call exchanges
+ * (a, b) in the host tables and reads a diag tensor in place at the exchanged index.  Everything else — workspace, scalars, statuses,
+ * launches, alignment — is as above; the Jacobi diagonal holds the same numbers as the forward system's. */
+int wlsqm_hip_krylov_system_start_transposed_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                    const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                                                    const double* coupling, const double* diag, const double* diag_const, int jacobi,
+                                                    const double* b, const double* x, double rtol, double atol, int64_t maxiter,
+                                                    void* workspace, int device, void* stream);
+int wlsqm_hip_krylov_system_bicgstab_transposed_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                       const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop,
+                                                       int m, const double* coupling, const double* diag, const double* diag_const,
+                                                       int jacobi, double* x, int64_t niter, void* workspace, int device, void* stream);
+int wlsqm_hip_krylov_system_product_transposed_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                      const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop,
+                                                      int m, const double* coupling, const double* diag, const double* diag_const,
+                                                      const double* in, const double* w, double* out, void* workspace, int device,
+                                                      void* stream);
+/* The gradients of a loss L through M x = b from x and lam, the solution of M^T lam = dL/dx, both (npoints, m) interleaved, in one pass
+ * over the FORWARD structure ("krylov-system-grads"; the values are not read):
+ *   grad_val  (nop, total), the planes' layout, or NULL: dL/d(entry e of row j in plane o) = -sum_b (sum_a coupling[a][b][o] lam[j][a])
+ *             x[col][b] at the live entries, +0.0 in every padding position;
+ *   grad_diag (m, m, npoints) or NULL: -(lam[i][a] * x[i][b]).
+ * The order of operations is stated at the head of the kernel.  One launch, no workspace, no atomics; lam and x 16-byte aligned for
+ * m = 2 and 4.  WLSQM_EVALUE when neither output is asked for (total == 0 counts grad_val as not asked for, and then as nothing to do). */
+int wlsqm_hip_krylov_system_grads_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                         const int32_t* col, int64_t total, int nop, int m, const double* coupling, const double* lam,
+                                         const double* x, double* grad_val, double* grad_diag, int device, void* stream);
+
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ---- */
 /* Runs `reps` back-to-back launches of the fit kernel for batch `b` (device-resident, uniform
  * order) on `stream`, bracketed by HIP events on that stream; returns the mean kernel time in

@@ -1655,6 +1655,9 @@ static int krylov_tolerances(const char* who, const void* b, const void* x, doub
 // recurrence are KrylovWork's at nrows = m npoints, and the update and reduce kernels above serve them unchanged: the product's
 // launches write ceil(npoints / 256) partials per plane, the updates' ceil(m npoints / 256), and each reduce is handed the count of
 // the launch that wrote.
+// M^T is the same kind of system: block (a, b) of M^T is D_ba + sum_o coupling[b][a][o] A_o^T, so the same kernels
+// serve it on the transposed arrays of the planes, with coupling and dconst exchanged on the host when KrylovCoupled is filled and a
+// diag tensor read in place at the exchanged index (dswap).  The scalar diagonal holds the same numbers.
 
 constexpr int KRYLOV_SYSTEM_FIELDS = 4;     // m <= 4
 constexpr int KRYLOV_SYSTEM_PLANES = 8;     // nop <= 8: the coupling table is at most 4 * 4 * 8 = 128 doubles
@@ -1664,6 +1667,7 @@ struct KrylovCoupled {
     const int32_t* len; const int32_t* width; const long long* soff;
     const int32_t* col; const double* val;                      // plane o at val + o * total
     const double* dten;                                          // D_ab,i = dten ? dten[(a * m + b) * npoints + i] : dconst[a * m + b]
+    int dswap;                                                   // M^T: dten is read at [(b * m + a) * npoints + i] (the host tables come exchanged)
     double dconst[KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS];
     double coupling[KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_PLANES];   // [(a * m + b) * nop + o]
 };
@@ -1760,7 +1764,7 @@ __global__ void __launch_bounds__(256) krylov_system_spmv_kernel(const KrylovCou
                 double sa = 0.0;
 #pragma unroll
                 for (int b = 0; b < M; ++b) {
-                    const double d = q.dten ? q.dten[(a * M + b) * q.npoints + row] : q.dconst[a * M + b];
+                    const double d = q.dten ? q.dten[(q.dswap ? b * M + a : a * M + b) * q.npoints + row] : q.dconst[a * M + b];
                     sa = b == 0 ? d * xi[0] : __builtin_fma(d, xi[b], sa);
                 }
                 y[a] = acc[a] + sa;
@@ -1822,6 +1826,120 @@ __global__ void __launch_bounds__(256) krylov_system_diag_kernel(const KrylovCou
         }
     }
     block_sums<false>(bad, 0.0, partial, gridDim.x);
+}
+
+// The gradients of a loss through the coupled solve M x = b, lam the solution of M^T lam = dL/dx, in one pass
+// over the forward structure with krylov_system_spmv_kernel's mapping.  The order of operations, which
+// tests/_krylov_system_adjoint_ref.py states in numpy:
+//   per lane, once:  u[b][o] = c[0][b][o] * lam_0, then u[b][o] = fma(c[a][b][o], lam_a, u[b][o]) for a = 1 .. m - 1   (lam the row's own)
+//   VALUES (nop, total): per live entry in entry order, per plane o: t = u[0][o] * x_0, then t = fma(u[b][o], x_b, t) for b = 1 .. m - 1,
+//           x the unknowns of the entry's column; gval[o * total + at + 64 e] = -t.  +0.0 in every padding position of every plane, the
+//           lanes of rows beyond npoints included; their padding col is never loaded, and val is never loaded at all
+//   DIAG (m, m, npoints): gdiag[(a * m + b) * npoints + j] = -(lam[j][a] * x[j][b]), one rounding
+// Each output is a template flag: a pass without VALUES never stores into a plane.  No atomics, no scratch, no workspace.
+template <int M, int NOP>
+__device__ __forceinline__ void krylov_system_grads_entry(const double (&u)[M][NOP], const double (&xs)[M], double* out, long long total) {
+#pragma unroll
+    for (int o = 0; o < NOP; ++o) {
+        double t = u[0][o] * xs[0];
+#pragma unroll
+        for (int b = 1; b < M; ++b) t = __builtin_fma(u[b][o], xs[b], t);
+        out[o * total] = -t;
+    }
+}
+
+template <int M, int NOP, bool VALUES, bool DIAG>
+__global__ void __launch_bounds__(256) krylov_system_grads_kernel(const KrylovCoupled q, const double* lam, const double* x, double* gval,
+                                                                  double* gdiag) {
+    const int lane = threadIdx.x & 63;
+    const long long s = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long row = s * 64 + lane;
+    if (s * 64 >= q.npoints) return;                             // wave-uniform
+    const bool live = row < q.npoints;
+    double lj[M];
+#pragma unroll
+    for (int a = 0; a < M; ++a) lj[a] = 0.0;
+    if (live) krylov_load_point<M>(lam + row * M, lj);
+    if (DIAG && live) {
+        double xj[M];
+        krylov_load_point<M>(x + row * M, xj);
+#pragma unroll
+        for (int a = 0; a < M; ++a) {
+#pragma unroll
+            for (int b = 0; b < M; ++b) gdiag[(a * M + b) * q.npoints + row] = -(lj[a] * xj[b]);
+        }
+    }
+    if (VALUES) {
+        constexpr int UNROLL = 4;
+        const int wid = __builtin_amdgcn_readfirstlane(q.width[s]);
+        const long long at = q.soff[s] + lane;
+        int n = live ? q.len[row] : 0;
+        n = n < wid ? n : wid;
+        const int32_t* col = q.col + at;
+        double* out = gval + at;
+        double u[M][NOP];
+#pragma unroll
+        for (int b = 0; b < M; ++b) {
+#pragma unroll
+            for (int o = 0; o < NOP; ++o) {
+                double t = q.coupling[b * NOP + o] * lj[0];
+#pragma unroll
+                for (int a = 1; a < M; ++a) t = __builtin_fma(q.coupling[(a * M + b) * NOP + o], lj[a], t);
+                u[b][o] = t;
+            }
+        }
+        for (int e = 0; e < wid; e += UNROLL) {                  // wave-uniform
+            if (e + UNROLL <= n) {
+                double xs[UNROLL][M];
+#pragma unroll
+                for (int k = 0; k < UNROLL; ++k) {
+                    const long long c = col[64LL * (e + k)];
+                    krylov_load_point<M>(x + c * M, xs[k]);
+                }
+#pragma unroll
+                for (int k = 0; k < UNROLL; ++k) krylov_system_grads_entry<M, NOP>(u, xs[k], out + 64LL * (e + k), q.total);
+            } else {
+                for (int k = 0; k < UNROLL && e + k < wid; ++k) {
+                    if (e + k < n) {
+                        const long long c = col[64LL * (e + k)];
+                        double xs[M];
+                        krylov_load_point<M>(x + c * M, xs);
+                        krylov_system_grads_entry<M, NOP>(u, xs, out + 64LL * (e + k), q.total);
+                    } else {
+#pragma unroll
+                        for (int o = 0; o < NOP; ++o) out[o * q.total + 64LL * (e + k)] = 0.0;
+                    }
+                }
+            }
+        }
+    }
+}
+
+template <int M, int NOP>
+static void krylov_system_grads_run(const KrylovCoupled& q, const double* lam, const double* x, double* gval, double* gdiag, hipStream_t s) {
+    const dim3 grid((unsigned)((q.npoints + 255) / 256)), block(256);
+    if (gdiag) hipLaunchKernelGGL((krylov_system_grads_kernel<M, NOP, true, true>), grid, block, 0, s, q, lam, x, gval, gdiag);
+    else hipLaunchKernelGGL((krylov_system_grads_kernel<M, NOP, true, false>), grid, block, 0, s, q, lam, x, gval, gdiag);
+}
+
+template <int M>
+static void krylov_system_grads_planes(int nop, const KrylovCoupled& q, const double* lam, const double* x, double* gval, double* gdiag,
+                                       hipStream_t s) {
+    if (!gval) {                                                 // DIAG alone does not look at the planes: one instance per m
+        hipLaunchKernelGGL((krylov_system_grads_kernel<M, 1, false, true>), dim3((unsigned)((q.npoints + 255) / 256)), dim3(256), 0, s, q,
+                           lam, x, gval, gdiag);
+        return;
+    }
+    switch (nop) {
+    case 1: krylov_system_grads_run<M, 1>(q, lam, x, gval, gdiag, s); break;
+    case 2: krylov_system_grads_run<M, 2>(q, lam, x, gval, gdiag, s); break;
+    case 3: krylov_system_grads_run<M, 3>(q, lam, x, gval, gdiag, s); break;
+    case 4: krylov_system_grads_run<M, 4>(q, lam, x, gval, gdiag, s); break;
+    case 5: krylov_system_grads_run<M, 5>(q, lam, x, gval, gdiag, s); break;
+    case 6: krylov_system_grads_run<M, 6>(q, lam, x, gval, gdiag, s); break;
+    case 7: krylov_system_grads_run<M, 7>(q, lam, x, gval, gdiag, s); break;
+    default: krylov_system_grads_run<M, 8>(q, lam, x, gval, gdiag, s); break;
+    }
 }
 
 enum { SYSTEM_CALL_START = 0, SYSTEM_CALL_ITERATE = 1, SYSTEM_CALL_PRODUCT = 2 };
@@ -1891,7 +2009,8 @@ static void krylov_system_planes(int nop, const KrylovSystemCall& c) {
 // The checks and the kernel argument that the three entry points share, then the call's launches.
 static int krylov_system_call(const char* who, KrylovSystemCall& c, int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
                               const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
-                              const double* coupling, const double* diag, const double* diag_const, void* workspace, int device) {
+                              const double* coupling, const double* diag, const double* diag_const, void* workspace, int device,
+                              bool transposed = false) {
     const std::string name(who);
     if (m < 1 || m > KRYLOV_SYSTEM_FIELDS) { set_error(name + ": m must be 1 .. 4"); return WLSQM_EVALUE; }
     if (nop < 1 || nop > KRYLOV_SYSTEM_PLANES) { set_error(name + ": nop must be 1 .. 8"); return WLSQM_EVALUE; }
@@ -1910,9 +2029,17 @@ static int krylov_system_call(const char* who, KrylovSystemCall& c, int64_t npoi
     KrylovCoupled& q = c.q;
     q.npoints = npoints; q.total = total;
     q.len = len; q.width = width; q.soff = reinterpret_cast<const long long*>(soff);
-    q.col = col; q.val = val; q.dten = diag;
+    q.col = col; q.val = val; q.dten = diag; q.dswap = transposed ? 1 : 0;
     for (int i = 0; i < KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS; ++i) q.dconst[i] = (!diag && i < m * m) ? diag_const[i] : 0.0;
     for (int i = 0; i < KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_PLANES; ++i) q.coupling[i] = i < m * m * nop ? coupling[i] : 0.0;
+    if (transposed) {                                           // block (a, b) of M^T takes D_ba and coupling[b][a][:]
+        for (int a = 0; a < m; ++a) {
+            for (int b = 0; b < m; ++b) {
+                if (!diag) q.dconst[a * m + b] = diag_const[b * m + a];
+                for (int o = 0; o < nop; ++o) q.coupling[(a * m + b) * nop + o] = coupling[(b * m + a) * nop + o];
+            }
+        }
+    }
     DeviceScope scope;
     const int rc = scope.enter(device);
     if (rc != WLSQM_OK) return rc;
@@ -2491,6 +2618,90 @@ int wlsqm_hip_krylov_system_product_device(int64_t npoints, int64_t nslices, con
     c.rtol = c.atol = 0.0; c.niter = 0; c.s = (hipStream_t)stream;
     return krylov_system_call("krylov_system_product", c, npoints, nslices, len, width, soff, col, val, total, nop, m, coupling, diag,
                               diag_const, workspace, device);
+}
+
+// M^T: the three calls above on the transposed arrays of the planes; coupling, diag and diag_const are the forward system's own.
+int wlsqm_hip_krylov_system_start_transposed_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                    const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                                                    const double* coupling, const double* diag, const double* diag_const, int jacobi,
+                                                    const double* b, const double* x, double rtol, double atol, int64_t maxiter,
+                                                    void* workspace, int device, void* stream) {
+    int rc = krylov_tolerances("krylov_system_start_transposed", b, x, rtol, atol, maxiter);
+    if (rc != WLSQM_OK) return rc;
+    KrylovSystemCall c;
+    c.what = SYSTEM_CALL_START; c.jacobi = jacobi; c.maxiter = (int)maxiter;
+    c.in = x; c.other = b; c.x = const_cast<double*>(x);
+    c.rtol = rtol; c.atol = atol; c.niter = 0; c.s = (hipStream_t)stream;
+    return krylov_system_call("krylov_system_start_transposed", c, npoints, nslices, len, width, soff, col, val, total, nop, m, coupling,
+                              diag, diag_const, workspace, device, true);
+}
+
+int wlsqm_hip_krylov_system_bicgstab_transposed_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                       const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop,
+                                                       int m, const double* coupling, const double* diag, const double* diag_const,
+                                                       int jacobi, double* x, int64_t niter, void* workspace, int device, void* stream) {
+    if (niter < 0) { set_error("krylov_system_bicgstab_transposed: niter must be >= 0"); return WLSQM_EVALUE; }
+    KrylovSystemCall c;
+    c.what = SYSTEM_CALL_ITERATE; c.jacobi = jacobi; c.maxiter = 0;
+    c.in = x; c.other = x; c.x = x;
+    c.rtol = c.atol = 0.0; c.niter = niter; c.s = (hipStream_t)stream;
+    return krylov_system_call("krylov_system_bicgstab_transposed", c, npoints, nslices, len, width, soff, col, val, total, nop, m, coupling,
+                              diag, diag_const, workspace, device, true);
+}
+
+int wlsqm_hip_krylov_system_product_transposed_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                      const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop,
+                                                      int m, const double* coupling, const double* diag, const double* diag_const,
+                                                      const double* in, const double* w, double* out, void* workspace, int device,
+                                                      void* stream) {
+    KrylovSystemCall c;
+    c.what = SYSTEM_CALL_PRODUCT; c.jacobi = 0; c.maxiter = 0;
+    c.in = in; c.other = w; c.x = out;
+    c.rtol = c.atol = 0.0; c.niter = 0; c.s = (hipStream_t)stream;
+    return krylov_system_call("krylov_system_product_transposed", c, npoints, nslices, len, width, soff, col, val, total, nop, m, coupling,
+                              diag, diag_const, workspace, device, true);
+}
+
+int wlsqm_hip_krylov_system_grads_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                         const int32_t* col, int64_t total, int nop, int m, const double* coupling, const double* lam,
+                                         const double* x, double* grad_val, double* grad_diag, int device, void* stream) {
+    const std::string name("krylov_system_grads");
+    if (m < 1 || m > KRYLOV_SYSTEM_FIELDS) { set_error(name + ": m must be 1 .. 4"); return WLSQM_EVALUE; }
+    if (nop < 1 || nop > KRYLOV_SYSTEM_PLANES) { set_error(name + ": nop must be 1 .. 8"); return WLSQM_EVALUE; }
+    if (npoints < 1 || nslices < 0 || npoints > 64 * nslices || total < 0 || (npoints + 255) / 256 > 0x7fffffffLL) {
+        set_error(name + ": npoints must be 1 .. 64 * nslices");
+        return WLSQM_EVALUE;
+    }
+    if (!len || !width || !soff || !col || !coupling || !lam || !x) { set_error(name + ": null array"); return WLSQM_EVALUE; }
+    if (total == 0) grad_val = nullptr;                          // no stored entry: nothing to write
+    if (!grad_val && !grad_diag) {
+        if (total == 0) return WLSQM_OK;
+        set_error(name + ": no output is asked for");
+        return WLSQM_EVALUE;
+    }
+    if (m % 2 == 0 && (((uintptr_t)lam | (uintptr_t)x) & 15)) {
+        set_error(name + ": with m = 2 or 4 lam and x must be 16-byte aligned");
+        return WLSQM_EVALUE;
+    }
+    KrylovCoupled q;
+    q.npoints = npoints; q.total = total;
+    q.len = len; q.width = width; q.soff = reinterpret_cast<const long long*>(soff);
+    q.col = col; q.val = nullptr; q.dten = nullptr; q.dswap = 0;
+    for (int i = 0; i < KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS; ++i) q.dconst[i] = 0.0;
+    for (int i = 0; i < KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_PLANES; ++i) q.coupling[i] = i < m * m * nop ? coupling[i] : 0.0;
+    DeviceScope scope;
+    const int rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    switch (m) {
+    case 1: krylov_system_grads_planes<1>(nop, q, lam, x, grad_val, grad_diag, s); break;
+    case 2: krylov_system_grads_planes<2>(nop, q, lam, x, grad_val, grad_diag, s); break;
+    case 3: krylov_system_grads_planes<3>(nop, q, lam, x, grad_val, grad_diag, s); break;
+    default: krylov_system_grads_planes<4>(nop, q, lam, x, grad_val, grad_diag, s); break;
+    }
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-system-grads");
+    return WLSQM_OK;
 }
 
 }  // extern "C"

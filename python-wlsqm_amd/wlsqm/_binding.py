@@ -275,6 +275,15 @@ def lib():
         L.wlsqm_hip_krylov_system_product_device.argtypes = coupled + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         for name in ("start", "bicgstab", "product"):
             getattr(L, "wlsqm_hip_krylov_system_%s_device" % name).restype = C.c_int
+    # their transposed forms and the gradients through such a solve (StencilSystemSolver.gradients)
+    if hasattr(L, "wlsqm_hip_krylov_system_grads_device"):
+        for name in ("start", "bicgstab", "product"):
+            fn = getattr(L, "wlsqm_hip_krylov_system_%s_transposed_device" % name)
+            fn.argtypes = getattr(L, "wlsqm_hip_krylov_system_%s_device" % name).argtypes
+            fn.restype = C.c_int
+        L.wlsqm_hip_krylov_system_grads_device.argtypes = ([C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_int]
+                                                           + [C.c_void_p] * 5 + [C.c_int, C.c_void_p])
+        L.wlsqm_hip_krylov_system_grads_device.restype = C.c_int
     # batched dense solves (wlsqm.utils.lapackdrivers, wlsqm.hip.*_batched)
     for op in ("getrf", "gesv", "sytrf", "sysv"):
         solve = op in ("gesv", "sysv")

@@ -20,7 +20,7 @@ __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_c
            "InterpolationPlan", "differentiable_evaluate",
            "StencilOperator", "stencil_rows", "differentiable_stencil_apply", "StencilSolver", "StencilSystemSolver", "SolveInfo",
            "SolveGradients", "BlockJacobi", "ApproximateInverse", "differentiable_stencil_solve", "differentiable_stencil_solve_many",
-           "SpatialOrder", "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
+           "SystemGradients", "differentiable_stencil_system_solve", "SpatialOrder", "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
            "getrf_batched", "getrs_batched", "gesv_batched", "sytrf_batched", "sytrs_batched", "sysv_batched", "symmetrize_batched"]
 
 
@@ -632,7 +632,7 @@ _AUTOGRAD = None
 
 def _autograd():
     """The torch.autograd.Function classes behind the differentiable_* functions, as a namespace with FitMany, FitCloud, Solve,
-    Evaluate, FitManyGeometry, FitCloudGeometry, StencilApply, StencilSolve and StencilSolveMany (made at first use: the module does not import torch).  Every forward takes its tensor inputs first."""
+    Evaluate, FitManyGeometry, FitCloudGeometry, StencilApply, StencilSolve, StencilSystemSolve and StencilSolveMany (made at first use: the module does not import torch).  Every forward takes its tensor inputs first."""
     global _AUTOGRAD
     if _AUTOGRAD is not None:
         return _AUTOGRAD
@@ -885,6 +885,71 @@ def _autograd():
                 return lam, gdiag, gS, gslots, gown
             return gradients(ctx, gout, 5, adjoint)
 
+    class StencilSystemSolve(torch.autograd.Function):
+        """StencilSystemSolver.solve with b, the diag tensor, the point table, the coefficients and coupling among the differentiable
+        inputs."""
+        @staticmethod
+        def forward(ctx, b, diag, S, slots, own, coupling, x0, solver, rtol, atol, maxiter, check_every, adjoint_rtol, stream):
+            op = solver._op
+            det = lambda t: t.detach() if t is not None else None
+            if S is not None:
+                op.update(S.detach(), stream=stream)
+            if slots is not None:
+                op.set_coefficients(slots.detach(), det(own), stream=stream)
+            if coupling is not None:
+                solver.set_coupling(coupling.detach().cpu().numpy())
+            with _torch_stream(stream, solver._device):
+                x = (x0.detach().clone() if x0 is not None
+                     else torch.zeros((solver.npoints, solver.m), dtype=torch.float64, device=solver._device))
+            info = solver.solve(b.detach(), x, rtol=rtol, atol=atol, maxiter=maxiter, check_every=check_every, stream=stream)
+            if info.status != 0:
+                raise RuntimeError("the forward solve did not converge: status %d, %r" % (info.status, info))
+            ctx.save_for_backward(x, *(t for t in (S, slots, own, coupling) if t is not None))
+            ctx.call = (solver, S is not None, slots is not None, own is not None, coupling is not None,
+                        adjoint_rtol if adjoint_rtol is not None else rtol, maxiter, check_every, stream)
+            return x
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gout):
+            def adjoint(g, need_b, need_diag, need_S, need_slots, need_own, need_coupling):
+                solver, has_S, has_slots, has_own, has_coupling, rtol, maxiter, check_every, stream = ctx.call
+                x, *made_from = ctx.saved_tensors
+                op, device = solver._op, solver._device
+                solver._no_capture("the backward pass of differentiable_stencil_system_solve", stream)
+                cp = made_from.pop() if has_coupling else None
+                if has_S:                                    # the operator and coupling back where the forward had them
+                    op.update(made_from[0].detach(), check=False, stream=stream)
+                elif has_slots:
+                    op.set_coefficients(made_from[0].detach(), made_from[1].detach() if has_own else None, stream=stream)
+                if has_coupling:
+                    solver.set_coupling(cp.detach().cpu().numpy())
+                with _torch_stream(stream, device):
+                    lam = torch.zeros((solver.npoints, solver.m), dtype=torch.float64, device=device)
+                    x = x.detach()
+                info = solver.solve(g, lam, rtol=rtol, atol=0.0, maxiter=maxiter, check_every=check_every, stream=stream, transpose=True)
+                if info.status != 0:
+                    raise RuntimeError("the adjoint solve did not converge: status %d, %r" % (info.status, info))
+                gdiag = gS = gslots = gown = gcp = None
+                if need_diag or need_slots or need_own:
+                    got = solver.gradients(lam, x, values=need_slots or need_own, diag=need_diag, stream=stream)
+                    gdiag = got.diag
+                    if got.values is not None:
+                        with _torch_stream(stream, device):
+                            sl, ow = op._unpack(got.values)
+                            if need_slots:
+                                gslots = torch.zeros(tuple(made_from[0].shape), dtype=torch.float64, device=device)
+                                gslots[:, :op.ncases, :op.K] = sl
+                            if need_own:
+                                gown = torch.zeros(tuple(made_from[1].shape), dtype=torch.float64, device=device)
+                                gown[:op.nop, :op.ncases] = ow
+                if need_S:
+                    gS = _system_geometry_adjoint(solver, made_from[0].detach(), x, lam, stream)
+                if need_coupling:
+                    gcp = solver.coupling_gradient(lam, x, stream=stream).to(cp.device)
+                return lam, gdiag, gS, gslots, gown, gcp
+            return gradients(ctx, gout, 6, adjoint)
+
     class StencilSolveMany(torch.autograd.Function):
         """StencilSolver.solve_many as a differentiable function of b alone: the backward pass is one solve_many(transpose=True) on the
         incoming gradient.  The gradients with respect to the operator (S, the coefficients), diag and scale are out of scope for
@@ -917,7 +982,7 @@ def _autograd():
 
     _AUTOGRAD = types.SimpleNamespace(FitMany=FitMany, FitCloud=FitCloud, Solve=Solve, Evaluate=Evaluate, FitManyGeometry=FitManyGeometry,
                                       FitCloudGeometry=FitCloudGeometry, StencilApply=StencilApply, StencilSolve=StencilSolve,
-                                      StencilSolveMany=StencilSolveMany)
+                                      StencilSolveMany=StencilSolveMany, StencilSystemSolve=StencilSystemSolve)
     return _AUTOGRAD
 
 
@@ -942,6 +1007,32 @@ def _solve_geometry_adjoint(solver, S, x, lam, stream):
     fit_cloud_device(op.dimension, op.order, S, F, hoods, fi, nk, knowns, weighting_method, point_index=point_index, stream=stream)
     return fit_cloud_geometry_adjoint_device(op.dimension, op.order, S, F, hoods, fi, nk, knowns, weighting_method, g.contiguous(),
                                              point_index=point_index, stream=stream)[0]
+
+
+def _system_geometry_adjoint(solver, S, x, lam, stream):
+    """dL/dS through the coupled M x = b at fixed x, lam and neighbour lists: section 18's route once per
+    component b — the fit of F = x[:, b] and its geometry adjoint with g_j = -sum_o (sum_a coupling[a, b, o] lam[j, a]) rows[o], per-case
+    rows where the operator has them — and the m results summed in component order."""
+    import torch
+    op = solver._op
+    hoods, nk, knowns, weighting_method, point_index = op._geo
+    rows, no, n = op._rows, op.no, op.ncases
+    total = None
+    for b in range(solver.m):
+        with _torch_stream(stream, solver._device):
+            cp = torch.from_numpy(solver.coupling[:, b, :].copy()).to(solver._device)          # (m, nop): coupling[a, b, o]
+            u = lam[:n] @ cp                                                                   # (n, nop)
+            F = torch.zeros((S.shape[0],), dtype=torch.float64, device=solver._device)         # points beyond the operator's: never named
+            F[:op.npoints] = x[:, b]
+            fi = torch.zeros((n, no), dtype=torch.float64, device=solver._device)
+            fi[:, 0] = x[:n, b]                              # the F-known cases take their own value from here (row j is point j)
+            g = -(torch.einsum("jo,ojn->jn", u, rows[:, :n, :no]) if rows.dim() == 3 else u @ rows[:, :no])
+        fit_cloud_device(op.dimension, op.order, S, F, hoods, fi, nk, knowns, weighting_method, point_index=point_index, stream=stream)
+        part = fit_cloud_geometry_adjoint_device(op.dimension, op.order, S, F, hoods, fi, nk, knowns, weighting_method, g.contiguous(),
+                                                 point_index=point_index, stream=stream)[0]
+        with _torch_stream(stream, solver._device):
+            total = part if total is None else total.add_(part)
+    return total
 
 
 def _no_geometry_grad(*geometry):
@@ -2201,6 +2292,10 @@ SolveGradients = collections.namedtuple("SolveGradients", "values diag scale")
 SolveGradients.__doc__ = """What StencilSolver.gradients returns: dL/d(the entries of the value plane) in the operator's layout, dL/d(diag)
 and dL/d(scale) (a 0-d device tensor); None for what was not asked for."""
 
+SystemGradients = collections.namedtuple("SystemGradients", "values diag")
+SystemGradients.__doc__ = """What StencilSystemSolver.gradients returns: dL/d(the entries of every value plane), (nop, total) in the operator's
+layout, and dL/d(diag), (m, m, npoints); None for what was not asked for."""
+
 SolveInfo = collections.namedtuple("SolveInfo", "status iterations residual")
 SolveInfo.__doc__ = """What a StencilSolver says of a solve.  status: 0 converged, 1 iteration limit, 2 breakdown (rho = 0 or (r0, v) = 0),
 3 a non-finite scalar, 4 a zero or non-finite Jacobi diagonal, a singular or non-finite block of a BlockJacobi or a singular row of an ApproximateInverse, -1 still running (enqueue with fewer iterations than the solve needs
@@ -2889,7 +2984,7 @@ class StencilSystemSolver:
     are a function of the inputs, and eager and captured runs agree.
 
     op: as StencilSolver takes it — square, row j the equation of point j, not closed, without known derivatives — with at most 8 planes.
-    coupling: host array-like of float64 (m, m, nop), every entry finite; read here, once.
+    coupling: host array-like of float64 (m, m, nop), every entry finite; read here, once (set_coupling replaces the table).
     diag: a float d (D = d I_m), a host (m, m) array-like of constants, or a contiguous float64 device tensor (m, m, npoints), each
     D_ab a diagonal matrix; a tensor is read at every solve (the caller may change it in place).
     preconditioner: "jacobi", the inverse of the scalar diagonal of M — for unknown (i, a): D_aa,i + sum_o coupling[a, a, o] (the sum of
@@ -2898,8 +2993,11 @@ class StencilSystemSolver:
     Unknowns and right-hand sides are contiguous float64 device tensors (npoints, m): x[i, a] is component a at point i.  For m = 2 and 4
     they are moved by 16-byte loads and must be 16-byte aligned, as every tensor that torch allocates is.
     The workspace is StencilSolver's at m npoints rows, 9 m npoints + 2 ceil(m npoints / 256) + 16 doubles, allocated here.
-    Out of scope (section 24): method="bicgstab2", BlockJacobi and ApproximateInverse, transposed solves and autograd, nfields, a
-    per-point coupling, m > 4, wlsqm.sharded."""
+    solve, enqueue and product take transpose=True for M^T, whose block (a, b) is D_ba + sum_o coupling[b, a, o] A_o^T: the same kernels
+    on the operator's transposed arrays (prepare_transpose), a diag tensor read in place.  gradients(), coupling_gradient() and
+    differentiable_stencil_system_solve carry a loss through the solve.
+    Out of scope (sections 24 and 25): method="bicgstab2", BlockJacobi and ApproximateInverse, nfields, a per-point coupling, m > 4, a
+    capturable backward pass, second derivatives, wlsqm.sharded."""
 
     def __init__(self, op, coupling, diag=0.0, preconditioner="jacobi"):
         import numpy as np
@@ -2915,16 +3013,7 @@ class StencilSystemSolver:
         if preconditioner is not None and not (isinstance(preconditioner, str) and preconditioner == "jacobi"):
             raise ValueError("preconditioner must be 'jacobi' or None for coupled fields; got %r" % (preconditioner,))
         self._jacobi = 1 if preconditioner == "jacobi" else 0
-        if hasattr(coupling, "is_cuda") and coupling.is_cuda:
-            raise ValueError("coupling must be a host array (m, m, nop); got a device tensor")
-        cp = np.ascontiguousarray(np.asarray(coupling, dtype=np.float64))
-        if cp.ndim != 3 or cp.shape[0] != cp.shape[1] or not 1 <= cp.shape[0] <= 4 or cp.shape[2] != op.nop:
-            raise ValueError("coupling must have shape (m, m, nop) with 1 <= m <= 4 and nop = %d, the operator's value planes; got shape %s"
-                             % (op.nop, tuple(cp.shape)))
-        if op.nop > 8:
-            raise ValueError("coupled fields take an operator of at most 8 value planes; it has %d" % op.nop)
-        if not np.isfinite(cp).all():
-            raise ValueError("every entry of coupling must be finite")
+        cp = self._coupling_table(coupling, op.nop)
         m = int(cp.shape[0])
         self.m, self.nop, self.npoints, self._device = m, op.nop, op.npoints, op._device
         self.coupling = cp
@@ -2956,6 +3045,35 @@ class StencilSystemSolver:
         self.x = None
         nbytes = int(B.lib().wlsqm_hip_krylov_system_workspace_bytes(self.npoints, m))
         self._ws = torch.zeros((nbytes // 8,), dtype=torch.float64, device=self._device)
+
+    @staticmethod
+    def _coupling_table(coupling, nop, m=None):
+        """The constructor's checks of `coupling`: a contiguous float64 host array (m, m, nop), every entry finite (m given: that m)."""
+        import numpy as np
+        if hasattr(coupling, "is_cuda") and coupling.is_cuda:
+            raise ValueError("coupling must be a host array (m, m, nop); got a device tensor")
+        cp = np.ascontiguousarray(np.array(coupling, dtype=np.float64))    # a copy: the caller's array may change afterwards
+        if cp.ndim != 3 or cp.shape[0] != cp.shape[1] or not 1 <= cp.shape[0] <= 4 or cp.shape[2] != nop:
+            raise ValueError("coupling must have shape (m, m, nop) with 1 <= m <= 4 and nop = %d, the operator's value planes; got shape %s"
+                             % (nop, tuple(cp.shape)))
+        if nop > 8:
+            raise ValueError("coupled fields take an operator of at most 8 value planes; it has %d" % nop)
+        if m is not None and cp.shape[0] != m:
+            raise ValueError("the new coupling must keep the solver's shape (%d, %d, %d); got shape %s" % (m, m, nop, tuple(cp.shape)))
+        if not np.isfinite(cp).all():
+            raise ValueError("every entry of coupling must be finite")
+        return cp
+
+    def set_coupling(self, coupling):
+        """Replace the coupling table by a new one of the same shape (m, m, nop), under the constructor's checks (a host array, every
+        entry finite; ValueError).  The table is host memory that travels with every launch: nothing is enqueued, and the next solve,
+        product or gradient reads the new one (a captured graph keeps the table it was captured with) — parameter sweeps on one
+        workspace, and what autograd writes `coupling` with."""
+        self._live()
+        cp = self._coupling_table(coupling, self.nop, self.m)
+        self.coupling = cp
+        self._cp = (C.c_double * cp.size)(*cp.ravel().tolist())
+        return self
 
     def _live(self):
         if getattr(self, "_ws", None) is None:
@@ -3004,32 +3122,51 @@ class StencilSystemSolver:
                 if a in named and _overlap(held[a], held[b]):
                     raise ValueError("%s overlaps %s in memory" % (a, b))
 
-    def _system(self):
-        m = self._op._m
+    def _system(self, transpose=False):
+        """The system's arguments of the C entry points; transpose: the operator's transposed arrays for the *_transposed_device calls,
+        which exchange (a, b) in coupling and diag themselves."""
+        m, val = (self._op._t, self._op._tval) if transpose else (self._op._m, self._op._val)
         d = self.diag
-        return (m["nrows"], int(m["width"].shape[0]), _ptr(m["len"]), _ptr(m["width"]), _ptr(m["soff"]), _ptr(m["col"]), _ptr(self._op._val),
+        return (m["nrows"], int(m["width"].shape[0]), _ptr(m["len"]), _ptr(m["width"]), _ptr(m["soff"]), _ptr(m["col"]), _ptr(val),
                 m["total"], self.nop, self.m, C.cast(self._cp, C.c_void_p), _ptr(d) if hasattr(d, "dim") else None,
                 C.cast(self._dc, C.c_void_p))
 
     _no_capture = StencilSolver._no_capture
     _tolerances = staticmethod(StencilSolver._tolerances)
 
-    def _start(self, b, x, rtol, atol, maxiter, dev, s):
-        B.check(B.lib().wlsqm_hip_krylov_system_start_device(*self._system(), self._jacobi, _ptr(b), _ptr(x), rtol, atol, maxiter,
-                                                             _ptr(self._ws), dev, s))
+    def _transposed(self, transpose, stream):
+        """The operator's transposed matrix, built at the first transposed use (prepare_transpose: RuntimeError inside a capture)."""
+        if transpose and self._op._t is None:
+            self.prepare_transpose(stream)
+        return bool(transpose)
 
-    def _iterate(self, x, niter, dev, s):
-        B.check(B.lib().wlsqm_hip_krylov_system_bicgstab_device(*self._system(), self._jacobi, _ptr(x), niter, _ptr(self._ws), dev, s))
+    def prepare_transpose(self, stream=None):
+        """Build now what a transposed solve needs: the operator's transposed matrix with all its planes (op.prepare_transpose).  Without
+        this call the first transposed use builds it, which allocates and synchronises — RuntimeError when that would happen inside a
+        graph capture.  op.update and set_coefficients keep it refreshed, or drop it where the operator does (new hoods; too large for
+        its index pairs), and the next transposed use rebuilds it.  Returns True when this call built something."""
+        self._live()
+        return self._op.prepare_transpose(stream) if self._op._t is None else False
 
-    def enqueue(self, b, x, iterations, rtol=1e-10, atol=0.0, stream=None):
+    def _start(self, b, x, rtol, atol, maxiter, dev, s, transpose=False):
+        fn = B.lib().wlsqm_hip_krylov_system_start_transposed_device if transpose else B.lib().wlsqm_hip_krylov_system_start_device
+        B.check(fn(*self._system(transpose), self._jacobi, _ptr(b), _ptr(x), rtol, atol, maxiter, _ptr(self._ws), dev, s))
+
+    def _iterate(self, x, niter, dev, s, transpose=False):
+        fn = B.lib().wlsqm_hip_krylov_system_bicgstab_transposed_device if transpose else B.lib().wlsqm_hip_krylov_system_bicgstab_device
+        B.check(fn(*self._system(transpose), self._jacobi, _ptr(x), niter, _ptr(self._ws), dev, s))
+
+    def enqueue(self, b, x, iterations, rtol=1e-10, atol=0.0, stream=None, transpose=False):
         """The start of a solve and `iterations` iterations as kernel launches on `stream` and nothing else, as StencilSolver.enqueue:
         no allocation, no host read, capturable behind op.update(S, check=False).  x (npoints, m) holds the initial guess and receives
-        the solution; info() tells later how it went."""
+        the solution; info() tells later how it went.  transpose=True solves M^T x = b by the same kernels on the operator's transposed
+        matrix, which is built at the first transposed use (RuntimeError inside a capture: call prepare_transpose first)."""
         self._vectors(b=b, x=x)
         rtol, atol, iterations = self._tolerances(rtol, atol, iterations)
+        transpose = self._transposed(transpose, stream)
         s, dev = _stream_and_device(x, stream)
-        self._start(b, x, rtol, atol, iterations, dev, s)
-        self._iterate(x, iterations, dev, s)
+        self._start(b, x, rtol, atol, iterations, dev, s, transpose)
+        self._iterate(x, iterations, dev, s, transpose)
         self.x = x
         return self
 
@@ -3045,11 +3182,11 @@ class StencilSystemSolver:
         """SolveInfo of the last solve enqueued on `stream`: one read of 128 bytes, which synchronises with that stream."""
         return self._read("info", stream)[0]
 
-    def solve(self, b, x0=None, rtol=1e-10, atol=0.0, maxiter=1000, check_every=8, stream=None):
+    def solve(self, b, x0=None, rtol=1e-10, atol=0.0, maxiter=1000, check_every=8, stream=None, transpose=False):
         """The solution of M x = b; returns SolveInfo(status, iterations, residual).  x0 (npoints, m) is what StencilSolver.solve calls
         x: it holds the initial guess and receives the solution in place.  x0=None starts from zero in a new tensor.  Either way
         `solver.x` names the tensor that holds the solution afterwards.  The outcome is read every `check_every` iterations; the stop
-        is taken on the device after every iteration.  RuntimeError inside a graph capture."""
+        is taken on the device after every iteration.  RuntimeError inside a graph capture.  transpose=True: M^T x = b, as enqueue."""
         import torch
         self._live()
         self._no_capture("solve", stream)
@@ -3062,21 +3199,22 @@ class StencilSystemSolver:
         check_every = int(check_every)
         if check_every < 1:
             raise ValueError("check_every must be >= 1; got %d" % check_every)
+        transpose = self._transposed(transpose, stream)
         s, dev = _stream_and_device(x, stream)
-        self._start(b, x, rtol, atol, maxiter, dev, s)
+        self._start(b, x, rtol, atol, maxiter, dev, s, transpose)
         self.x = x
         left = maxiter
         while True:
             n = min(check_every, left)
-            self._iterate(x, n, dev, s)
+            self._iterate(x, n, dev, s, transpose)
             left -= n
             info, done = self._read("solve", stream)
             if done or left == 0:
                 return info
 
-    def product(self, v, w=None, out=None, stream=None):
+    def product(self, v, w=None, out=None, stream=None, transpose=False):
         """(M v, (M v, w), (M v, M v)): the solve's own fused product and the dot products of its pass (w default v), all (npoints, m).
-        One host read of the two sums; not between an enqueue and the end of its solve."""
+        One host read of the two sums; not between an enqueue and the end of its solve.  transpose=True: M^T v."""
         import torch
         self._live()
         self._no_capture("product", stream)
@@ -3088,8 +3226,10 @@ class StencilSystemSolver:
             self._vectors(v=v, out=out)
         else:
             self._vectors(v=v, w=w, out=out)
+        transpose = self._transposed(transpose, stream)
         s, dev = _stream_and_device(v, stream)
-        B.check(B.lib().wlsqm_hip_krylov_system_product_device(*self._system(), _ptr(v), _ptr(w), _ptr(out), _ptr(self._ws), dev, s))
+        fn = B.lib().wlsqm_hip_krylov_system_product_transposed_device if transpose else B.lib().wlsqm_hip_krylov_system_product_device
+        B.check(fn(*self._system(transpose), _ptr(v), _ptr(w), _ptr(out), _ptr(self._ws), dev, s))
         with _torch_stream(stream, self._device):
             head = self._ws[:16].cpu().numpy()
         return out, float(head[6]), float(head[7])
@@ -3125,6 +3265,65 @@ class StencilSystemSolver:
         with warnings.catch_warnings():
             warnings.simplefilter("ignore", UserWarning)
             return coo.coalesce().to_sparse_csr()
+
+    def gradients(self, lam, x, values=False, diag=False, stream=None):
+        """The gradients of a loss L through the solve M x = b, from x and lam, the solution of M^T lam = dL/dx (solve(transpose=True)):
+        SystemGradients(values, diag), each None unless asked for with True or with a tensor to write into.
+          values: (nop, total) in the operator's layout: at every live entry of row j, in plane o,
+                  -sum_b (sum_a coupling[a, b, o] lam[j, a]) x[col, b], and +0.0 in the padding: dL/d(the entries of the value planes);
+                  op._unpack's layout per slot through differentiable_stencil_system_solve's `coefficients`.
+          diag:   (m, m, npoints), -(lam[i, a] * x[i, b]): dL/d(diag).
+        One kernel launch on `stream` ("krylov-system-grads": one pass over the forward structure that reads the columns and writes the
+        planes, never the values); no synchronisation, no allocation when the outputs are given.  lam and x are (npoints, m) as every
+        vector of the solver; the outputs are contiguous float64 tensors on the operator's device that overlap neither lam, x, each
+        other, the operator's values, the diag tensor nor the workspace."""
+        import torch
+        m = self._live()
+        total = int(m["total"])
+        asked = lambda flag: flag is not None and flag is not False
+        if not (asked(values) or asked(diag)):
+            raise ValueError("gradients: neither values nor diag is asked for")
+        f64 = dict(dtype=torch.float64, device=self._device)
+        with _torch_stream(stream, self._device):
+            gval = torch.empty((self.nop, total), **f64) if values is True else (values if asked(values) else None)
+            gdiag = torch.empty((self.m, self.m, self.npoints), **f64) if diag is True else (diag if asked(diag) else None)
+        named = dict(lam=lam, x=x)
+        self._vectors(**named)
+        others = dict(named, workspace=self._ws, **{"the operator's values": self._op._val})
+        if hasattr(self.diag, "dim"):
+            others["diag"] = self.diag
+        for t, name, shape, says in ((gval, "values", (self.nop, total), "the operator's layout"),
+                                     (gdiag, "diag", (self.m, self.m, self.npoints), "the diag tensor's")):
+            if t is None:
+                continue
+            if not hasattr(t, "dim") or not hasattr(t, "is_cuda"):
+                raise ValueError("argument %s must be True, False or a device (HIP) tensor" % name)
+            _check(t, name, "float64", len(shape))
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous float64 device tensor of shape %s, %s; got shape %s with strides %s"
+                                 % (name, shape, says, tuple(t.shape), tuple(t.stride())))
+            _same_device(self._ws, t)
+            for other, held in others.items():
+                if _overlap(t, held):
+                    raise ValueError("%s overlaps %s in memory" % ("grad_diag" if name == "diag" else name, other))
+            others["grad_diag" if name == "diag" else name] = t
+        s, dev = _stream_and_device(x, stream)
+        B.check(B.lib().wlsqm_hip_krylov_system_grads_device(
+            m["nrows"], int(m["width"].shape[0]), _ptr(m["len"]), _ptr(m["width"]), _ptr(m["soff"]), _ptr(m["col"]), total, self.nop, self.m,
+            C.cast(self._cp, C.c_void_p), _ptr(lam), _ptr(x), _ptr(gval) if gval is not None and total else None, _ptr(gdiag), dev, s))
+        return SystemGradients(gval, gdiag)
+
+    def coupling_gradient(self, lam, x, stream=None):
+        """dL/d(coupling), a new device tensor (m, m, nop): entry (a, b, o) is -sum_i lam[i, a] (A_o x[:, b])_i.  No kernel of its own:
+        the operator's stacked product on the m columns of x (op.apply, all planes in one pass) and a contraction with lam by torch, on
+        `stream`: m elementwise products and sums over the points (a matrix product with one dimension of npoints is not what the
+        BLAS behind torch.einsum is built for: 30 to 100 ms at 10^6 points, against about 1 ms).  It allocates its result and the
+        products."""
+        import torch
+        self._vectors(lam=lam, x=x)
+        Y = self._op.apply(x.t(), stream=stream)                          # (m, nop, npoints): Y[b, o] = A_o x[:, b]
+        with _torch_stream(stream, self._device):
+            return -torch.stack([(Y * lam[:, a]).sum(dim=-1) for a in range(self.m)])
 
 
 def differentiable_stencil_solve(solver, b, x0=None, S=None, coefficients=None, rtol=1e-10, atol=0.0, maxiter=1000, check_every=8,
@@ -3197,6 +3396,60 @@ def differentiable_stencil_solve_many(solver, b, x0=None, rtol=1e-10, atol=0.0, 
     solver._no_capture("differentiable_stencil_solve_many", stream)
     return _autograd().StencilSolveMany.apply(b, x0, solver, float(rtol), float(atol), int(maxiter), int(check_every),
                                               None if adjoint_rtol is None else float(adjoint_rtol), stream)
+
+
+def differentiable_stencil_system_solve(solver, b, x0=None, S=None, coefficients=None, coupling=None, rtol=1e-10, atol=0.0, maxiter=1000,
+                                        check_every=8, adjoint_rtol=None, stream=None):
+    """x (npoints, m), the solution of the coupled M x = b by solver.solve (a StencilSystemSolver), as a differentiable function of b,
+    of solver.diag when that is a tensor, of `coupling` and of what the operator is made from: differentiable_stencil_solve's contract
+    carried over to m fields.
+
+    S: the point table; the forward runs op.update(S.detach()) first (RuntimeError for an operator without a fit), and S receives dL/dS
+    at fixed neighbour lists.  coefficients=(slots, own) as StencilOperator.set_coefficients takes them, all nop planes: written into
+    the operator first, and they receive the gradients of every plane's entries, exact zeros in the padding.  Both: ValueError.
+    coupling: a float64 torch tensor (m, m, nop), on the host or on the device; the forward writes it into the solver
+    (solver.set_coupling), and it receives its gradient on its own device.  Without it the solver's table is read as it is, in both
+    passes.  With S, coefficients or coupling the backward pass first puts the operator and the table back where the forward had them,
+    so that the steps of a loop may share one operator and one solver.
+
+    The forward solves from x0 (default zeros; no gradient) to rtol / atol within maxiter iterations; a status other than 0 is a
+    RuntimeError that quotes the SolveInfo.  The backward pass solves M^T lam = dL/dx from zero (solve(transpose=True), relative
+    tolerance `adjoint_rtol or rtol`, atol 0; RuntimeError when it does not converge), then: b gets lam; diag and the coefficients get
+    StencilSystemSolver.gradients; coupling gets coupling_gradient; S gets the geometry adjoint of the fits of F = x[:, b], summed over
+    the components.  Only what requires a gradient is computed, and nothing is launched when nothing does.  Not capturable (RuntimeError
+    inside a graph capture).  Once differentiable."""
+    if not isinstance(solver, StencilSystemSolver):
+        raise ValueError("solver must be a StencilSystemSolver")
+    solver._live()
+    op = solver._op
+    if S is not None and coefficients is not None:
+        raise ValueError("S and coefficients are two ways to make the operator: pass one of them")
+    slots = own = None
+    if coefficients is not None:
+        if not isinstance(coefficients, (tuple, list)) or len(coefficients) != 2:
+            raise ValueError("coefficients must be (slots, own), own None for an operator without own entries")
+        slots, own = coefficients
+        if slots is None:
+            raise ValueError("coefficients must be (slots, own), own None for an operator without own entries")
+    if S is not None and getattr(op, "_geo", None) is None:
+        raise RuntimeError("the stencil operator was made from coefficients: there is no fit to redo")
+    if coupling is not None:
+        if not hasattr(coupling, "dim") or not hasattr(coupling, "is_cuda") or not hasattr(coupling, "requires_grad"):
+            raise ValueError("coupling must be a float64 torch tensor (m, m, nop), on the host or on the device")
+        if str(coupling.dtype) != "torch.float64" or tuple(coupling.shape) != (solver.m, solver.m, solver.nop):
+            raise ValueError("coupling must be a float64 torch tensor of shape (%d, %d, %d); got %s of shape %s"
+                             % (solver.m, solver.m, solver.nop, coupling.dtype, tuple(coupling.shape)))
+    named = dict(b=b) if x0 is None else dict(b=b, x0=x0)
+    solver._vectors(**named)                         # before anything is detached or cloned
+    solver._tolerances(rtol, atol, maxiter)
+    if adjoint_rtol is not None:
+        solver._tolerances(adjoint_rtol, atol, maxiter)
+    if int(check_every) < 1:
+        raise ValueError("check_every must be >= 1; got %d" % int(check_every))
+    solver._no_capture("differentiable_stencil_system_solve", stream)
+    diag = solver.diag if hasattr(solver.diag, "dim") else None
+    return _autograd().StencilSystemSolve.apply(b, diag, S, slots, own, coupling, x0, solver, float(rtol), float(atol), int(maxiter),
+                                                int(check_every), None if adjoint_rtol is None else float(adjoint_rtol), stream)
 
 
 # ---- batched dense solves (the kernels behind wlsqm.utils.lapackdrivers), device-resident ----
