@@ -846,6 +846,36 @@ int wlsqm_hip_krylov_system_grads_device(int64_t npoints, int64_t nslices, const
                                          const int32_t* col, int64_t total, int nop, int m, const double* coupling, const double* lam,
                                          const double* x, double* grad_val, double* grad_diag, int device, void* stream);
 
+/* ---- coupled fields: a per-point coupling (extension; csrc/krylov.hip) ----
+ * The calls above with `coupling` a DEVICE tensor (m, m, nop, npoints), plane-major like the diag tensor, read on the stream by every call:
+ *   M[(i, a), (j, b)] = D_ab,i * delta_ij + sum_o coupling[a][b][o][i] * A_o[i, j]
+ * (the equation of point i carries its own coefficients).  The order of operations differs from the constant table's and is stated at
+ * the head of that part of csrc/krylov.hip.  transposed == 0: len .. val are the forward arrays and `mixed` is not looked at
+ * ("krylov-system-diag-point", "krylov-system-spmv-point"; 4 launches for a start, 8 per iteration, 2 for a product).
+ * transposed != 0: M^T; len .. val are the arrays of the TRANSPOSED planes, coupling, diag and diag_const the forward system's own, and
+ * `mixed` is a device plane of nop * m * npoints doubles, 16-byte aligned, that "krylov-system-mix" writes in front of every product of
+ * "krylov-system-spmv-mixed" (5 launches for a start, 10 per iteration, 3 for a product).  Workspace, scalars, statuses, alignment
+ * and WLSQM_EVALUE are those of the calls above.  wlsqm_hip_krylov_system_point_grads_device is wlsqm_hip_krylov_system_grads_device
+ * with sum_a coupling[a][b][o][j] lam[j][a] for row j. */
+int wlsqm_hip_krylov_system_point_start_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                               const int32_t* col, const double* val, int64_t total, int nop, int m, const double* coupling,
+                                               const double* diag, const double* diag_const, int transposed, double* mixed, int jacobi,
+                                               const double* b, const double* x, double rtol, double atol, int64_t maxiter, void* workspace,
+                                               int device, void* stream);
+int wlsqm_hip_krylov_system_point_bicgstab_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                  const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                                                  const double* coupling, const double* diag, const double* diag_const, int transposed,
+                                                  double* mixed, int jacobi, double* x, int64_t niter, void* workspace, int device,
+                                                  void* stream);
+int wlsqm_hip_krylov_system_point_product_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                 const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                                                 const double* coupling, const double* diag, const double* diag_const, int transposed,
+                                                 double* mixed, const double* in, const double* w, double* out, void* workspace, int device,
+                                                 void* stream);
+int wlsqm_hip_krylov_system_point_grads_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                               const int32_t* col, int64_t total, int nop, int m, const double* coupling, const double* lam,
+                                               const double* x, double* grad_val, double* grad_diag, int device, void* stream);
+
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ---- */
 /* Runs `reps` back-to-back launches of the fit kernel for batch `b` (device-resident, uniform
  * order) on `stream`, bracketed by HIP events on that stream; returns the mean kernel time in

@@ -1670,6 +1670,7 @@ struct KrylovCoupled {
     int dswap;                                                   // M^T: dten is read at [(b * m + a) * npoints + i] (the host tables come exchanged)
     double dconst[KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS];
     double coupling[KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_PLANES];   // [(a * m + b) * nop + o]
+    const double* cpt;                                           // a per-point table (section 26): [((a * m + b) * nop + o) * npoints + i], else null
 };
 
 // The m unknowns of one point of an interleaved vector.
@@ -1837,6 +1838,7 @@ __global__ void __launch_bounds__(256) krylov_system_diag_kernel(const KrylovCou
 //           lanes of rows beyond npoints included; their padding col is never loaded, and val is never loaded at all
 //   DIAG (m, m, npoints): gdiag[(a * m + b) * npoints + j] = -(lam[j][a] * x[j][b]), one rounding
 // Each output is a template flag: a pass without VALUES never stores into a plane.  No atomics, no scratch, no workspace.
+// POINT: c[a][b][o] is the row's own, q.cpt[((a * m + b) * nop + o) * npoints + j], one coalesced run per (a, b, o).
 template <int M, int NOP>
 __device__ __forceinline__ void krylov_system_grads_entry(const double (&u)[M][NOP], const double (&xs)[M], double* out, long long total) {
 #pragma unroll
@@ -1848,7 +1850,7 @@ __device__ __forceinline__ void krylov_system_grads_entry(const double (&u)[M][N
     }
 }
 
-template <int M, int NOP, bool VALUES, bool DIAG>
+template <int M, int NOP, bool VALUES, bool DIAG, bool POINT = false>
 __global__ void __launch_bounds__(256) krylov_system_grads_kernel(const KrylovCoupled q, const double* lam, const double* x, double* gval,
                                                                   double* gdiag) {
     const int lane = threadIdx.x & 63;
@@ -1882,9 +1884,17 @@ __global__ void __launch_bounds__(256) krylov_system_grads_kernel(const KrylovCo
         for (int b = 0; b < M; ++b) {
 #pragma unroll
             for (int o = 0; o < NOP; ++o) {
-                double t = q.coupling[b * NOP + o] * lj[0];
+                double t;
+                if constexpr (POINT) {                           // a lane beyond npoints has lam = 0 and stores only padding zeros
+                    const double* cp = q.cpt + (live ? row : 0);
+                    t = cp[(b * NOP + o) * q.npoints] * lj[0];
 #pragma unroll
-                for (int a = 1; a < M; ++a) t = __builtin_fma(q.coupling[(a * M + b) * NOP + o], lj[a], t);
+                    for (int a = 1; a < M; ++a) t = __builtin_fma(cp[((a * M + b) * NOP + o) * q.npoints], lj[a], t);
+                } else {
+                    t = q.coupling[b * NOP + o] * lj[0];
+#pragma unroll
+                    for (int a = 1; a < M; ++a) t = __builtin_fma(q.coupling[(a * M + b) * NOP + o], lj[a], t);
+                }
                 u[b][o] = t;
             }
         }
@@ -1918,7 +1928,10 @@ __global__ void __launch_bounds__(256) krylov_system_grads_kernel(const KrylovCo
 template <int M, int NOP>
 static void krylov_system_grads_run(const KrylovCoupled& q, const double* lam, const double* x, double* gval, double* gdiag, hipStream_t s) {
     const dim3 grid((unsigned)((q.npoints + 255) / 256)), block(256);
-    if (gdiag) hipLaunchKernelGGL((krylov_system_grads_kernel<M, NOP, true, true>), grid, block, 0, s, q, lam, x, gval, gdiag);
+    if (q.cpt) {
+        if (gdiag) hipLaunchKernelGGL((krylov_system_grads_kernel<M, NOP, true, true, true>), grid, block, 0, s, q, lam, x, gval, gdiag);
+        else hipLaunchKernelGGL((krylov_system_grads_kernel<M, NOP, true, false, true>), grid, block, 0, s, q, lam, x, gval, gdiag);
+    } else if (gdiag) hipLaunchKernelGGL((krylov_system_grads_kernel<M, NOP, true, true>), grid, block, 0, s, q, lam, x, gval, gdiag);
     else hipLaunchKernelGGL((krylov_system_grads_kernel<M, NOP, true, false>), grid, block, 0, s, q, lam, x, gval, gdiag);
 }
 
@@ -2029,7 +2042,7 @@ static int krylov_system_call(const char* who, KrylovSystemCall& c, int64_t npoi
     KrylovCoupled& q = c.q;
     q.npoints = npoints; q.total = total;
     q.len = len; q.width = width; q.soff = reinterpret_cast<const long long*>(soff);
-    q.col = col; q.val = val; q.dten = diag; q.dswap = transposed ? 1 : 0;
+    q.col = col; q.val = val; q.dten = diag; q.dswap = transposed ? 1 : 0; q.cpt = nullptr;
     for (int i = 0; i < KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS; ++i) q.dconst[i] = (!diag && i < m * m) ? diag_const[i] : 0.0;
     for (int i = 0; i < KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_PLANES; ++i) q.coupling[i] = i < m * m * nop ? coupling[i] : 0.0;
     if (transposed) {                                           // block (a, b) of M^T takes D_ba and coupling[b][a][:]
@@ -2051,6 +2064,422 @@ static int krylov_system_call(const char* who, KrylovSystemCall& c, int64_t npoi
     default: krylov_system_planes<4>(nop, c); break;
     }
     WLSQM_HIP_CHECK(hipGetLastError());
+    return WLSQM_OK;
+}
+
+// ---- a per-point coupling: M[(i, a), (j, b)] = D_ab,i delta_ij + sum_o c[a][b][o][i] A_o[i, j] ----------------------
+// c is a device tensor (m, m, nop, npoints), plane-major like the diag tensor: the equation of point i carries its own coefficients.
+// m^2 nop coefficients per lane do not fit registers beside the product, so the order of operations is not section 24's; it is the one
+// that tests/_krylov_system_point_ref.py states in numpy.
+// Forward (krylov-system-spmv-point), section 24's mapping, nop m accumulators per lane:
+//   per stored entry, in entry order:  s[o][b] = fma(val_o, x_b, s[o][b]), x the unknowns of the entry's column   (s = A_o x_b, row i)
+//   at the end of the row:  t_a = c[a][0][0][i] * s[0][0], then t_a = fma(c[a][b][o][i], s[o][b], t_a), b outer and o inner, (0, 0) left out
+//   y_a = t_a + s_a, s_a the diag part exactly as in section 24
+// Each coefficient is one coalesced 512-byte run per (a, b, o), used once and dropped.
+// Transposed: (M^T lam)_b(j) = (D^T lam)_b(j) + sum_o sum_i A_o^T[j, i] z[i][o][b], the coefficients applied at their own point:
+//   krylov-system-mix, one lane per point:  z[i][o][b] = c[0][b][o][i] * lam_0, then fma(c[a][b][o][i], lam_a, .) for a = 1 .. m - 1,
+//     written as (npoints, nop, m)
+//   krylov-system-spmv-mixed on the operator's transposed arrays, m accumulators: per stored entry of row j, in entry order, o ascending,
+//     acc_b = fma(valT_o, z[col][o][b], acc_b); y_b = acc_b + s_b, s_b = D_0b lam_0, then fma(D_ab, lam_a, s_b): dten at the exchanged index
+// No coefficient is gathered.  The epilogues, block_sums and the partial counts are section 24's.
+
+// The end of a row of either product: y = t + (the diag part), then the epilogue that `mode` names (krylov_system_spmv_kernel's).
+template <int M>
+__device__ __forceinline__ void krylov_system_finish(const KrylovCoupled& q, int mode, const double* in, const double* w, double* out, double* out2,
+                                                     long long row, const double (&t)[M], double& pa, double& pb) {
+    double xi[M], y[M], wi[M];
+    krylov_load_point<M>(in + row * M, xi);
+    krylov_load_point<M>(w + row * M, wi);
+#pragma unroll
+    for (int a = 0; a < M; ++a) {
+        double sa = 0.0;
+#pragma unroll
+        for (int b = 0; b < M; ++b) {
+            const double d = q.dten ? q.dten[(q.dswap ? b * M + a : a * M + b) * q.npoints + row] : q.dconst[a * M + b];
+            sa = b == 0 ? d * xi[0] : __builtin_fma(d, xi[b], sa);
+        }
+        y[a] = t[a] + sa;
+    }
+    if (mode == SYSTEM_RESIDUAL) {
+#pragma unroll
+        for (int a = 0; a < M; ++a) {
+            const double r = wi[a] - y[a];
+            out[row * M + a] = r; out2[row * M + a] = r;
+            pa += r * r; pb += wi[a] * wi[a];
+        }
+    } else {
+#pragma unroll
+        for (int a = 0; a < M; ++a) {
+            out[row * M + a] = y[a];
+            pa += wi[a] * y[a]; pb += y[a] * y[a];
+        }
+    }
+}
+
+template <int M, int NOP>
+__device__ __forceinline__ void krylov_point_entry(const double (&vs)[NOP], const double (&xs)[M], double (&s)[NOP][M]) {
+#pragma unroll
+    for (int o = 0; o < NOP; ++o) {
+#pragma unroll
+        for (int b = 0; b < M; ++b) s[o][b] = __builtin_fma(vs[o], xs[b], s[o][b]);
+    }
+}
+
+template <int M, int NOP>
+__global__ void __launch_bounds__(256) krylov_system_spmv_point_kernel(const KrylovCoupled q, int mode, const double* in, const double* w, double* out,
+                                                                       double* out2, double* partial, const KrylovScalars* sc) {
+    if (mode != SYSTEM_PRODUCT && sc->done) return;              // uniform: the whole grid
+    constexpr int UNROLL = M * NOP > 16 ? 2 : 4;
+    const int lane = threadIdx.x & 63;
+    const long long sl = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long row = sl * 64 + lane;
+    double pa = 0.0, pb = 0.0;
+    if (sl * 64 < q.npoints) {                                   // wave-uniform
+        const int wid = __builtin_amdgcn_readfirstlane(q.width[sl]);
+        const long long at = q.soff[sl] + lane;
+        int n = row < q.npoints ? q.len[row] : 0;
+        n = n < wid ? n : wid;
+        const int32_t* col = q.col + at;
+        const double* val = q.val + at;
+        double s[NOP][M];
+#pragma unroll
+        for (int o = 0; o < NOP; ++o) {
+#pragma unroll
+            for (int b = 0; b < M; ++b) s[o][b] = 0.0;
+        }
+        for (int e = 0; e < wid; e += UNROLL) {                  // wave-uniform
+            if (e + UNROLL <= n) {
+                double xs[UNROLL][M], vs[UNROLL][NOP];
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) {
+                    const long long c = col[64LL * (e + u)];
+                    krylov_load_point<M>(in + c * M, xs[u]);
+#pragma unroll
+                    for (int o = 0; o < NOP; ++o) vs[u][o] = val[o * q.total + 64LL * (e + u)];
+                }
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) krylov_point_entry<M, NOP>(vs[u], xs[u], s);
+            } else {
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) {
+                    if (e + u < n) {
+                        const long long c = col[64LL * (e + u)];
+                        double xs[M], vs[NOP];
+                        krylov_load_point<M>(in + c * M, xs);
+#pragma unroll
+                        for (int o = 0; o < NOP; ++o) vs[o] = val[o * q.total + 64LL * (e + u)];
+                        krylov_point_entry<M, NOP>(vs, xs, s);
+                    }
+                }
+            }
+        }
+        if (row < q.npoints) {
+            const double* cp = q.cpt + row;
+            double t[M];
+#pragma unroll
+            for (int a = 0; a < M; ++a) {
+                t[a] = cp[(long long)(a * M * NOP) * q.npoints] * s[0][0];
+#pragma unroll
+                for (int b = 0; b < M; ++b) {
+#pragma unroll
+                    for (int o = 0; o < NOP; ++o) {
+                        if (b + o > 0) t[a] = __builtin_fma(cp[(long long)((a * M + b) * NOP + o) * q.npoints], s[o][b], t[a]);
+                    }
+                }
+            }
+            krylov_system_finish<M>(q, mode, in, w, out, out2, row, t, pa, pb);
+        }
+    }
+    block_sums<true>(pa, pb, partial, gridDim.x);
+}
+
+// dinv[i * m + a] = 1 / (D_aa,i + sum_o c[a][a][o][i] own_o): krylov_system_diag_kernel's sums and count with the point's own coefficients.
+// On the transposed arrays the own entries of row i are the same numbers, so M^T takes the same kernel there.
+template <int M, int NOP>
+__global__ void __launch_bounds__(256) krylov_system_diag_point_kernel(const KrylovCoupled q, double* dinv, double* partial) {
+    const int lane = threadIdx.x & 63;
+    const long long sl = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long row = sl * 64 + lane;
+    double bad = 0.0;
+    if (sl * 64 < q.npoints) {                                   // wave-uniform
+        const int wid = __builtin_amdgcn_readfirstlane(q.width[sl]);
+        const long long at = q.soff[sl] + lane;
+        int n = row < q.npoints ? q.len[row] : 0;
+        n = n < wid ? n : wid;
+        double own[NOP];
+#pragma unroll
+        for (int o = 0; o < NOP; ++o) own[o] = 0.0;
+        for (int e = 0; e < wid; ++e) {                          // wave-uniform
+            if (e < n && q.col[at + 64LL * e] == row) {
+#pragma unroll
+                for (int o = 0; o < NOP; ++o) own[o] += q.val[o * q.total + at + 64LL * e];
+            }
+        }
+        if (row < q.npoints) {
+            const double* cp = q.cpt + row;
+            bool unusable = false;
+#pragma unroll
+            for (int a = 0; a < M; ++a) {
+                double t = cp[(long long)((a * M + a) * NOP) * q.npoints] * own[0];
+#pragma unroll
+                for (int o = 1; o < NOP; ++o) t = t + cp[(long long)((a * M + a) * NOP + o) * q.npoints] * own[o];
+                const double diag = (q.dten ? q.dten[(a * M + a) * q.npoints + row] : q.dconst[a * M + a]) + t;
+                const bool ok = diag != 0.0 && __builtin_isfinite(diag);
+                dinv[row * M + a] = ok ? 1.0 / diag : 0.0;
+                unusable = unusable || !ok;
+            }
+            bad = unusable ? 1.0 : 0.0;
+        }
+    }
+    block_sums<false>(bad, 0.0, partial, gridDim.x);
+}
+
+// z[i][o][b] = sum_a c[a][b][o][i] in[i][a]: pointwise, every coefficient one coalesced run.
+template <int M, int NOP>
+__global__ void __launch_bounds__(256) krylov_system_mix_kernel(const KrylovCoupled q, int mode, const double* in, double* z, const KrylovScalars* sc) {
+    if (mode != SYSTEM_PRODUCT && sc->done) return;              // uniform: the whole grid
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= q.npoints) return;
+    double li[M];
+    krylov_load_point<M>(in + i * M, li);
+    const double* cp = q.cpt + i;
+    double* zi = z + i * (NOP * M);
+#pragma unroll
+    for (int o = 0; o < NOP; ++o) {
+#pragma unroll
+        for (int b = 0; b < M; ++b) {
+            double t = cp[(long long)(b * NOP + o) * q.npoints] * li[0];
+#pragma unroll
+            for (int a = 1; a < M; ++a) t = __builtin_fma(cp[(long long)((a * M + b) * NOP + o) * q.npoints], li[a], t);
+            zi[o * M + b] = t;
+        }
+    }
+}
+
+template <int M, int NOP>
+__device__ __forceinline__ void krylov_mixed_entry(const double (&vs)[NOP], const double (&zs)[NOP * M], double (&acc)[M]) {
+#pragma unroll
+    for (int o = 0; o < NOP; ++o) {
+#pragma unroll
+        for (int b = 0; b < M; ++b) acc[b] = __builtin_fma(vs[o], zs[o * M + b], acc[b]);
+    }
+}
+
+// y = M^T in from z = mix(in): q holds the operator's transposed arrays and dswap = 1.
+template <int M, int NOP>
+__global__ void __launch_bounds__(256) krylov_system_spmv_mixed_kernel(const KrylovCoupled q, int mode, const double* in, const double* z,
+                                                                       const double* w, double* out, double* out2, double* partial,
+                                                                       const KrylovScalars* sc) {
+    if (mode != SYSTEM_PRODUCT && sc->done) return;              // uniform: the whole grid
+    constexpr int UNROLL = M * NOP > 16 ? 2 : 4;
+    const int lane = threadIdx.x & 63;
+    const long long sl = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long row = sl * 64 + lane;
+    double pa = 0.0, pb = 0.0;
+    if (sl * 64 < q.npoints) {                                   // wave-uniform
+        const int wid = __builtin_amdgcn_readfirstlane(q.width[sl]);
+        const long long at = q.soff[sl] + lane;
+        int n = row < q.npoints ? q.len[row] : 0;
+        n = n < wid ? n : wid;
+        const int32_t* col = q.col + at;
+        const double* val = q.val + at;
+        double acc[M];
+#pragma unroll
+        for (int b = 0; b < M; ++b) acc[b] = 0.0;
+        for (int e = 0; e < wid; e += UNROLL) {                  // wave-uniform
+            if (e + UNROLL <= n) {
+                double zs[UNROLL][NOP * M], vs[UNROLL][NOP];
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) {
+                    const long long c = col[64LL * (e + u)];
+                    krylov_load_point<NOP * M>(z + c * (NOP * M), zs[u]);
+#pragma unroll
+                    for (int o = 0; o < NOP; ++o) vs[u][o] = val[o * q.total + 64LL * (e + u)];
+                }
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) krylov_mixed_entry<M, NOP>(vs[u], zs[u], acc);
+            } else {
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) {
+                    if (e + u < n) {
+                        const long long c = col[64LL * (e + u)];
+                        double zs[NOP * M], vs[NOP];
+                        krylov_load_point<NOP * M>(z + c * (NOP * M), zs);
+#pragma unroll
+                        for (int o = 0; o < NOP; ++o) vs[o] = val[o * q.total + 64LL * (e + u)];
+                        krylov_mixed_entry<M, NOP>(vs, zs, acc);
+                    }
+                }
+            }
+        }
+        if (row < q.npoints) krylov_system_finish<M>(q, mode, in, w, out, out2, row, acc, pa, pb);
+    }
+    block_sums<true>(pa, pb, partial, gridDim.x);
+}
+
+struct KrylovPointCall {
+    KrylovSystemCall c;
+    double* mixed;                                              // z, nop m npoints doubles: the transposed calls only
+};
+
+template <int M, int NOP>
+static void krylov_point_product(const KrylovPointCall& p, int mode, const double* in, const double* w, double* out, double* out2) {
+    const KrylovSystemCall& c = p.c;
+    const dim3 pgrid((unsigned)((c.q.npoints + 255) / 256)), block(256);
+    if (c.q.dswap) {
+        hipLaunchKernelGGL((krylov_system_mix_kernel<M, NOP>), pgrid, block, 0, c.s, c.q, mode, in, p.mixed, (const KrylovScalars*)c.w.sc);
+        hipLaunchKernelGGL((krylov_system_spmv_mixed_kernel<M, NOP>), pgrid, block, 0, c.s, c.q, mode, in, (const double*)p.mixed, w, out, out2,
+                           c.w.partial, (const KrylovScalars*)c.w.sc);
+    } else {
+        hipLaunchKernelGGL((krylov_system_spmv_point_kernel<M, NOP>), pgrid, block, 0, c.s, c.q, mode, in, w, out, out2, c.w.partial,
+                           (const KrylovScalars*)c.w.sc);
+    }
+}
+
+// krylov_system_run's launch lists with the per-point products: 8 launches per forward iteration, 10 per transposed one.
+template <int M, int NOP>
+static void krylov_point_run(const KrylovPointCall& p) {
+    const KrylovSystemCall& c = p.c;
+    const KrylovWork& w = c.w;
+    const long long nwgp = (c.q.npoints + 255) / 256, nrows = c.q.npoints * M;
+    const dim3 pgrid((unsigned)nwgp), ugrid((unsigned)w.nwg), block(256);
+    const KrylovScalars* sc = w.sc;
+    hipStream_t s = c.s;
+    double* const none = nullptr;
+    const char* product = c.q.dswap ? "krylov-system-spmv-mixed" : "krylov-system-spmv-point";
+    if (c.what == SYSTEM_CALL_START) {
+        if (c.jacobi) {
+            hipLaunchKernelGGL((krylov_system_diag_point_kernel<M, NOP>), pgrid, block, 0, s, c.q, w.dinv, w.partial);
+            note_kernel("krylov-system-diag-point");
+        }
+        krylov_reduce(REDUCE_DIAG, w, c.jacobi ? nwgp : 0, 1, c.rtol, c.atol, c.maxiter, s);
+        krylov_point_product<M, NOP>(p, SYSTEM_RESIDUAL, c.in, c.other, w.r, w.r0);
+        note_kernel(product);
+        krylov_reduce(REDUCE_RESIDUAL, w, nwgp, 2, c.rtol, c.atol, c.maxiter, s);
+        note_kernel("krylov-reduce");
+    } else if (c.what == SYSTEM_CALL_ITERATE) {
+        for (int64_t it = 0; it < c.niter; ++it) {
+            hipLaunchKernelGGL((krylov_update_kernel<UPDATE_P>), ugrid, block, 0, s, nrows, w, c.x, sc);
+            krylov_point_product<M, NOP>(p, SYSTEM_V, w.phat, w.r0, w.v, none);
+            krylov_reduce(REDUCE_ALPHA, w, nwgp, 1, 0.0, 0.0, 0, s);
+            hipLaunchKernelGGL((krylov_update_kernel<UPDATE_S>), ugrid, block, 0, s, nrows, w, c.x, sc);
+            krylov_point_product<M, NOP>(p, SYSTEM_T, w.shat, w.s, w.t, none);
+            krylov_reduce(REDUCE_OMEGA, w, nwgp, 2, 0.0, 0.0, 0, s);
+            hipLaunchKernelGGL((krylov_update_kernel<UPDATE_X>), ugrid, block, 0, s, nrows, w, c.x, sc);
+            krylov_reduce(REDUCE_RHO, w, w.nwg, 2, 0.0, 0.0, 0, s);
+        }
+        note_kernel("krylov-update");
+    } else {
+        krylov_point_product<M, NOP>(p, SYSTEM_PRODUCT, c.in, c.other, c.x, none);
+        krylov_reduce(REDUCE_PRODUCT, w, nwgp, 2, 0.0, 0.0, 0, s);
+        note_kernel(product);
+    }
+}
+
+template <int M>
+static void krylov_point_planes(int nop, const KrylovPointCall& p) {
+    switch (nop) {
+    case 1: krylov_point_run<M, 1>(p); break;
+    case 2: krylov_point_run<M, 2>(p); break;
+    case 3: krylov_point_run<M, 3>(p); break;
+    case 4: krylov_point_run<M, 4>(p); break;
+    case 5: krylov_point_run<M, 5>(p); break;
+    case 6: krylov_point_run<M, 6>(p); break;
+    case 7: krylov_point_run<M, 7>(p); break;
+    default: krylov_point_run<M, 8>(p); break;
+    }
+}
+
+// krylov_system_call for a per-point table: its checks, then those of the tensor and of z, then the call's launches.
+static int krylov_point_call(const char* who, KrylovPointCall& p, int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                             const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                             const double* coupling, const double* diag, const double* diag_const, int transposed, void* workspace,
+                             int device) {
+    const std::string name(who);
+    KrylovSystemCall& c = p.c;
+    if (m < 1 || m > KRYLOV_SYSTEM_FIELDS) { set_error(name + ": m must be 1 .. 4"); return WLSQM_EVALUE; }
+    if (nop < 1 || nop > KRYLOV_SYSTEM_PLANES) { set_error(name + ": nop must be 1 .. 8"); return WLSQM_EVALUE; }
+    if (npoints < 1 || nslices < 0 || npoints > 64 * nslices || total < 0 || (npoints * m + 255) / 256 > 0x7fffffffLL) {
+        set_error(name + ": npoints must be 1 .. 64 * nslices");
+        return WLSQM_EVALUE;
+    }
+    if (!len || !width || !soff || !col || !val || !coupling || !workspace || (!diag && !diag_const) || !c.in || !c.other || !c.x
+        || (transposed && !p.mixed)) {
+        set_error(name + ": null array");
+        return WLSQM_EVALUE;
+    }
+    if (m % 2 == 0 && (((uintptr_t)c.in | (uintptr_t)c.other | (uintptr_t)c.x | (uintptr_t)workspace) & 15)) {
+        set_error(name + ": with m = 2 or 4 the vectors and the workspace must be 16-byte aligned");
+        return WLSQM_EVALUE;
+    }
+    if (((uintptr_t)coupling & 7) || (transposed && ((uintptr_t)p.mixed & 15))) {
+        set_error(name + ": coupling must be 8-byte aligned and the mixed plane 16-byte aligned");
+        return WLSQM_EVALUE;
+    }
+    KrylovCoupled& q = c.q;
+    q.npoints = npoints; q.total = total;
+    q.len = len; q.width = width; q.soff = reinterpret_cast<const long long*>(soff);
+    q.col = col; q.val = val; q.dten = diag; q.dswap = transposed ? 1 : 0; q.cpt = coupling;
+    for (int i = 0; i < KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS; ++i) q.dconst[i] = 0.0;
+    for (int a = 0; a < m && !diag; ++a) {                      // block (a, b) of M^T takes D_ba
+        for (int b = 0; b < m; ++b) q.dconst[a * m + b] = transposed ? diag_const[b * m + a] : diag_const[a * m + b];
+    }
+    for (int i = 0; i < KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_PLANES; ++i) q.coupling[i] = 0.0;
+    DeviceScope scope;
+    const int rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    c.w = krylov_work(workspace, npoints * m, c.jacobi != 0);
+    switch (m) {
+    case 1: krylov_point_planes<1>(nop, p); break;
+    case 2: krylov_point_planes<2>(nop, p); break;
+    case 3: krylov_point_planes<3>(nop, p); break;
+    default: krylov_point_planes<4>(nop, p); break;
+    }
+    WLSQM_HIP_CHECK(hipGetLastError());
+    return WLSQM_OK;
+}
+
+// wlsqm_hip_krylov_system_grads_device and its per-point form: `coupling` is the host table, or the device tensor when `point`.
+static int krylov_system_grads_call(const char* who, bool point, int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                    const int64_t* soff, const int32_t* col, int64_t total, int nop, int m, const double* coupling,
+                                    const double* lam, const double* x, double* grad_val, double* grad_diag, int device, void* stream) {
+    const std::string name(who);
+    if (m < 1 || m > KRYLOV_SYSTEM_FIELDS) { set_error(name + ": m must be 1 .. 4"); return WLSQM_EVALUE; }
+    if (nop < 1 || nop > KRYLOV_SYSTEM_PLANES) { set_error(name + ": nop must be 1 .. 8"); return WLSQM_EVALUE; }
+    if (npoints < 1 || nslices < 0 || npoints > 64 * nslices || total < 0 || (npoints + 255) / 256 > 0x7fffffffLL) {
+        set_error(name + ": npoints must be 1 .. 64 * nslices");
+        return WLSQM_EVALUE;
+    }
+    if (!len || !width || !soff || !col || !coupling || !lam || !x) { set_error(name + ": null array"); return WLSQM_EVALUE; }
+    if (total == 0) grad_val = nullptr;                          // no stored entry: nothing to write
+    if (!grad_val && !grad_diag) {
+        if (total == 0) return WLSQM_OK;
+        set_error(name + ": no output is asked for");
+        return WLSQM_EVALUE;
+    }
+    if (m % 2 == 0 && (((uintptr_t)lam | (uintptr_t)x) & 15)) {
+        set_error(name + ": with m = 2 or 4 lam and x must be 16-byte aligned");
+        return WLSQM_EVALUE;
+    }
+    if (point && ((uintptr_t)coupling & 7)) { set_error(name + ": coupling must be 8-byte aligned"); return WLSQM_EVALUE; }
+    KrylovCoupled q;
+    q.npoints = npoints; q.total = total;
+    q.len = len; q.width = width; q.soff = reinterpret_cast<const long long*>(soff);
+    q.col = col; q.val = nullptr; q.dten = nullptr; q.dswap = 0; q.cpt = point ? coupling : nullptr;
+    for (int i = 0; i < KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS; ++i) q.dconst[i] = 0.0;
+    for (int i = 0; i < KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_PLANES; ++i) q.coupling[i] = (!point && i < m * m * nop) ? coupling[i] : 0.0;
+    DeviceScope scope;
+    const int rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    switch (m) {
+    case 1: krylov_system_grads_planes<1>(nop, q, lam, x, grad_val, grad_diag, s); break;
+    case 2: krylov_system_grads_planes<2>(nop, q, lam, x, grad_val, grad_diag, s); break;
+    case 3: krylov_system_grads_planes<3>(nop, q, lam, x, grad_val, grad_diag, s); break;
+    default: krylov_system_grads_planes<4>(nop, q, lam, x, grad_val, grad_diag, s); break;
+    }
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-system-grads");
     return WLSQM_OK;
 }
 
@@ -2665,43 +3094,65 @@ int wlsqm_hip_krylov_system_product_transposed_device(int64_t npoints, int64_t n
 int wlsqm_hip_krylov_system_grads_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
                                          const int32_t* col, int64_t total, int nop, int m, const double* coupling, const double* lam,
                                          const double* x, double* grad_val, double* grad_diag, int device, void* stream) {
-    const std::string name("krylov_system_grads");
-    if (m < 1 || m > KRYLOV_SYSTEM_FIELDS) { set_error(name + ": m must be 1 .. 4"); return WLSQM_EVALUE; }
-    if (nop < 1 || nop > KRYLOV_SYSTEM_PLANES) { set_error(name + ": nop must be 1 .. 8"); return WLSQM_EVALUE; }
-    if (npoints < 1 || nslices < 0 || npoints > 64 * nslices || total < 0 || (npoints + 255) / 256 > 0x7fffffffLL) {
-        set_error(name + ": npoints must be 1 .. 64 * nslices");
-        return WLSQM_EVALUE;
-    }
-    if (!len || !width || !soff || !col || !coupling || !lam || !x) { set_error(name + ": null array"); return WLSQM_EVALUE; }
-    if (total == 0) grad_val = nullptr;                          // no stored entry: nothing to write
-    if (!grad_val && !grad_diag) {
-        if (total == 0) return WLSQM_OK;
-        set_error(name + ": no output is asked for");
-        return WLSQM_EVALUE;
-    }
-    if (m % 2 == 0 && (((uintptr_t)lam | (uintptr_t)x) & 15)) {
-        set_error(name + ": with m = 2 or 4 lam and x must be 16-byte aligned");
-        return WLSQM_EVALUE;
-    }
-    KrylovCoupled q;
-    q.npoints = npoints; q.total = total;
-    q.len = len; q.width = width; q.soff = reinterpret_cast<const long long*>(soff);
-    q.col = col; q.val = nullptr; q.dten = nullptr; q.dswap = 0;
-    for (int i = 0; i < KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS; ++i) q.dconst[i] = 0.0;
-    for (int i = 0; i < KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_PLANES; ++i) q.coupling[i] = i < m * m * nop ? coupling[i] : 0.0;
-    DeviceScope scope;
-    const int rc = scope.enter(device);
+    return krylov_system_grads_call("krylov_system_grads", false, npoints, nslices, len, width, soff, col, total, nop, m, coupling, lam, x,
+                                    grad_val, grad_diag, device, stream);
+}
+
+// A per-point coupling: `coupling` is a device tensor (m, m, nop, npoints).  transposed != 0: the arrays are the
+// transposed ones of the planes and `mixed` is a device plane of nop * m * npoints doubles that every product writes first.
+int wlsqm_hip_krylov_system_point_start_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                               const int32_t* col, const double* val, int64_t total, int nop, int m, const double* coupling,
+                                               const double* diag, const double* diag_const, int transposed, double* mixed, int jacobi,
+                                               const double* b, const double* x, double rtol, double atol, int64_t maxiter, void* workspace,
+                                               int device, void* stream) {
+    int rc = krylov_tolerances("krylov_system_point_start", b, x, rtol, atol, maxiter);
     if (rc != WLSQM_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    switch (m) {
-    case 1: krylov_system_grads_planes<1>(nop, q, lam, x, grad_val, grad_diag, s); break;
-    case 2: krylov_system_grads_planes<2>(nop, q, lam, x, grad_val, grad_diag, s); break;
-    case 3: krylov_system_grads_planes<3>(nop, q, lam, x, grad_val, grad_diag, s); break;
-    default: krylov_system_grads_planes<4>(nop, q, lam, x, grad_val, grad_diag, s); break;
-    }
-    WLSQM_HIP_CHECK(hipGetLastError());
-    note_kernel("krylov-system-grads");
-    return WLSQM_OK;
+    KrylovPointCall p;
+    KrylovSystemCall& c = p.c;
+    p.mixed = mixed;
+    c.what = SYSTEM_CALL_START; c.jacobi = jacobi; c.maxiter = (int)maxiter;
+    c.in = x; c.other = b; c.x = const_cast<double*>(x);        // the start reads x
+    c.rtol = rtol; c.atol = atol; c.niter = 0; c.s = (hipStream_t)stream;
+    return krylov_point_call("krylov_system_point_start", p, npoints, nslices, len, width, soff, col, val, total, nop, m, coupling, diag,
+                             diag_const, transposed, workspace, device);
+}
+
+int wlsqm_hip_krylov_system_point_bicgstab_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                  const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                                                  const double* coupling, const double* diag, const double* diag_const, int transposed,
+                                                  double* mixed, int jacobi, double* x, int64_t niter, void* workspace, int device,
+                                                  void* stream) {
+    if (niter < 0) { set_error("krylov_system_point_bicgstab: niter must be >= 0"); return WLSQM_EVALUE; }
+    KrylovPointCall p;
+    KrylovSystemCall& c = p.c;
+    p.mixed = mixed;
+    c.what = SYSTEM_CALL_ITERATE; c.jacobi = jacobi; c.maxiter = 0;
+    c.in = x; c.other = x; c.x = x;
+    c.rtol = c.atol = 0.0; c.niter = niter; c.s = (hipStream_t)stream;
+    return krylov_point_call("krylov_system_point_bicgstab", p, npoints, nslices, len, width, soff, col, val, total, nop, m, coupling, diag,
+                             diag_const, transposed, workspace, device);
+}
+
+int wlsqm_hip_krylov_system_point_product_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                 const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                                                 const double* coupling, const double* diag, const double* diag_const, int transposed,
+                                                 double* mixed, const double* in, const double* w, double* out, void* workspace, int device,
+                                                 void* stream) {
+    KrylovPointCall p;
+    KrylovSystemCall& c = p.c;
+    p.mixed = mixed;
+    c.what = SYSTEM_CALL_PRODUCT; c.jacobi = 0; c.maxiter = 0;
+    c.in = in; c.other = w; c.x = out;
+    c.rtol = c.atol = 0.0; c.niter = 0; c.s = (hipStream_t)stream;
+    return krylov_point_call("krylov_system_point_product", p, npoints, nslices, len, width, soff, col, val, total, nop, m, coupling, diag,
+                             diag_const, transposed, workspace, device);
+}
+
+int wlsqm_hip_krylov_system_point_grads_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                               const int32_t* col, int64_t total, int nop, int m, const double* coupling, const double* lam,
+                                               const double* x, double* grad_val, double* grad_diag, int device, void* stream) {
+    return krylov_system_grads_call("krylov_system_point_grads", true, npoints, nslices, len, width, soff, col, total, nop, m, coupling, lam, x,
+                                    grad_val, grad_diag, device, stream);
 }
 
 }  // extern "C"

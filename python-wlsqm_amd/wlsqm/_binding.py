@@ -284,6 +284,15 @@ def lib():
         L.wlsqm_hip_krylov_system_grads_device.argtypes = ([C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_int]
                                                            + [C.c_void_p] * 5 + [C.c_int, C.c_void_p])
         L.wlsqm_hip_krylov_system_grads_device.restype = C.c_int
+    # a per-point coupling: coupling is a device tensor, then transposed and the mixed plane (StencilSystemSolver)
+    if hasattr(L, "wlsqm_hip_krylov_system_point_start_device"):
+        point = coupled + [C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_system_point_start_device.argtypes = point + L.wlsqm_hip_krylov_system_start_device.argtypes[len(coupled):]
+        L.wlsqm_hip_krylov_system_point_bicgstab_device.argtypes = point + L.wlsqm_hip_krylov_system_bicgstab_device.argtypes[len(coupled):]
+        L.wlsqm_hip_krylov_system_point_product_device.argtypes = point + L.wlsqm_hip_krylov_system_product_device.argtypes[len(coupled):]
+        L.wlsqm_hip_krylov_system_point_grads_device.argtypes = L.wlsqm_hip_krylov_system_grads_device.argtypes
+        for name in ("start", "bicgstab", "product", "grads"):
+            getattr(L, "wlsqm_hip_krylov_system_point_%s_device" % name).restype = C.c_int
     # batched dense solves (wlsqm.utils.lapackdrivers, wlsqm.hip.*_batched)
     for op in ("getrf", "gesv", "sytrf", "sysv"):
         solve = op in ("gesv", "sysv")

@@ -897,7 +897,7 @@ def _autograd():
             if slots is not None:
                 op.set_coefficients(slots.detach(), det(own), stream=stream)
             if coupling is not None:
-                solver.set_coupling(coupling.detach().cpu().numpy())
+                solver.set_coupling(coupling.detach() if solver.per_point else coupling.detach().cpu().numpy())
             with _torch_stream(stream, solver._device):
                 x = (x0.detach().clone() if x0 is not None
                      else torch.zeros((solver.npoints, solver.m), dtype=torch.float64, device=solver._device))
@@ -923,7 +923,7 @@ def _autograd():
                 elif has_slots:
                     op.set_coefficients(made_from[0].detach(), made_from[1].detach() if has_own else None, stream=stream)
                 if has_coupling:
-                    solver.set_coupling(cp.detach().cpu().numpy())
+                    solver.set_coupling(cp.detach() if solver.per_point else cp.detach().cpu().numpy())
                 with _torch_stream(stream, device):
                     lam = torch.zeros((solver.npoints, solver.m), dtype=torch.float64, device=device)
                     x = x.detach()
@@ -1012,7 +1012,8 @@ def _solve_geometry_adjoint(solver, S, x, lam, stream):
 def _system_geometry_adjoint(solver, S, x, lam, stream):
     """dL/dS through the coupled M x = b at fixed x, lam and neighbour lists: section 18's route once per
     component b — the fit of F = x[:, b] and its geometry adjoint with g_j = -sum_o (sum_a coupling[a, b, o] lam[j, a]) rows[o], per-case
-    rows where the operator has them — and the m results summed in component order."""
+    rows where the operator has them — and the m results summed in component order.  A per-point table (section 26) contributes
+    coupling[a, b, o, j], the coefficients of row j."""
     import torch
     op = solver._op
     hoods, nk, knowns, weighting_method, point_index = op._geo
@@ -1020,8 +1021,11 @@ def _system_geometry_adjoint(solver, S, x, lam, stream):
     total = None
     for b in range(solver.m):
         with _torch_stream(stream, solver._device):
-            cp = torch.from_numpy(solver.coupling[:, b, :].copy()).to(solver._device)          # (m, nop): coupling[a, b, o]
-            u = lam[:n] @ cp                                                                   # (n, nop)
+            if solver.per_point:                             # u[j, o] = sum_a coupling[a, b, o, j] lam[j, a]
+                u = torch.einsum("aoj,ja->jo", solver.coupling[:, b, :, :n], lam[:n])
+            else:
+                cp = torch.from_numpy(solver.coupling[:, b, :].copy()).to(solver._device)      # (m, nop): coupling[a, b, o]
+                u = lam[:n] @ cp                                                               # (n, nop)
             F = torch.zeros((S.shape[0],), dtype=torch.float64, device=solver._device)         # points beyond the operator's: never named
             F[:op.npoints] = x[:, b]
             fi = torch.zeros((n, no), dtype=torch.float64, device=solver._device)
@@ -2984,7 +2988,12 @@ class StencilSystemSolver:
     are a function of the inputs, and eager and captured runs agree.
 
     op: as StencilSolver takes it — square, row j the equation of point j, not closed, without known derivatives — with at most 8 planes.
-    coupling: host array-like of float64 (m, m, nop), every entry finite; read here, once (set_coupling replaces the table).
+    coupling: host array-like of float64 (m, m, nop), every entry finite; read here, once (set_coupling replaces the table).  Or a
+    contiguous float64 device tensor (m, m, nop, npoints), plane-major like the diag tensor: the equation of point i
+    carries its own coefficients, M[(i, a), (j, b)] = D_ab,i delta_ij + sum_o coupling[a, b, o, i] A_o[i, j].  The tensor is read on the
+    stream by every start, product and gradient; the caller may change it in place, and a captured graph sees the change.  Its kernels
+    sum in another order than the constant table's (same bounds, other bits); M^T mixes lam with the coefficients at their own point
+    into a plane of m nop npoints doubles first (prepare_transpose), 10 launches per iteration.
     diag: a float d (D = d I_m), a host (m, m) array-like of constants, or a contiguous float64 device tensor (m, m, npoints), each
     D_ab a diagonal matrix; a tensor is read at every solve (the caller may change it in place).
     preconditioner: "jacobi", the inverse of the scalar diagonal of M — for unknown (i, a): D_aa,i + sum_o coupling[a, a, o] (the sum of
@@ -2996,8 +3005,8 @@ class StencilSystemSolver:
     solve, enqueue and product take transpose=True for M^T, whose block (a, b) is D_ba + sum_o coupling[b, a, o] A_o^T: the same kernels
     on the operator's transposed arrays (prepare_transpose), a diag tensor read in place.  gradients(), coupling_gradient() and
     differentiable_stencil_system_solve carry a loss through the solve.
-    Out of scope (sections 24 and 25): method="bicgstab2", BlockJacobi and ApproximateInverse, nfields, a per-point coupling, m > 4, a
-    capturable backward pass, second derivatives, wlsqm.sharded."""
+    Out of scope (sections 24 to 26): method="bicgstab2", BlockJacobi and ApproximateInverse, nfields, a coupling that scales columns,
+    m > 4, a capturable backward pass, second derivatives, wlsqm.sharded."""
 
     def __init__(self, op, coupling, diag=0.0, preconditioner="jacobi"):
         import numpy as np
@@ -3013,7 +3022,12 @@ class StencilSystemSolver:
         if preconditioner is not None and not (isinstance(preconditioner, str) and preconditioner == "jacobi"):
             raise ValueError("preconditioner must be 'jacobi' or None for coupled fields; got %r" % (preconditioner,))
         self._jacobi = 1 if preconditioner == "jacobi" else 0
-        cp = self._coupling_table(coupling, op.nop)
+        self.per_point = self._is_point_table(coupling)
+        self._mixed = None
+        if self.per_point:
+            cp = self._coupling_tensor(coupling, op.nop, op.npoints, op._m["col"])
+        else:
+            cp = self._coupling_table(coupling, op.nop)
         m = int(cp.shape[0])
         self.m, self.nop, self.npoints, self._device = m, op.nop, op.npoints, op._device
         self.coupling = cp
@@ -3036,7 +3050,7 @@ class StencilSystemSolver:
             if not np.isfinite(dc).all():
                 raise ValueError("every entry of diag must be finite")
             self.diag = dc = np.ascontiguousarray(dc)
-        self._cp = (C.c_double * cp.size)(*cp.ravel().tolist())
+        self._cp = None if self.per_point else (C.c_double * cp.size)(*cp.ravel().tolist())
         self._dc = (C.c_double * (m * m))(*dc.ravel().tolist())
         pi = getattr(op, "_point_index", None)
         if pi is not None and not bool((pi[:op.ncases].long() == torch.arange(op.ncases, device=pi.device)).all()):
@@ -3064,12 +3078,43 @@ class StencilSystemSolver:
             raise ValueError("every entry of coupling must be finite")
         return cp
 
+    @staticmethod
+    def _is_point_table(coupling):
+        """True for what is taken as a per-point table: a device tensor of four dimensions.  A device tensor of any other rank is left
+        to _coupling_table, which refuses it."""
+        return bool(hasattr(coupling, "is_cuda") and coupling.is_cuda and hasattr(coupling, "dim") and coupling.dim() == 4)
+
+    @staticmethod
+    def _coupling_tensor(coupling, nop, npoints, like, m=None):
+        """The constructor's checks of a per-point `coupling`: a contiguous float64 device tensor (m, m, nop, npoints) on the operator's
+        device (m given: that m).  Its entries are not read here: a NaN or Inf among them ends a solve with status 3 or 4."""
+        _check(coupling, "coupling", "float64", 4)
+        sh = tuple(coupling.shape)
+        if sh[0] != sh[1] or not 1 <= sh[0] <= 4 or sh[2] != nop or sh[3] != npoints or not coupling.is_contiguous():
+            raise ValueError("a per-point coupling must be a contiguous float64 device tensor of shape (m, m, nop, npoints) with 1 <= m <= 4, "
+                             "nop = %d, the operator's value planes, and npoints = %d; got shape %s with strides %s"
+                             % (nop, npoints, sh, tuple(coupling.stride())))
+        if nop > 8:
+            raise ValueError("coupled fields take an operator of at most 8 value planes; it has %d" % nop)
+        if m is not None and sh[0] != m:
+            raise ValueError("the new coupling must keep the solver's shape (%d, %d, %d, %d); got shape %s" % (m, m, nop, npoints, sh))
+        _same_device(like, coupling)
+        return coupling
+
     def set_coupling(self, coupling):
-        """Replace the coupling table by a new one of the same shape (m, m, nop), under the constructor's checks (a host array, every
-        entry finite; ValueError).  The table is host memory that travels with every launch: nothing is enqueued, and the next solve,
-        product or gradient reads the new one (a captured graph keeps the table it was captured with) — parameter sweeps on one
-        workspace, and what autograd writes `coupling` with."""
+        """Replace the coupling table by a new one of the same kind and shape, under the constructor's checks (ValueError).
+        A host table (m, m, nop) is host memory that travels with every launch: nothing is enqueued, and the next solve, product or
+        gradient reads the new one (a captured graph keeps the table it was captured with) — parameter sweeps on one workspace, and
+        what autograd writes `coupling` with.  A per-point solver takes a new device tensor (m, m, nop, npoints) on the same device,
+        which the next call reads on its stream; a captured graph keeps reading the tensor it was captured with, whose contents the
+        caller may change in place.  Changing a solver from one kind of table to the other is a ValueError."""
         self._live()
+        if self._is_point_table(coupling) != self.per_point:
+            raise ValueError("set_coupling cannot change the kind of table: the solver was made with %s"
+                             % ("a per-point device tensor (m, m, nop, npoints)" if self.per_point else "a host table (m, m, nop)"))
+        if self.per_point:
+            self.coupling = self._coupling_tensor(coupling, self.nop, self.npoints, self._ws, self.m)
+            return self
         cp = self._coupling_table(coupling, self.nop, self.m)
         self.coupling = cp
         self._cp = (C.c_double * cp.size)(*cp.ravel().tolist())
@@ -3082,14 +3127,17 @@ class StencilSystemSolver:
 
     def close(self):
         """Release the workspace now; harmless when called again.  The operator and a diag tensor stay the caller's."""
-        self._ws = self._op = self.x = None
+        self._ws = self._op = self.x = self._mixed = None
         if hasattr(self.__dict__.get("diag"), "dim"):
             self.diag = None
+        if self.__dict__.get("per_point"):
+            self.coupling = None
 
     def memory_used(self):
-        """Bytes of device memory the solver holds: the workspace."""
+        """Bytes of device memory the solver holds: the workspace and, for a per-point coupling once a transposed use has allocated
+        it, the mixed plane of m nop npoints doubles.  The coupling tensor is the caller's."""
         self._live()
-        return self._ws.numel() * self._ws.element_size()
+        return sum(t.numel() * t.element_size() for t in (self._ws, self._mixed) if t is not None)
 
     def refresh(self, stream=None):
         """The Jacobi diagonal is recomputed from the operator's arrays and the diag tensor as they are on the stream by the start of
@@ -3116,6 +3164,10 @@ class StencilSystemSolver:
         held = dict(named, workspace=self._ws)
         if hasattr(self.diag, "dim"):
             held["diag"] = self.diag
+        if self.per_point:
+            held["coupling"] = self.coupling
+            if self._mixed is not None:
+                held["the mixed plane"] = self._mixed
         names = list(held)
         for i, a in enumerate(names):
             for b in names[i + 1:]:
@@ -3124,19 +3176,30 @@ class StencilSystemSolver:
 
     def _system(self, transpose=False):
         """The system's arguments of the C entry points; transpose: the operator's transposed arrays for the *_transposed_device calls,
-        which exchange (a, b) in coupling and diag themselves."""
+        which exchange (a, b) in coupling and diag themselves.  A per-point solver: the coupling tensor's pointer in the table's place,
+        then `transposed` and the mixed plane, the leading arguments of the *_point_* calls."""
         m, val = (self._op._t, self._op._tval) if transpose else (self._op._m, self._op._val)
         d = self.diag
-        return (m["nrows"], int(m["width"].shape[0]), _ptr(m["len"]), _ptr(m["width"]), _ptr(m["soff"]), _ptr(m["col"]), _ptr(val),
-                m["total"], self.nop, self.m, C.cast(self._cp, C.c_void_p), _ptr(d) if hasattr(d, "dim") else None,
-                C.cast(self._dc, C.c_void_p))
+        head = (m["nrows"], int(m["width"].shape[0]), _ptr(m["len"]), _ptr(m["width"]), _ptr(m["soff"]), _ptr(m["col"]), _ptr(val),
+                m["total"], self.nop, self.m)
+        tail = (_ptr(d) if hasattr(d, "dim") else None, C.cast(self._dc, C.c_void_p))
+        if self.per_point:
+            return head + (_ptr(self.coupling),) + tail + (1 if transpose else 0, _ptr(self._mixed) if transpose else None)
+        return head + (C.cast(self._cp, C.c_void_p),) + tail
+
+    def _call(self, what, transpose):
+        """The C entry point of `what` (start, bicgstab, product) for this solver's kind of table."""
+        if self.per_point:
+            return getattr(B.lib(), "wlsqm_hip_krylov_system_point_%s_device" % what)
+        return getattr(B.lib(), "wlsqm_hip_krylov_system_%s%s_device" % (what, "_transposed" if transpose else ""))
 
     _no_capture = StencilSolver._no_capture
     _tolerances = staticmethod(StencilSolver._tolerances)
 
     def _transposed(self, transpose, stream):
-        """The operator's transposed matrix, built at the first transposed use (prepare_transpose: RuntimeError inside a capture)."""
-        if transpose and self._op._t is None:
+        """The operator's transposed matrix and a per-point solver's mixed plane, built at the first transposed use (prepare_transpose:
+        RuntimeError inside a capture)."""
+        if transpose and (self._op._t is None or (self.per_point and self._mixed is None)):
             self.prepare_transpose(stream)
         return bool(transpose)
 
@@ -3146,15 +3209,23 @@ class StencilSystemSolver:
         graph capture.  op.update and set_coefficients keep it refreshed, or drop it where the operator does (new hoods; too large for
         its index pairs), and the next transposed use rebuilds it.  Returns True when this call built something."""
         self._live()
-        return self._op.prepare_transpose(stream) if self._op._t is None else False
+        built = self._op.prepare_transpose(stream) if self._op._t is None else False
+        if self.per_point and self._mixed is None:
+            import torch
+            with _torch_stream(stream, self._device):
+                if self._device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("the solver has no mixed plane for its per-point coupling yet and the stream is capturing: call "
+                                       "prepare_transpose before the capture")
+                self._mixed = torch.zeros((self.npoints, self.nop, self.m), dtype=torch.float64, device=self._device)
+            built = True
+        return built
 
     def _start(self, b, x, rtol, atol, maxiter, dev, s, transpose=False):
-        fn = B.lib().wlsqm_hip_krylov_system_start_transposed_device if transpose else B.lib().wlsqm_hip_krylov_system_start_device
-        B.check(fn(*self._system(transpose), self._jacobi, _ptr(b), _ptr(x), rtol, atol, maxiter, _ptr(self._ws), dev, s))
+        B.check(self._call("start", transpose)(*self._system(transpose), self._jacobi, _ptr(b), _ptr(x), rtol, atol, maxiter,
+                                               _ptr(self._ws), dev, s))
 
     def _iterate(self, x, niter, dev, s, transpose=False):
-        fn = B.lib().wlsqm_hip_krylov_system_bicgstab_transposed_device if transpose else B.lib().wlsqm_hip_krylov_system_bicgstab_device
-        B.check(fn(*self._system(transpose), self._jacobi, _ptr(x), niter, _ptr(self._ws), dev, s))
+        B.check(self._call("bicgstab", transpose)(*self._system(transpose), self._jacobi, _ptr(x), niter, _ptr(self._ws), dev, s))
 
     def enqueue(self, b, x, iterations, rtol=1e-10, atol=0.0, stream=None, transpose=False):
         """The start of a solve and `iterations` iterations as kernel launches on `stream` and nothing else, as StencilSolver.enqueue:
@@ -3228,8 +3299,7 @@ class StencilSystemSolver:
             self._vectors(v=v, w=w, out=out)
         transpose = self._transposed(transpose, stream)
         s, dev = _stream_and_device(v, stream)
-        fn = B.lib().wlsqm_hip_krylov_system_product_transposed_device if transpose else B.lib().wlsqm_hip_krylov_system_product_device
-        B.check(fn(*self._system(transpose), _ptr(v), _ptr(w), _ptr(out), _ptr(self._ws), dev, s))
+        B.check(self._call("product", transpose)(*self._system(transpose), _ptr(v), _ptr(w), _ptr(out), _ptr(self._ws), dev, s))
         with _torch_stream(stream, self._device):
             head = self._ws[:16].cpu().numpy()
         return out, float(head[6]), float(head[7])
@@ -3237,20 +3307,21 @@ class StencilSystemSolver:
     def matrix(self):
         """M as a new torch.sparse_csr_tensor of m npoints rows in the interleaved numbering (row i m + a: component a at point i), built
         with torch operations from the operator's planes, coupling and diag as they are now: columns sorted, duplicates summed, the
-        blocks whose coupling is all zeros left out.  For checks and as the baseline of a flattened solve; not for a graph capture."""
+        blocks whose coupling is all zeros left out.  A per-point coupling scales the entries of row i by coupling[a, b, :, i] (one host
+        read per block to see whether it is all zeros).  For checks and as the baseline of a flattened solve; not for a graph capture."""
         import torch
         self._live()
         op, m, n = self._op, self.m, self.npoints
         src, row = op._entries()
         col = op._m["col"][src].long()
         rows, cols, vals = [], [], []
-        cp = torch.from_numpy(self.coupling).to(self._device)
+        cp = self.coupling if self.per_point else torch.from_numpy(self.coupling).to(self._device)
         for a in range(m):
             for b in range(m):
-                if self.coupling[a, b].any():
+                if bool((cp if self.per_point else self.coupling)[a, b].any()):
                     rows.append(row * m + a)
                     cols.append(col * m + b)
-                    vals.append((cp[a, b][:, None] * op._val[:, src]).sum(dim=0))
+                    vals.append(((cp[a, b][:, row] if self.per_point else cp[a, b][:, None]) * op._val[:, src]).sum(dim=0))
                 tensor = hasattr(self.diag, "dim")
                 if tensor or self.diag[a, b] != 0.0:
                     i = torch.arange(n, device=self._device)
@@ -3270,7 +3341,8 @@ class StencilSystemSolver:
         """The gradients of a loss L through the solve M x = b, from x and lam, the solution of M^T lam = dL/dx (solve(transpose=True)):
         SystemGradients(values, diag), each None unless asked for with True or with a tensor to write into.
           values: (nop, total) in the operator's layout: at every live entry of row j, in plane o,
-                  -sum_b (sum_a coupling[a, b, o] lam[j, a]) x[col, b], and +0.0 in the padding: dL/d(the entries of the value planes);
+                  -sum_b (sum_a coupling[a, b, o] lam[j, a]) x[col, b] (a per-point table: coupling[a, b, o, j], row j's own), and +0.0 in
+                  the padding: dL/d(the entries of the value planes);
                   op._unpack's layout per slot through differentiable_stencil_system_solve's `coefficients`.
           diag:   (m, m, npoints), -(lam[i, a] * x[i, b]): dL/d(diag).
         One kernel launch on `stream` ("krylov-system-grads": one pass over the forward structure that reads the columns and writes the
@@ -3292,6 +3364,8 @@ class StencilSystemSolver:
         others = dict(named, workspace=self._ws, **{"the operator's values": self._op._val})
         if hasattr(self.diag, "dim"):
             others["diag"] = self.diag
+        if self.per_point:
+            others["coupling"] = self.coupling
         for t, name, shape, says in ((gval, "values", (self.nop, total), "the operator's layout"),
                                      (gdiag, "diag", (self.m, self.m, self.npoints), "the diag tensor's")):
             if t is None:
@@ -3308,9 +3382,11 @@ class StencilSystemSolver:
                     raise ValueError("%s overlaps %s in memory" % ("grad_diag" if name == "diag" else name, other))
             others["grad_diag" if name == "diag" else name] = t
         s, dev = _stream_and_device(x, stream)
-        B.check(B.lib().wlsqm_hip_krylov_system_grads_device(
+        fn = B.lib().wlsqm_hip_krylov_system_point_grads_device if self.per_point else B.lib().wlsqm_hip_krylov_system_grads_device
+        B.check(fn(
             m["nrows"], int(m["width"].shape[0]), _ptr(m["len"]), _ptr(m["width"]), _ptr(m["soff"]), _ptr(m["col"]), total, self.nop, self.m,
-            C.cast(self._cp, C.c_void_p), _ptr(lam), _ptr(x), _ptr(gval) if gval is not None and total else None, _ptr(gdiag), dev, s))
+            _ptr(self.coupling) if self.per_point else C.cast(self._cp, C.c_void_p), _ptr(lam), _ptr(x),
+            _ptr(gval) if gval is not None and total else None, _ptr(gdiag), dev, s))
         return SystemGradients(gval, gdiag)
 
     def coupling_gradient(self, lam, x, stream=None):
@@ -3318,11 +3394,14 @@ class StencilSystemSolver:
         the operator's stacked product on the m columns of x (op.apply, all planes in one pass) and a contraction with lam by torch, on
         `stream`: m elementwise products and sums over the points (a matrix product with one dimension of npoints is not what the
         BLAS behind torch.einsum is built for: 30 to 100 ms at 10^6 points, against about 1 ms).  It allocates its result and the
-        products."""
+        products.  A per-point solver: (m, m, nop, npoints), entry (a, b, o, i) is -(lam[i, a] * (A_o x[:, b])_i), the same stacked
+        product and one elementwise product, with no sum over the points."""
         import torch
         self._vectors(lam=lam, x=x)
         Y = self._op.apply(x.t(), stream=stream)                          # (m, nop, npoints): Y[b, o] = A_o x[:, b]
         with _torch_stream(stream, self._device):
+            if self.per_point:
+                return -(lam.t().contiguous()[:, None, None, :] * Y[None])   # contiguous, as the coupling tensor it is the gradient of
             return -torch.stack([(Y * lam[:, a]).sum(dim=-1) for a in range(self.m)])
 
 
@@ -3408,8 +3487,9 @@ def differentiable_stencil_system_solve(solver, b, x0=None, S=None, coefficients
     at fixed neighbour lists.  coefficients=(slots, own) as StencilOperator.set_coefficients takes them, all nop planes: written into
     the operator first, and they receive the gradients of every plane's entries, exact zeros in the padding.  Both: ValueError.
     coupling: a float64 torch tensor (m, m, nop), on the host or on the device; the forward writes it into the solver
-    (solver.set_coupling), and it receives its gradient on its own device.  Without it the solver's table is read as it is, in both
-    passes.  With S, coefficients or coupling the backward pass first puts the operator and the table back where the forward had them,
+    (solver.set_coupling), and it receives its gradient on its own device.  For a solver with a per-point coupling it is the contiguous
+    float64 device tensor (m, m, nop, npoints) that set_coupling takes, and its gradient has that shape: a coefficient field (DESIGN.md
+    section 26).  Without it the solver's table is read as it is, in both passes.  With S, coefficients or coupling the backward pass first puts the operator and the table back where the forward had them,
     so that the steps of a loop may share one operator and one solver.
 
     The forward solves from x0 (default zeros; no gradient) to rtol / atol within maxiter iterations; a status other than 0 is a
@@ -3436,7 +3516,9 @@ def differentiable_stencil_system_solve(solver, b, x0=None, S=None, coefficients
     if coupling is not None:
         if not hasattr(coupling, "dim") or not hasattr(coupling, "is_cuda") or not hasattr(coupling, "requires_grad"):
             raise ValueError("coupling must be a float64 torch tensor (m, m, nop), on the host or on the device")
-        if str(coupling.dtype) != "torch.float64" or tuple(coupling.shape) != (solver.m, solver.m, solver.nop):
+        if solver.per_point:
+            solver._coupling_tensor(coupling, solver.nop, solver.npoints, solver._ws, solver.m)
+        elif str(coupling.dtype) != "torch.float64" or tuple(coupling.shape) != (solver.m, solver.m, solver.nop):
             raise ValueError("coupling must be a float64 torch tensor of shape (%d, %d, %d); got %s of shape %s"
                              % (solver.m, solver.m, solver.nop, coupling.dtype, tuple(coupling.shape)))
     named = dict(b=b) if x0 is None else dict(b=b, x0=x0)
