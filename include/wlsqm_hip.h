@@ -876,6 +876,67 @@ int wlsqm_hip_krylov_system_point_grads_device(int64_t npoints, int64_t nslices,
                                                const int32_t* col, int64_t total, int nop, int m, const double* coupling, const double* lam,
                                                const double* x, double* grad_val, double* grad_diag, int device, void* stream);
 
+/* ---- coupled fields: block-Jacobi over points (extension; csrc/krylov.hip) ----
+ * P = blockdiag(M_BB)^-1, block B the `points` consecutive points B points .. (B + 1) points - 1 with all m unknowns of each:
+ * R = m * points <= 32 consecutive rows of the flat (npoints, m) vectors, the last block cut at npoints and completed by the identity.
+ * The plane: wlsqm_hip_krylov_system_block_bytes(npoints, m, points) bytes of device memory (-1 for arguments out of range), 8-byte
+ * aligned, 16-byte aligned for m = 2 and 4.  With NB the smallest of 8, 16, 32 that holds R and G = 64 / NB, lane g NB + l of wave w is
+ * row l of block w G + g, and W[(w NB + j) 64 + lane] is entry (l, j) of that block's inverse; rows and columns from R on hold the
+ * identity.  ceil(nwaves / 4) doubles behind the nwaves NB 64 count the unusable blocks of the last factor.
+ * wlsqm_hip_krylov_system_block_factor_device ("krylov-system-blocks", one launch): len .. val are the FORWARD arrays, `coupling` the
+ * host table (point == 0) or the device tensor (m, m, nop, npoints) (point != 0); `planes` receives the inverses and `planes_t`
+ * (nullable) their transposes, which are the inverse blocks of M^T.  A block with a zero or non-finite pivot or a non-finite inverse
+ * is counted, and the next start ends with status 4 before the first iteration.
+ * wlsqm_hip_krylov_system_block_gather_device is an internal check hook, not part of the supported surface (the tests read the
+ * gathered entries through it; it may change or go without notice): the same launch without the elimination; `planes` (of the same
+ * size) receives the gathered blocks of M themselves in the same layout, identity padding included, and nothing is counted.
+ * wlsqm_hip_krylov_system_block_precondition_device ("krylov-system-precondition", one launch): out = P v; v and out must not overlap.
+ * The start and bicgstab forms are their siblings above with `points, planes` in the place of `jacobi`: the start reduces the plane's
+ * counts where the sibling computes the scalar diagonal, and an iteration applies P in "krylov-system-update-block" (8 launches, 10 on
+ * the per-point transposed route).  The transposed forms take the arrays of the transposed planes and the plane of the transposes.
+ * WLSQM_EVALUE before any launch: points < 1 or m * points > 32, a null plane, a plane that is not 16-byte aligned for m = 2 or 4, and
+ * what the siblings refuse. */
+int64_t wlsqm_hip_krylov_system_block_bytes(int64_t npoints, int m, int points);
+int wlsqm_hip_krylov_system_block_factor_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                                                const double* coupling, const double* diag, const double* diag_const, int point, int points,
+                                                void* planes, void* planes_t, int device, void* stream);
+int wlsqm_hip_krylov_system_block_gather_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                                                const double* coupling, const double* diag, const double* diag_const, int point, int points,
+                                                void* planes, int device, void* stream);
+int wlsqm_hip_krylov_system_block_precondition_device(int64_t npoints, int m, int points, const void* planes, const double* v, double* out,
+                                                      int device, void* stream);
+int wlsqm_hip_krylov_system_block_start_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                               const int32_t* col, const double* val, int64_t total, int nop, int m, const double* coupling,
+                                               const double* diag, const double* diag_const, int points, const void* planes, const double* b,
+                                               const double* x, double rtol, double atol, int64_t maxiter, void* workspace, int device,
+                                               void* stream);
+int wlsqm_hip_krylov_system_block_bicgstab_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                  const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                                                  const double* coupling, const double* diag, const double* diag_const, int points,
+                                                  const void* planes, double* x, int64_t niter, void* workspace, int device, void* stream);
+int wlsqm_hip_krylov_system_block_start_transposed_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                          const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop,
+                                                          int m, const double* coupling, const double* diag, const double* diag_const,
+                                                          int points, const void* planes, const double* b, const double* x, double rtol,
+                                                          double atol, int64_t maxiter, void* workspace, int device, void* stream);
+int wlsqm_hip_krylov_system_block_bicgstab_transposed_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                             const int64_t* soff, const int32_t* col, const double* val, int64_t total,
+                                                             int nop, int m, const double* coupling, const double* diag,
+                                                             const double* diag_const, int points, const void* planes, double* x,
+                                                             int64_t niter, void* workspace, int device, void* stream);
+int wlsqm_hip_krylov_system_point_block_start_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                     const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                                                     const double* coupling, const double* diag, const double* diag_const, int transposed,
+                                                     double* mixed, int points, const void* planes, const double* b, const double* x,
+                                                     double rtol, double atol, int64_t maxiter, void* workspace, int device, void* stream);
+int wlsqm_hip_krylov_system_point_block_bicgstab_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                        const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop,
+                                                        int m, const double* coupling, const double* diag, const double* diag_const,
+                                                        int transposed, double* mixed, int points, const void* planes, double* x,
+                                                        int64_t niter, void* workspace, int device, void* stream);
+
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ---- */
 /* Runs `reps` back-to-back launches of the fit kernel for batch `b` (device-resident, uniform
  * order) on `stream`, bracketed by HIP events on that stream; returns the mean kernel time in

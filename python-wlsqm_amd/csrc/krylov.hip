@@ -1955,9 +1955,219 @@ static void krylov_system_grads_planes(int nop, const KrylovCoupled& q, const do
     }
 }
 
+// ---- blocks over points for coupled fields: P = blockdiag(M_BB)^-1, block B the points B points .. (B + 1) points - 1 --
+// with all m unknowns of each: R = m points <= 32 consecutive rows of the flat vectors.  Section 19's plane carried to R <= NB, NB the
+// smallest of 8, 16, 32 that holds R: a wave holds G = 64 / NB blocks, lane g NB + l is row l of block wave G + g, flat row
+// (wave G + g) R + l, live when l < R and the row is below m npoints.  W[(wave NB + j) 64 + lane] is entry (l, j) of that block's inverse;
+// rows and columns from R on, and the rows that the cut last block leaves over, hold the identity.  Behind the nwaves NB 64 doubles sit
+// ceil(nwaves / 4) per-workgroup counts of the unusable blocks, which every start reduces into status 4.  A block of points need not
+// stay inside one slice of the operator, so every lane looks up the slice of its own point.
+// The entries, which tests/_krylov_system_block_ref.py states in numpy: entry ((i, a), (j, b)) = D_ab,i delta_ij + s, s the plain sum over
+// the stored entries e of row i with column j, in entry order, of t_ab(e) = c[a][b][0] val_0, then fma(c[a][b][o], val_o, t) for
+// o = 1 .. nop - 1; c the constant table or the point's own coefficients c[a][b][o][i].  The blocks of M^T are the transposes: the
+// factor always reads the forward arrays and writes the transposed inverses into WT.
+
+__host__ __device__ static inline int krylov_system_block_nb(int rows) { return rows <= 8 ? 8 : rows <= 16 ? 16 : 32; }
+
+static long long krylov_system_block_waves(long long npoints, int m, int points) {
+    const long long nblocks = (npoints + points - 1) / points;
+    const int per = 64 / krylov_system_block_nb(m * points);
+    return (nblocks + per - 1) / per;
+}
+
+// t_ab(e) of the lane's own a.  The constant table is indexed wave-uniformly (every a in turn, the lane keeps its own); a per-point
+// table is read at the lane's own address.
+__device__ __forceinline__ double krylov_system_block_term(const KrylovCoupled& q, int m, int nop, int a, int b, long long i,
+                                                           const double (&vs)[KRYLOV_SYSTEM_PLANES]) {
+    if (q.cpt) {
+        const double* cp = q.cpt + ((long long)(a * m + b) * nop) * q.npoints + i;
+        double t = cp[0] * vs[0];
+#pragma unroll
+        for (int o = 1; o < KRYLOV_SYSTEM_PLANES; ++o)
+            if (o < nop) t = __builtin_fma(cp[o * q.npoints], vs[o], t);
+        return t;
+    }
+    double t = 0.0;
+    for (int aa = 0; aa < m; ++aa) {                             // uniform
+        const int at = (aa * m + b) * nop;
+        double ta = q.coupling[at] * vs[0];
+#pragma unroll
+        for (int o = 1; o < KRYLOV_SYSTEM_PLANES; ++o)
+            if (o < nop) ta = __builtin_fma(q.coupling[at + o], vs[o], ta);
+        t = aa == a ? ta : t;
+    }
+    return t;
+}
+
+// One lane per row of the block layout.  The lane gathers its row of the block (the m targets of every stored entry whose column is a
+// point of the block, in entry order; padding is beyond the lane's own count and never loaded), then the NB lanes of a block invert it
+// exactly as krylov_blocks_kernel does, with the same elimination, checks, counts and stores.  m, nop and points are run-time
+// arguments; every register index is a constant.  invert == 0 stores the gathered rows as they are and counts nothing.
+template <int NB>
+__global__ void __launch_bounds__(256) krylov_system_blocks_kernel(const KrylovCoupled q, int m, int nop, int points, long long nwaves,
+                                                                   int invert, double* W, double* WT) {
+    constexpr int G = 64 / NB;
+    const int lane = threadIdx.x & 63, l = lane & (NB - 1), b0 = lane - l;
+    const long long wv = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    double bad = 0.0;
+    if (wv < nwaves) {                                           // wave-uniform
+        const int rows = m * points;
+        const long long blk = wv * G + lane / NB, row = blk * rows + l;
+        const bool live = l < rows && row < q.npoints * m;
+        const long long i = live ? row / m : 0, first = blk * points;        // the lane's point; the block's first point
+        const int a = live ? (int)(row - i * m) : 0;
+        double A[NB], inv[NB];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) A[j] = 0.0;
+        if (live) {
+            const long long sl = i >> 6, at = q.soff[sl] + (i & 63);
+            const int wid = q.width[sl];
+            int n = q.len[i];
+            n = n < wid ? n : wid;
+            for (int e = 0; e < n; ++e) {
+                const long long p = (long long)q.col[at + 64LL * e] - first;
+                if (p >= 0 && p < points) {
+                    double vs[KRYLOV_SYSTEM_PLANES];
+#pragma unroll
+                    for (int o = 0; o < KRYLOV_SYSTEM_PLANES; ++o) vs[o] = o < nop ? q.val[o * q.total + at + 64LL * e] : 0.0;
+                    for (int b = 0; b < m; ++b) {                // uniform
+                        const double t = krylov_system_block_term(q, m, nop, a, b, i, vs);
+                        const int tj = (int)p * m + b;
+#pragma unroll
+                        for (int j = 0; j < NB; ++j) A[j] += tj == j ? t : 0.0;
+                    }
+                }
+            }
+            for (int b = 0; b < m; ++b) {                        // uniform
+                double d = 0.0;
+                if (q.dten) {
+                    d = q.dten[(long long)(a * m + b) * q.npoints + i];
+                } else {
+                    for (int aa = 0; aa < m; ++aa) d = aa == a ? q.dconst[aa * m + b] : d;
+                }
+                const int tj = (int)(i - first) * m + b;
+#pragma unroll
+                for (int j = 0; j < NB; ++j) A[j] = (tj == j ? d : 0.0) + A[j];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            if (!live) A[j] = j == l ? 1.0 : 0.0;
+            inv[j] = j == l ? 1.0 : 0.0;
+        }
+        double* w = W + (wv * NB) * 64 + lane;
+        if (!invert) {                                           // uniform: the gathered blocks as they are (wlsqm_hip_krylov_system_block_gather_device)
+#pragma unroll
+            for (int j = 0; j < NB; ++j) w[64LL * j] = A[j];
+        } else {
+            bool used = false, unusable = false;
+            int step = 0;
+            krylov_eliminate<NB, 0>(A, inv, lane, used, step, unusable);
+            int src = lane;
+#pragma unroll
+            for (int j = 0; j < NB; ++j)
+                if (__shfl(step, b0 + j, 64) == l) src = b0 + j;
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                inv[j] = __shfl(inv[j], src, 64);
+                if (!__builtin_isfinite(inv[j])) unusable = true;
+                w[64LL * j] = inv[j];
+            }
+            if (WT) {
+                double* wt = WT + (wv * NB + l) * 64 + b0;       // column l of the transposed block, its rows b0 .. b0 + NB - 1
+#pragma unroll
+                for (int j = 0; j < NB; ++j) wt[j] = inv[j];
+            }
+            bad = unusable ? 1.0 : 0.0;
+        }
+    }
+    double* counts = W + nwaves * NB * 64;
+    block_sums<false>(bad, 0.0, counts, gridDim.x);
+    if (WT && threadIdx.x == 0) WT[nwaves * NB * 64 + blockIdx.x] = counts[blockIdx.x];
+}
+
+// krylov_update_block_kernel's P and S steps under the (wave, g, l) mapping above: no partial sums, so no summation order changes.
+template <int NB, int MODE>
+__global__ void __launch_bounds__(256) krylov_system_update_block_kernel(long long nrows, int rows, long long nwaves, const KrylovWork k,
+                                                                         const double* W, const KrylovScalars* sc) {
+    if (sc->done) return;                                        // uniform: the whole grid
+    const int lane = threadIdx.x & 63, l = lane & (NB - 1);
+    const long long wv = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (wv >= nwaves) return;                                    // wave-uniform
+    const long long i = (wv * (64 / NB) + lane / NB) * rows + l;
+    const bool live = l < rows && i < nrows;
+    double u = 0.0;
+    if (live) {
+        if (MODE == UPDATE_P) {
+            u = k.r[i];
+            if (sc->iterations > 0) {
+                const double omega = sc->omega, beta = (sc->rho / sc->rho_old) * (sc->alpha / omega);
+                u = u + beta * (k.p[i] - omega * k.v[i]);
+            }
+            k.p[i] = u;
+        } else {
+            u = k.r[i] - sc->alpha * k.v[i];
+            k.s[i] = u;
+        }
+    }
+    const double z = krylov_block_apply<NB>(W + (wv * NB) * 64 + lane, u, lane);
+    if (live) (MODE == UPDATE_P ? k.phat : k.shat)[i] = z;
+}
+
+template <int NB>
+__global__ void __launch_bounds__(256) krylov_system_precondition_kernel(long long nrows, int rows, long long nwaves, const double* W,
+                                                                         const double* v, double* out) {
+    const int lane = threadIdx.x & 63, l = lane & (NB - 1);
+    const long long wv = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (wv >= nwaves) return;                                    // wave-uniform
+    const long long i = (wv * (64 / NB) + lane / NB) * rows + l;
+    const bool live = l < rows && i < nrows;
+    const double z = krylov_block_apply<NB>(W + (wv * NB) * 64 + lane, live ? v[i] : 0.0, lane);
+    if (live) out[i] = z;
+}
+
+// The P or S step of an iteration with the blocks over `points` points.
+template <int MODE>
+static void krylov_system_update_block(long long npoints, int m, int points, const KrylovWork& w, const double* W, hipStream_t s) {
+    const int rows = m * points;
+    const long long nrows = npoints * m, nwaves = krylov_system_block_waves(npoints, m, points);
+    const dim3 grid((unsigned)((nwaves + 3) / 4)), block(256);
+    const KrylovScalars* sc = w.sc;
+    switch (krylov_system_block_nb(rows)) {
+    case 8: hipLaunchKernelGGL((krylov_system_update_block_kernel<8, MODE>), grid, block, 0, s, nrows, rows, nwaves, w, W, sc); break;
+    case 16: hipLaunchKernelGGL((krylov_system_update_block_kernel<16, MODE>), grid, block, 0, s, nrows, rows, nwaves, w, W, sc); break;
+    default: hipLaunchKernelGGL((krylov_system_update_block_kernel<32, MODE>), grid, block, 0, s, nrows, rows, nwaves, w, W, sc); break;
+    }
+}
+
+// The start of a solve with the blocks: the counts behind the plane into status 4, in the scalar diagonal's place.
+static void krylov_system_block_counts(long long npoints, int m, int points, const KrylovWork& w, const double* W, double rtol, double atol,
+                                       int maxiter, hipStream_t s) {
+    const long long nwaves = krylov_system_block_waves(npoints, m, points);
+    const double* counts = W + nwaves * krylov_system_block_nb(m * points) * 64;
+    hipLaunchKernelGGL(krylov_reduce_kernel, dim3(1), dim3(256), 0, s, (int)REDUCE_DIAG, counts, (nwaves + 3) / 4, 1, w.sc, rtol, atol, maxiter);
+}
+
+// The checks of `points` and of a plane that the block entry points share, ahead of any launch.
+static int krylov_system_block_arguments(const char* who, int m, int points, const void* planes, const void* planes_t) {
+    const std::string name(who);
+    if (m < 1 || m > KRYLOV_SYSTEM_FIELDS) { set_error(name + ": m must be 1 .. 4"); return WLSQM_EVALUE; }
+    if (points < 1 || m * points > 32) {
+        set_error(name + ": points must be 1 .. " + std::to_string(32 / m) + " for m = " + std::to_string(m) + " (m points <= 32)");
+        return WLSQM_EVALUE;
+    }
+    if (!planes) { set_error(name + ": null array"); return WLSQM_EVALUE; }
+    if (m % 2 == 0 && (((uintptr_t)planes | (uintptr_t)planes_t) & 15)) {
+        set_error(name + ": with m = 2 or 4 the block planes must be 16-byte aligned");
+        return WLSQM_EVALUE;
+    }
+    return WLSQM_OK;
+}
+
 enum { SYSTEM_CALL_START = 0, SYSTEM_CALL_ITERATE = 1, SYSTEM_CALL_PRODUCT = 2 };
 
 struct KrylovSystemCall {
+    int points = 0; const double* W = nullptr;                  // blocks over points (section 27): the plane, else null
     int what, jacobi, maxiter;
     KrylovCoupled q;
     KrylovWork w;                                               // at nrows = m npoints
@@ -1977,27 +2187,33 @@ static void krylov_system_run(const KrylovSystemCall& c) {
     hipStream_t s = c.s;
     double* const none = nullptr;
     if (c.what == SYSTEM_CALL_START) {
-        if (c.jacobi) {
-            hipLaunchKernelGGL((krylov_system_diag_kernel<M, NOP>), pgrid, block, 0, s, c.q, w.dinv, w.partial);
-            note_kernel("krylov-system-diag");
+        if (c.W) {
+            krylov_system_block_counts(c.q.npoints, M, c.points, w, c.W, c.rtol, c.atol, c.maxiter, s);
+        } else {
+            if (c.jacobi) {
+                hipLaunchKernelGGL((krylov_system_diag_kernel<M, NOP>), pgrid, block, 0, s, c.q, w.dinv, w.partial);
+                note_kernel("krylov-system-diag");
+            }
+            krylov_reduce(REDUCE_DIAG, w, c.jacobi ? nwgp : 0, 1, c.rtol, c.atol, c.maxiter, s);
         }
-        krylov_reduce(REDUCE_DIAG, w, c.jacobi ? nwgp : 0, 1, c.rtol, c.atol, c.maxiter, s);
         hipLaunchKernelGGL((krylov_system_spmv_kernel<M, NOP>), pgrid, block, 0, s, c.q, (int)SYSTEM_RESIDUAL, c.in, c.other, w.r, w.r0, w.partial, sc);
         note_kernel("krylov-system-spmv");
         krylov_reduce(REDUCE_RESIDUAL, w, nwgp, 2, c.rtol, c.atol, c.maxiter, s);
         note_kernel("krylov-reduce");
     } else if (c.what == SYSTEM_CALL_ITERATE) {
         for (int64_t it = 0; it < c.niter; ++it) {
-            hipLaunchKernelGGL((krylov_update_kernel<UPDATE_P>), ugrid, block, 0, s, nrows, w, c.x, sc);
+            if (c.W) krylov_system_update_block<UPDATE_P>(c.q.npoints, M, c.points, w, c.W, s);
+            else hipLaunchKernelGGL((krylov_update_kernel<UPDATE_P>), ugrid, block, 0, s, nrows, w, c.x, sc);
             hipLaunchKernelGGL((krylov_system_spmv_kernel<M, NOP>), pgrid, block, 0, s, c.q, (int)SYSTEM_V, (const double*)w.phat, (const double*)w.r0, w.v, none, w.partial, sc);
             krylov_reduce(REDUCE_ALPHA, w, nwgp, 1, 0.0, 0.0, 0, s);
-            hipLaunchKernelGGL((krylov_update_kernel<UPDATE_S>), ugrid, block, 0, s, nrows, w, c.x, sc);
+            if (c.W) krylov_system_update_block<UPDATE_S>(c.q.npoints, M, c.points, w, c.W, s);
+            else hipLaunchKernelGGL((krylov_update_kernel<UPDATE_S>), ugrid, block, 0, s, nrows, w, c.x, sc);
             hipLaunchKernelGGL((krylov_system_spmv_kernel<M, NOP>), pgrid, block, 0, s, c.q, (int)SYSTEM_T, (const double*)w.shat, (const double*)w.s, w.t, none, w.partial, sc);
             krylov_reduce(REDUCE_OMEGA, w, nwgp, 2, 0.0, 0.0, 0, s);
             hipLaunchKernelGGL((krylov_update_kernel<UPDATE_X>), ugrid, block, 0, s, nrows, w, c.x, sc);
             krylov_reduce(REDUCE_RHO, w, w.nwg, 2, 0.0, 0.0, 0, s);
         }
-        note_kernel("krylov-update");
+        note_kernel(c.W ? "krylov-system-update-block" : "krylov-update");
     } else {
         hipLaunchKernelGGL((krylov_system_spmv_kernel<M, NOP>), pgrid, block, 0, s, c.q, (int)SYSTEM_PRODUCT, c.in, c.other, c.x, none, w.partial, sc);
         krylov_reduce(REDUCE_PRODUCT, w, nwgp, 2, 0.0, 0.0, 0, s);
@@ -2348,27 +2564,33 @@ static void krylov_point_run(const KrylovPointCall& p) {
     double* const none = nullptr;
     const char* product = c.q.dswap ? "krylov-system-spmv-mixed" : "krylov-system-spmv-point";
     if (c.what == SYSTEM_CALL_START) {
-        if (c.jacobi) {
-            hipLaunchKernelGGL((krylov_system_diag_point_kernel<M, NOP>), pgrid, block, 0, s, c.q, w.dinv, w.partial);
-            note_kernel("krylov-system-diag-point");
+        if (c.W) {
+            krylov_system_block_counts(c.q.npoints, M, c.points, w, c.W, c.rtol, c.atol, c.maxiter, s);
+        } else {
+            if (c.jacobi) {
+                hipLaunchKernelGGL((krylov_system_diag_point_kernel<M, NOP>), pgrid, block, 0, s, c.q, w.dinv, w.partial);
+                note_kernel("krylov-system-diag-point");
+            }
+            krylov_reduce(REDUCE_DIAG, w, c.jacobi ? nwgp : 0, 1, c.rtol, c.atol, c.maxiter, s);
         }
-        krylov_reduce(REDUCE_DIAG, w, c.jacobi ? nwgp : 0, 1, c.rtol, c.atol, c.maxiter, s);
         krylov_point_product<M, NOP>(p, SYSTEM_RESIDUAL, c.in, c.other, w.r, w.r0);
         note_kernel(product);
         krylov_reduce(REDUCE_RESIDUAL, w, nwgp, 2, c.rtol, c.atol, c.maxiter, s);
         note_kernel("krylov-reduce");
     } else if (c.what == SYSTEM_CALL_ITERATE) {
         for (int64_t it = 0; it < c.niter; ++it) {
-            hipLaunchKernelGGL((krylov_update_kernel<UPDATE_P>), ugrid, block, 0, s, nrows, w, c.x, sc);
+            if (c.W) krylov_system_update_block<UPDATE_P>(c.q.npoints, M, c.points, w, c.W, s);
+            else hipLaunchKernelGGL((krylov_update_kernel<UPDATE_P>), ugrid, block, 0, s, nrows, w, c.x, sc);
             krylov_point_product<M, NOP>(p, SYSTEM_V, w.phat, w.r0, w.v, none);
             krylov_reduce(REDUCE_ALPHA, w, nwgp, 1, 0.0, 0.0, 0, s);
-            hipLaunchKernelGGL((krylov_update_kernel<UPDATE_S>), ugrid, block, 0, s, nrows, w, c.x, sc);
+            if (c.W) krylov_system_update_block<UPDATE_S>(c.q.npoints, M, c.points, w, c.W, s);
+            else hipLaunchKernelGGL((krylov_update_kernel<UPDATE_S>), ugrid, block, 0, s, nrows, w, c.x, sc);
             krylov_point_product<M, NOP>(p, SYSTEM_T, w.shat, w.s, w.t, none);
             krylov_reduce(REDUCE_OMEGA, w, nwgp, 2, 0.0, 0.0, 0, s);
             hipLaunchKernelGGL((krylov_update_kernel<UPDATE_X>), ugrid, block, 0, s, nrows, w, c.x, sc);
             krylov_reduce(REDUCE_RHO, w, w.nwg, 2, 0.0, 0.0, 0, s);
         }
-        note_kernel("krylov-update");
+        note_kernel(c.W ? "krylov-system-update-block" : "krylov-update");
     } else {
         krylov_point_product<M, NOP>(p, SYSTEM_PRODUCT, c.in, c.other, c.x, none);
         krylov_reduce(REDUCE_PRODUCT, w, nwgp, 2, 0.0, 0.0, 0, s);
@@ -3153,6 +3375,208 @@ int wlsqm_hip_krylov_system_point_grads_device(int64_t npoints, int64_t nslices,
                                                const double* x, double* grad_val, double* grad_diag, int device, void* stream) {
     return krylov_system_grads_call("krylov_system_point_grads", true, npoints, nslices, len, width, soff, col, total, nop, m, coupling, lam, x,
                                     grad_val, grad_diag, device, stream);
+}
+
+// Blocks over points.  `points` points of m unknowns each make a block, m points <= 32.
+int64_t wlsqm_hip_krylov_system_block_bytes(int64_t npoints, int m, int points) {
+    if (npoints < 0 || m < 1 || m > KRYLOV_SYSTEM_FIELDS || points < 1 || m * points > 32) return -1;
+    const long long nwaves = npoints ? krylov_system_block_waves(npoints, m, points) : 0;
+    return (int64_t)sizeof(double) * (nwaves * krylov_system_block_nb(m * points) * 64 + (nwaves + 3) / 4);
+}
+
+// "krylov-system-blocks", one launch: the forward arrays, the host table (point == 0) or the device tensor (point != 0), diag; the
+// inverses into `planes` and, when given, their transposes into `planes_t`.
+static int krylov_system_block_build(const char* who, int invert, int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                     const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                                     const double* coupling, const double* diag, const double* diag_const, int point, int points,
+                                     void* planes, void* planes_t, int device, void* stream) {
+    const std::string name(who);
+    int rc = krylov_system_block_arguments(who, m, points, planes, planes_t);
+    if (rc != WLSQM_OK) return rc;
+    if (nop < 1 || nop > KRYLOV_SYSTEM_PLANES) { set_error(name + ": nop must be 1 .. 8"); return WLSQM_EVALUE; }
+    if (npoints < 1 || nslices < 0 || npoints > 64 * nslices || total < 0 || (npoints * m + 255) / 256 > 0x7fffffffLL) {
+        set_error(name + ": npoints must be 1 .. 64 * nslices");
+        return WLSQM_EVALUE;
+    }
+    if (!len || !width || !soff || !col || !val || !coupling || (!diag && !diag_const)) { set_error(name + ": null array"); return WLSQM_EVALUE; }
+    if (point && ((uintptr_t)coupling & 7)) { set_error(name + ": coupling must be 8-byte aligned"); return WLSQM_EVALUE; }
+    KrylovCoupled q;
+    q.npoints = npoints; q.total = total;
+    q.len = len; q.width = width; q.soff = reinterpret_cast<const long long*>(soff);
+    q.col = col; q.val = val; q.dten = diag; q.dswap = 0; q.cpt = point ? coupling : nullptr;
+    for (int i = 0; i < KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS; ++i) q.dconst[i] = (!diag && i < m * m) ? diag_const[i] : 0.0;
+    for (int i = 0; i < KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_FIELDS * KRYLOV_SYSTEM_PLANES; ++i) q.coupling[i] = (!point && i < m * m * nop) ? coupling[i] : 0.0;
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const long long nwaves = krylov_system_block_waves(npoints, m, points);
+    const dim3 grid((unsigned)((nwaves + 3) / 4));
+    double *W = static_cast<double*>(planes), *WT = static_cast<double*>(planes_t);
+    switch (krylov_system_block_nb(m * points)) {
+    case 8: hipLaunchKernelGGL(krylov_system_blocks_kernel<8>, grid, dim3(256), 0, s, q, m, nop, points, nwaves, invert, W, WT); break;
+    case 16: hipLaunchKernelGGL(krylov_system_blocks_kernel<16>, grid, dim3(256), 0, s, q, m, nop, points, nwaves, invert, W, WT); break;
+    default: hipLaunchKernelGGL(krylov_system_blocks_kernel<32>, grid, dim3(256), 0, s, q, m, nop, points, nwaves, invert, W, WT); break;
+    }
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-system-blocks");
+    return WLSQM_OK;
+}
+
+int wlsqm_hip_krylov_system_block_factor_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                                                const double* coupling, const double* diag, const double* diag_const, int point, int points,
+                                                void* planes, void* planes_t, int device, void* stream) {
+    return krylov_system_block_build("krylov_system_block_factor", 1, npoints, nslices, len, width, soff, col, val, total, nop, m, coupling,
+                                     diag, diag_const, point, points, planes, planes_t, device, stream);
+}
+
+// The same launch without the elimination: the gathered diagonal blocks of M themselves in the plane's layout, for checks.
+int wlsqm_hip_krylov_system_block_gather_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                                                const double* coupling, const double* diag, const double* diag_const, int point, int points,
+                                                void* planes, int device, void* stream) {
+    return krylov_system_block_build("krylov_system_block_gather", 0, npoints, nslices, len, width, soff, col, val, total, nop, m, coupling,
+                                     diag, diag_const, point, points, planes, nullptr, device, stream);
+}
+
+// "krylov-system-precondition", one launch: out = P v on (npoints, m) vectors; the plane of the transposes gives P^T v.
+int wlsqm_hip_krylov_system_block_precondition_device(int64_t npoints, int m, int points, const void* planes, const double* v, double* out,
+                                                      int device, void* stream) {
+    int rc = krylov_system_block_arguments("krylov_system_block_precondition", m, points, planes, nullptr);
+    if (rc != WLSQM_OK) return rc;
+    if (npoints < 1 || (npoints * m + 255) / 256 > 0x7fffffffLL) {
+        set_error("krylov_system_block_precondition: npoints must be >= 1");
+        return WLSQM_EVALUE;
+    }
+    if (!v || !out) { set_error("krylov_system_block_precondition: null array"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = m * points;
+    const long long nrows = npoints * m, nwaves = krylov_system_block_waves(npoints, m, points);
+    const dim3 grid((unsigned)((nwaves + 3) / 4));
+    const double* W = static_cast<const double*>(planes);
+    switch (krylov_system_block_nb(rows)) {
+    case 8: hipLaunchKernelGGL(krylov_system_precondition_kernel<8>, grid, dim3(256), 0, s, nrows, rows, nwaves, W, v, out); break;
+    case 16: hipLaunchKernelGGL(krylov_system_precondition_kernel<16>, grid, dim3(256), 0, s, nrows, rows, nwaves, W, v, out); break;
+    default: hipLaunchKernelGGL(krylov_system_precondition_kernel<32>, grid, dim3(256), 0, s, nrows, rows, nwaves, W, v, out); break;
+    }
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-system-precondition");
+    return WLSQM_OK;
+}
+
+// wlsqm_hip_krylov_system_start_device / _bicgstab_device and their transposed forms with P taken from `planes` (the transposed forms:
+// from the plane of the transposes) as the factor left it.
+int wlsqm_hip_krylov_system_block_start_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                               const int32_t* col, const double* val, int64_t total, int nop, int m, const double* coupling,
+                                               const double* diag, const double* diag_const, int points, const void* planes, const double* b,
+                                               const double* x, double rtol, double atol, int64_t maxiter, void* workspace, int device,
+                                               void* stream) {
+    int rc = krylov_system_block_arguments("krylov_system_block_start", m, points, planes, nullptr);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_tolerances("krylov_system_block_start", b, x, rtol, atol, maxiter);
+    if (rc != WLSQM_OK) return rc;
+    KrylovSystemCall c;
+    c.points = points; c.W = static_cast<const double*>(planes);
+    c.what = SYSTEM_CALL_START; c.jacobi = 1; c.maxiter = (int)maxiter;
+    c.in = x; c.other = b; c.x = const_cast<double*>(x);
+    c.rtol = rtol; c.atol = atol; c.niter = 0; c.s = (hipStream_t)stream;
+    return krylov_system_call("krylov_system_block_start", c, npoints, nslices, len, width, soff, col, val, total, nop, m, coupling, diag,
+                              diag_const, workspace, device);
+}
+
+int wlsqm_hip_krylov_system_block_bicgstab_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                  const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                                                  const double* coupling, const double* diag, const double* diag_const, int points,
+                                                  const void* planes, double* x, int64_t niter, void* workspace, int device, void* stream) {
+    int rc = krylov_system_block_arguments("krylov_system_block_bicgstab", m, points, planes, nullptr);
+    if (rc != WLSQM_OK) return rc;
+    if (niter < 0) { set_error("krylov_system_block_bicgstab: niter must be >= 0"); return WLSQM_EVALUE; }
+    KrylovSystemCall c;
+    c.points = points; c.W = static_cast<const double*>(planes);
+    c.what = SYSTEM_CALL_ITERATE; c.jacobi = 1; c.maxiter = 0;
+    c.in = x; c.other = x; c.x = x;
+    c.rtol = c.atol = 0.0; c.niter = niter; c.s = (hipStream_t)stream;
+    return krylov_system_call("krylov_system_block_bicgstab", c, npoints, nslices, len, width, soff, col, val, total, nop, m, coupling, diag,
+                              diag_const, workspace, device);
+}
+
+int wlsqm_hip_krylov_system_block_start_transposed_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                          const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop,
+                                                          int m, const double* coupling, const double* diag, const double* diag_const,
+                                                          int points, const void* planes, const double* b, const double* x, double rtol,
+                                                          double atol, int64_t maxiter, void* workspace, int device, void* stream) {
+    int rc = krylov_system_block_arguments("krylov_system_block_start_transposed", m, points, planes, nullptr);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_tolerances("krylov_system_block_start_transposed", b, x, rtol, atol, maxiter);
+    if (rc != WLSQM_OK) return rc;
+    KrylovSystemCall c;
+    c.points = points; c.W = static_cast<const double*>(planes);
+    c.what = SYSTEM_CALL_START; c.jacobi = 1; c.maxiter = (int)maxiter;
+    c.in = x; c.other = b; c.x = const_cast<double*>(x);
+    c.rtol = rtol; c.atol = atol; c.niter = 0; c.s = (hipStream_t)stream;
+    return krylov_system_call("krylov_system_block_start_transposed", c, npoints, nslices, len, width, soff, col, val, total, nop, m,
+                              coupling, diag, diag_const, workspace, device, true);
+}
+
+int wlsqm_hip_krylov_system_block_bicgstab_transposed_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                             const int64_t* soff, const int32_t* col, const double* val, int64_t total,
+                                                             int nop, int m, const double* coupling, const double* diag,
+                                                             const double* diag_const, int points, const void* planes, double* x,
+                                                             int64_t niter, void* workspace, int device, void* stream) {
+    int rc = krylov_system_block_arguments("krylov_system_block_bicgstab_transposed", m, points, planes, nullptr);
+    if (rc != WLSQM_OK) return rc;
+    if (niter < 0) { set_error("krylov_system_block_bicgstab_transposed: niter must be >= 0"); return WLSQM_EVALUE; }
+    KrylovSystemCall c;
+    c.points = points; c.W = static_cast<const double*>(planes);
+    c.what = SYSTEM_CALL_ITERATE; c.jacobi = 1; c.maxiter = 0;
+    c.in = x; c.other = x; c.x = x;
+    c.rtol = c.atol = 0.0; c.niter = niter; c.s = (hipStream_t)stream;
+    return krylov_system_call("krylov_system_block_bicgstab_transposed", c, npoints, nslices, len, width, soff, col, val, total, nop, m,
+                              coupling, diag, diag_const, workspace, device, true);
+}
+
+// The same for a per-point coupling: wlsqm_hip_krylov_system_point_start_device / _bicgstab_device with the blocks.
+int wlsqm_hip_krylov_system_point_block_start_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                     const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop, int m,
+                                                     const double* coupling, const double* diag, const double* diag_const, int transposed,
+                                                     double* mixed, int points, const void* planes, const double* b, const double* x,
+                                                     double rtol, double atol, int64_t maxiter, void* workspace, int device, void* stream) {
+    int rc = krylov_system_block_arguments("krylov_system_point_block_start", m, points, planes, nullptr);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_tolerances("krylov_system_point_block_start", b, x, rtol, atol, maxiter);
+    if (rc != WLSQM_OK) return rc;
+    KrylovPointCall p;
+    KrylovSystemCall& c = p.c;
+    p.mixed = mixed;
+    c.points = points; c.W = static_cast<const double*>(planes);
+    c.what = SYSTEM_CALL_START; c.jacobi = 1; c.maxiter = (int)maxiter;
+    c.in = x; c.other = b; c.x = const_cast<double*>(x);
+    c.rtol = rtol; c.atol = atol; c.niter = 0; c.s = (hipStream_t)stream;
+    return krylov_point_call("krylov_system_point_block_start", p, npoints, nslices, len, width, soff, col, val, total, nop, m, coupling,
+                             diag, diag_const, transposed, workspace, device);
+}
+
+int wlsqm_hip_krylov_system_point_block_bicgstab_device(int64_t npoints, int64_t nslices, const int32_t* len, const int32_t* width,
+                                                        const int64_t* soff, const int32_t* col, const double* val, int64_t total, int nop,
+                                                        int m, const double* coupling, const double* diag, const double* diag_const,
+                                                        int transposed, double* mixed, int points, const void* planes, double* x,
+                                                        int64_t niter, void* workspace, int device, void* stream) {
+    int rc = krylov_system_block_arguments("krylov_system_point_block_bicgstab", m, points, planes, nullptr);
+    if (rc != WLSQM_OK) return rc;
+    if (niter < 0) { set_error("krylov_system_point_block_bicgstab: niter must be >= 0"); return WLSQM_EVALUE; }
+    KrylovPointCall p;
+    KrylovSystemCall& c = p.c;
+    p.mixed = mixed;
+    c.points = points; c.W = static_cast<const double*>(planes);
+    c.what = SYSTEM_CALL_ITERATE; c.jacobi = 1; c.maxiter = 0;
+    c.in = x; c.other = x; c.x = x;
+    c.rtol = c.atol = 0.0; c.niter = niter; c.s = (hipStream_t)stream;
+    return krylov_point_call("krylov_system_point_block_bicgstab", p, npoints, nslices, len, width, soff, col, val, total, nop, m, coupling,
+                             diag, diag_const, transposed, workspace, device);
 }
 
 }  // extern "C"

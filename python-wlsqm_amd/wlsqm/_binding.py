@@ -293,6 +293,27 @@ def lib():
         L.wlsqm_hip_krylov_system_point_grads_device.argtypes = L.wlsqm_hip_krylov_system_grads_device.argtypes
         for name in ("start", "bicgstab", "product", "grads"):
             getattr(L, "wlsqm_hip_krylov_system_point_%s_device" % name).restype = C.c_int
+    # block-Jacobi over points for coupled fields (wlsqm.hip.PointBlockJacobi): points, planes in jacobi's place
+    if hasattr(L, "wlsqm_hip_krylov_system_block_factor_device"):
+        point = coupled + [C.c_int, C.c_void_p]
+        blocks = [C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_system_block_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
+        L.wlsqm_hip_krylov_system_block_bytes.restype = C.c_int64
+        L.wlsqm_hip_krylov_system_block_factor_device.argtypes = coupled + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_system_block_gather_device.argtypes = coupled + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_system_block_precondition_device.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                                        C.c_void_p]
+        start = L.wlsqm_hip_krylov_system_start_device.argtypes[len(coupled) + 1:]
+        iterate = L.wlsqm_hip_krylov_system_bicgstab_device.argtypes[len(coupled) + 1:]
+        for name in ("system_block_start", "system_block_start_transposed"):
+            getattr(L, "wlsqm_hip_krylov_%s_device" % name).argtypes = coupled + blocks + start
+        for name in ("system_block_bicgstab", "system_block_bicgstab_transposed"):
+            getattr(L, "wlsqm_hip_krylov_%s_device" % name).argtypes = coupled + blocks + iterate
+        L.wlsqm_hip_krylov_system_point_block_start_device.argtypes = point + blocks + start
+        L.wlsqm_hip_krylov_system_point_block_bicgstab_device.argtypes = point + blocks + iterate
+        for name in ("system_block_factor", "system_block_gather", "system_block_precondition", "system_block_start", "system_block_start_transposed",
+                     "system_block_bicgstab", "system_block_bicgstab_transposed", "system_point_block_start", "system_point_block_bicgstab"):
+            getattr(L, "wlsqm_hip_krylov_%s_device" % name).restype = C.c_int
     # batched dense solves (wlsqm.utils.lapackdrivers, wlsqm.hip.*_batched)
     for op in ("getrf", "gesv", "sytrf", "sysv"):
         solve = op in ("gesv", "sysv")

@@ -19,7 +19,7 @@ __all__ = ["fit_many_device", "time_fit_device", "fit_cloud_device", "time_fit_c
            "differentiable_solve", "differentiable_solve_many",
            "InterpolationPlan", "differentiable_evaluate",
            "StencilOperator", "stencil_rows", "differentiable_stencil_apply", "StencilSolver", "StencilSystemSolver", "SolveInfo",
-           "SolveGradients", "BlockJacobi", "ApproximateInverse", "differentiable_stencil_solve", "differentiable_stencil_solve_many",
+           "SolveGradients", "BlockJacobi", "ApproximateInverse", "PointBlockJacobi", "differentiable_stencil_solve", "differentiable_stencil_solve_many",
            "SystemGradients", "differentiable_stencil_system_solve", "SpatialOrder", "last_kernel", "set_strict", "get_strict", "strict", "accurate", "contracted", "strict_intermediates",
            "getrf_batched", "getrs_batched", "gesv_batched", "sytrf_batched", "sytrs_batched", "sysv_batched", "symmetrize_batched"]
 
@@ -2339,6 +2339,30 @@ class ApproximateInverse:
         return "ApproximateInverse(refresh=%r)" % (self.refresh,)
 
 
+class PointBlockJacobi:
+    """The block-Jacobi preconditioner of a StencilSystemSolver: P = blockdiag(M_BB)^-1, the exact inverses of
+    the diagonal blocks of `points` consecutive points with all m unknowns of each — m points consecutive rows of the flat (npoints, m)
+    vectors, the last block cut at npoints.  points counts points, not rows: 1 <= points and m points <= 32; None takes the largest
+    value with m points <= 16 (16 / 8 / 5 / 4 points for m = 1 / 2 / 3 / 4); points=1 is the m x m point-block diagonal.
+    It pays where consecutive points are neighbours in space — a cloud in Morton order (wlsqm.hip.SpatialOrder) — and the more the
+    larger the cloud: on 2D elasticity at 1000 points the reference takes 84 iterations with 16 points per block where "jacobi" takes
+    213.  In 3D ten points are a small cluster and the blocks gain little (39 against 40 at 1000 points).  DESIGN.md section 27 has
+    the counts, which tests/test_krylov_system_block_host.py holds, and what was measured at 10^6 points: an iteration costs 1.08 to
+    1.38 of Jacobi's (what the plane's bytes predict), the factor one to seven iterations at every start (refresh=False: once), and
+    on the Dirichlet elasticity systems the time to solution gained a tenth at best in 2D and lost in 3D.  The plane is
+    8 NB^2 / R bytes per row.
+    refresh: what it means for a BlockJacobi: True recomputes P at the start of every solve / enqueue, False computes it at the first
+    start and again only by solver.refresh()."""
+
+    def __init__(self, points=None, refresh=True):
+        if points is not None and (isinstance(points, bool) or not isinstance(points, int) or points < 1):
+            raise ValueError("points must be None or an int >= 1, the points of a block; got %r" % (points,))
+        self.points, self.refresh = points, bool(refresh)
+
+    def __repr__(self):
+        return "PointBlockJacobi(points=%r, refresh=%r)" % (self.points, self.refresh)
+
+
 class StencilSolver:
     """Solves M x = b with M = diag(d) + scale * A_o, A_o value plane `o` of a square StencilOperator, by BiCGSTAB resident on the
     device (csrc/krylov.hip): eight kernel launches per iteration, two passes over the matrix, every dot product
@@ -2395,6 +2419,9 @@ class StencilSolver:
             raise ValueError("the operator has %d value planes; got o = %d" % (op.nop, int(o)))
         self._block = preconditioner if isinstance(preconditioner, BlockJacobi) else None
         self._spai = preconditioner if isinstance(preconditioner, ApproximateInverse) else None
+        if isinstance(preconditioner, PointBlockJacobi):
+            raise ValueError("a PointBlockJacobi belongs to a StencilSystemSolver, whose blocks count points of m unknowns; a StencilSolver "
+                             "takes a BlockJacobi, whose block counts rows")
         if self._block is None and self._spai is None and preconditioner not in ("jacobi", None):
             raise ValueError("preconditioner must be 'jacobi' or None, or a BlockJacobi or an ApproximateInverse; got %r" % (preconditioner,))
         if self._spai is not None and nfields > 1:
@@ -2997,7 +3024,11 @@ class StencilSystemSolver:
     diag: a float d (D = d I_m), a host (m, m) array-like of constants, or a contiguous float64 device tensor (m, m, npoints), each
     D_ab a diagonal matrix; a tensor is read at every solve (the caller may change it in place).
     preconditioner: "jacobi", the inverse of the scalar diagonal of M — for unknown (i, a): D_aa,i + sum_o coupling[a, a, o] (the sum of
-    row i's own entries in plane o) — or None.  Nothing else: blocks over points are the follow-up that section 24 argues for.
+    row i's own entries in plane o) — None, or a PointBlockJacobi: the exact inverses of the diagonal blocks of
+    `points` consecutive points with all m unknowns of each, for a cloud in Morton order; block_points and block_rows say what it
+    took.  It brings what a BlockJacobi brings to a StencilSolver, under the same conventions: refresh(), precondition(v),
+    preconditioner_blocks(), the transposed plane from prepare_transpose(), status 4 for a block that cannot be inverted.  Its planes
+    are wlsqm_hip_krylov_system_block_bytes(npoints, m, points) bytes each.
 
     Unknowns and right-hand sides are contiguous float64 device tensors (npoints, m): x[i, a] is component a at point i.  For m = 2 and 4
     they are moved by 16-byte loads and must be 16-byte aligned, as every tensor that torch allocates is.
@@ -3005,8 +3036,8 @@ class StencilSystemSolver:
     solve, enqueue and product take transpose=True for M^T, whose block (a, b) is D_ba + sum_o coupling[b, a, o] A_o^T: the same kernels
     on the operator's transposed arrays (prepare_transpose), a diag tensor read in place.  gradients(), coupling_gradient() and
     differentiable_stencil_system_solve carry a loss through the solve.
-    Out of scope (sections 24 to 26): method="bicgstab2", BlockJacobi and ApproximateInverse, nfields, a coupling that scales columns,
-    m > 4, a capturable backward pass, second derivatives, wlsqm.sharded."""
+    Out of scope (sections 24 to 27): method="bicgstab2", BlockJacobi (its block counts rows) and ApproximateInverse, blocks of more
+    than 32 rows, nfields, a coupling that scales columns, m > 4, a capturable backward pass, second derivatives, wlsqm.sharded."""
 
     def __init__(self, op, coupling, diag=0.0, preconditioner="jacobi"):
         import numpy as np
@@ -3019,9 +3050,14 @@ class StencilSystemSolver:
             raise ValueError("the operator must be square: it has %d rows (cases) for %d points" % (op.ncases, op.npoints))
         if op.has_known_derivatives:
             raise ValueError("the operator depends on known DOFs other than F: their affine term belongs in b, build the operator without them")
-        if preconditioner is not None and not (isinstance(preconditioner, str) and preconditioner == "jacobi"):
-            raise ValueError("preconditioner must be 'jacobi' or None for coupled fields; got %r" % (preconditioner,))
-        self._jacobi = 1 if preconditioner == "jacobi" else 0
+        self._block = preconditioner if isinstance(preconditioner, PointBlockJacobi) else None
+        if self._block is None and preconditioner is not None and not (isinstance(preconditioner, str) and preconditioner == "jacobi"):
+            raise ValueError("preconditioner must be 'jacobi' or None, or a PointBlockJacobi, for coupled fields (its blocks count points; "
+                             "a BlockJacobi's count rows); got %r" % (preconditioner,))
+        self._jacobi = 1 if self._block is None and preconditioner == "jacobi" else 0
+        self._planes = self._planes_t = None
+        self._factored = self._factored_t = False
+        self.block_points = self.block_rows = None
         self.per_point = self._is_point_table(coupling)
         self._mixed = None
         if self.per_point:
@@ -3031,6 +3067,11 @@ class StencilSystemSolver:
         m = int(cp.shape[0])
         self.m, self.nop, self.npoints, self._device = m, op.nop, op.npoints, op._device
         self.coupling = cp
+        if self._block is not None:
+            points = 16 // m if self._block.points is None else self._block.points
+            if m * points > 32:
+                raise ValueError("points must be 1 .. %d for m = %d: a block holds m points <= 32 rows; got %d" % (32 // m, m, points))
+            self.block_points, self.block_rows = points, m * points
         if hasattr(diag, "dim"):
             if not hasattr(diag, "is_cuda"):
                 raise ValueError("argument diag must be a device (HIP) tensor")
@@ -3059,6 +3100,13 @@ class StencilSystemSolver:
         self.x = None
         nbytes = int(B.lib().wlsqm_hip_krylov_system_workspace_bytes(self.npoints, m))
         self._ws = torch.zeros((nbytes // 8,), dtype=torch.float64, device=self._device)
+        if self._block is not None:
+            self._planes = self._new_planes()
+
+    def _new_planes(self):
+        import torch
+        nbytes = int(B.lib().wlsqm_hip_krylov_system_block_bytes(self.npoints, self.m, self.block_points))
+        return torch.zeros((nbytes // 8,), dtype=torch.float64, device=self._device)
 
     @staticmethod
     def _coupling_table(coupling, nop, m=None):
@@ -3127,7 +3175,7 @@ class StencilSystemSolver:
 
     def close(self):
         """Release the workspace now; harmless when called again.  The operator and a diag tensor stay the caller's."""
-        self._ws = self._op = self.x = self._mixed = None
+        self._ws = self._op = self.x = self._mixed = self._planes = self._planes_t = None
         if hasattr(self.__dict__.get("diag"), "dim"):
             self.diag = None
         if self.__dict__.get("per_point"):
@@ -3135,16 +3183,97 @@ class StencilSystemSolver:
 
     def memory_used(self):
         """Bytes of device memory the solver holds: the workspace and, for a per-point coupling once a transposed use has allocated
-        it, the mixed plane of m nop npoints doubles.  The coupling tensor is the caller's."""
+        it, the mixed plane of m nop npoints doubles, and the planes of a PointBlockJacobi (wlsqm_hip_krylov_system_block_bytes each; the
+        transposed one from the first transposed use on).  The coupling tensor is the caller's."""
         self._live()
-        return sum(t.numel() * t.element_size() for t in (self._ws, self._mixed) if t is not None)
+        return sum(t.numel() * t.element_size() for t in (self._ws, self._mixed, self._planes, self._planes_t) if t is not None)
 
     def refresh(self, stream=None):
         """The Jacobi diagonal is recomputed from the operator's arrays and the diag tensor as they are on the stream by the start of
         every solve and enqueue, a captured one included: after op.update or an in-place change of diag there is nothing left to call.
-        refresh() says so in code that is written for a preconditioner which needs it; it checks that the solver is live."""
+        refresh() says so in code that is written for a preconditioner which needs it; it checks that the solver is live.
+        With a PointBlockJacobi: its blocks are recomputed now from the operator's arrays, coupling and diag as they are on `stream` —
+        what refresh=False leaves to the caller.  One kernel launch ("krylov-system-blocks"), no allocation, no host read: capturable."""
         self._live()
+        if self._block is not None:
+            s, dev = _stream_and_device(self._planes, stream)
+            self._factor(dev, s, force=True)
         return self
+
+    def _factor(self, dev, s, transpose=False, force=False):
+        """"krylov-system-blocks" when P is due, by StencilSolver._factor's rules: at every start with refresh=True, else at the first one,
+        when the transposed plane is new, and from refresh().  One launch on the forward arrays, the forward coupling and diag, which
+        fills the transposed plane too when this start needs it or, with refresh=False, whenever it exists."""
+        bj = self._block
+        if not (force or bj.refresh or not self._factored or (transpose and not self._factored_t)):
+            return
+        both = self._planes_t is not None and (transpose or not bj.refresh or force)
+        B.check(B.lib().wlsqm_hip_krylov_system_block_factor_device(*self._system(False)[:13], 1 if self.per_point else 0, self.block_points,
+                                                                    _ptr(self._planes), _ptr(self._planes_t) if both else None, dev, s))
+        self._factored = True
+        if both:
+            self._factored_t = True
+        elif bj.refresh:
+            self._factored_t = False
+
+    def _block_args(self, transpose=False):
+        return self.block_points, _ptr(self._planes_t if transpose else self._planes)
+
+    def precondition(self, v, out=None, stream=None, transpose=False):
+        """z = P v (P^T v with transpose=True) on (npoints, m) tensors, P the PointBlockJacobi's block inverses as the next solve would
+        use them: factored first when due (refresh=True: always).  One launch ("krylov-system-precondition") behind the factor's; v and
+        out must not overlap.  ValueError on a solver without blocks."""
+        import torch
+        self._live()
+        if self._block is None:
+            raise ValueError("precondition() belongs to a PointBlockJacobi preconditioner")
+        if out is None:
+            with _torch_stream(stream, self._device):
+                out = torch.empty((self.npoints, self.m), dtype=torch.float64, device=self._device)
+        self._vectors(v=v, out=out)
+        transpose = self._transposed(transpose, stream)
+        s, dev = _stream_and_device(v, stream)
+        self._factor(dev, s, transpose)
+        B.check(B.lib().wlsqm_hip_krylov_system_block_precondition_device(self.npoints, self.m, *self._block_args(transpose), _ptr(v),
+                                                                          _ptr(out), dev, s))
+        return out
+
+    def _blocks_of(self, plane):
+        """(nblocks, R, R) out of a plane in the layout of section 27, as a new tensor."""
+        rows = self.block_rows
+        nb = 8 if rows <= 8 else 16 if rows <= 16 else 32
+        nblocks = (self.npoints + self.block_points - 1) // self.block_points
+        nwaves = (nblocks * nb + 63) // 64
+        W = plane[:nwaves * nb * 64].view(nwaves, nb, 64 // nb, nb)                      # [wave, j, g, l]
+        return W.permute(0, 2, 3, 1).reshape(-1, nb, nb)[:nblocks, :rows, :rows].clone()
+
+    def _matrix_blocks(self, stream=None):
+        """Internal check hook (the tests hold the gather to its bound through it; not part of the supported surface): the
+        diagonal blocks of M themselves, (nblocks, R, R), as the factor gathers them from the operator's arrays, coupling and
+        diag before it inverts them ("krylov-system-blocks" without the elimination, into a plane of its own): for checks.  It
+        allocates, so it is not for a graph capture."""
+        self._live()
+        if self._block is None:
+            raise ValueError("_matrix_blocks() belongs to a PointBlockJacobi preconditioner")
+        s, dev = _stream_and_device(self._planes, stream)
+        with _torch_stream(stream, self._device):
+            plane = self._new_planes()
+            B.check(B.lib().wlsqm_hip_krylov_system_block_gather_device(*self._system(False)[:13], 1 if self.per_point else 0,
+                                                                        self.block_points, _ptr(plane), dev, s))
+            return self._blocks_of(plane)
+
+    def preconditioner_blocks(self, transpose=False, stream=None):
+        """The inverse blocks (of M^T with transpose=True) as a new tensor (nblocks, R, R), nblocks = ceil(npoints / block_points) and
+        R = block_rows, factored first when due; what the cut last block leaves over is the identity.  It allocates the result, so
+        it is not for a graph capture."""
+        self._live()
+        if self._block is None:
+            raise ValueError("preconditioner_blocks() belongs to a PointBlockJacobi preconditioner")
+        transpose = self._transposed(transpose, stream)
+        s, dev = _stream_and_device(self._planes, stream)
+        self._factor(dev, s, transpose)
+        with _torch_stream(stream, self._device):
+            return self._blocks_of(self._planes_t if transpose else self._planes)
 
     def _vector(self, t, name):
         if not hasattr(t, "dim") or not hasattr(t, "is_cuda"):
@@ -3168,6 +3297,9 @@ class StencilSystemSolver:
             held["coupling"] = self.coupling
             if self._mixed is not None:
                 held["the mixed plane"] = self._mixed
+        for name, t in (("the preconditioner's blocks", self._planes), ("the preconditioner's transposed blocks", self._planes_t)):
+            if t is not None:
+                held[name] = t
         names = list(held)
         for i, a in enumerate(names):
             for b in names[i + 1:]:
@@ -3187,8 +3319,10 @@ class StencilSystemSolver:
             return head + (_ptr(self.coupling),) + tail + (1 if transpose else 0, _ptr(self._mixed) if transpose else None)
         return head + (C.cast(self._cp, C.c_void_p),) + tail
 
-    def _call(self, what, transpose):
-        """The C entry point of `what` (start, bicgstab, product) for this solver's kind of table."""
+    def _call(self, what, transpose, block=False):
+        """The C entry point of `what` (start, bicgstab, product) for this solver's kind of table; block: the form that takes the
+        blocks of a PointBlockJacobi (start, bicgstab)."""
+        what = "block_" + what if block else what
         if self.per_point:
             return getattr(B.lib(), "wlsqm_hip_krylov_system_point_%s_device" % what)
         return getattr(B.lib(), "wlsqm_hip_krylov_system_%s%s_device" % (what, "_transposed" if transpose else ""))
@@ -3199,7 +3333,8 @@ class StencilSystemSolver:
     def _transposed(self, transpose, stream):
         """The operator's transposed matrix and a per-point solver's mixed plane, built at the first transposed use (prepare_transpose:
         RuntimeError inside a capture)."""
-        if transpose and (self._op._t is None or (self.per_point and self._mixed is None)):
+        if transpose and (self._op._t is None or (self.per_point and self._mixed is None)
+                          or (self._block is not None and self._planes_t is None)):
             self.prepare_transpose(stream)
         return bool(transpose)
 
@@ -3218,13 +3353,31 @@ class StencilSystemSolver:
                                        "prepare_transpose before the capture")
                 self._mixed = torch.zeros((self.npoints, self.nop, self.m), dtype=torch.float64, device=self._device)
             built = True
+        if self._block is not None and self._planes_t is None:
+            import torch
+            with _torch_stream(stream, self._device):
+                if self._device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("the solver has no transposed preconditioner blocks yet and the stream is capturing: call "
+                                       "prepare_transpose before the capture")
+                self._planes_t = self._new_planes()
+            self._factored_t = False
+            built = True
         return built
 
     def _start(self, b, x, rtol, atol, maxiter, dev, s, transpose=False):
+        if self._block is not None:
+            self._factor(dev, s, transpose)
+            B.check(self._call("start", transpose, True)(*self._system(transpose), *self._block_args(transpose), _ptr(b), _ptr(x), rtol,
+                                                         atol, maxiter, _ptr(self._ws), dev, s))
+            return
         B.check(self._call("start", transpose)(*self._system(transpose), self._jacobi, _ptr(b), _ptr(x), rtol, atol, maxiter,
                                                _ptr(self._ws), dev, s))
 
     def _iterate(self, x, niter, dev, s, transpose=False):
+        if self._block is not None:
+            B.check(self._call("bicgstab", transpose, True)(*self._system(transpose), *self._block_args(transpose), _ptr(x), niter,
+                                                            _ptr(self._ws), dev, s))
+            return
         B.check(self._call("bicgstab", transpose)(*self._system(transpose), self._jacobi, _ptr(x), niter, _ptr(self._ws), dev, s))
 
     def enqueue(self, b, x, iterations, rtol=1e-10, atol=0.0, stream=None, transpose=False):
