@@ -787,6 +787,54 @@ int wlsqm_hip_krylov_spai_iterate_device(int64_t nrows, int64_t nslices, const i
                                          const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
                                          int l2, const void* planes, double* x, int64_t niter, void* workspace, int device, void* stream);
 
+/* ---- overlapping blocks: a restricted additive Schwarz preconditioner of those solves (extension; csrc/krylov.hip) ----
+ * Block B is rows B * block .. B * block + block - 1 of M (block one of 8, 16, 32; the last block cut at nrows: cnt rows).  Its set ext_B
+ * is those rows followed by at most rows - cnt others in ascending order (rows one of 32, 64, rows > block), which the caller chooses:
+ *   table[B * rows + p]   int32   position p of ext_B, ceil(nrows / block) * rows of them on the device; -1: none.  The positions p < cnt
+ *                                 are read as B * block + p whatever the table holds, and an entry outside 0 .. nrows - 1 or inside the
+ *                                 block's own range counts as -1, so no table can make a kernel read out of bounds.  The entries
+ *                                 behind the block's own must be ascending and distinct, the -1s last: the kernels find a column by
+ *                                 a binary search of that list, and in a table that is not sorted an entry that the search misses
+ *                                 is left out of A_B without an error (still a valid preconditioner, not the documented one).
+ * A_B = M[ext_B, ext_B], entry (p, q) = d_ext[p] where ext[p] == ext[q], plus scale * (the sum of row ext[p]'s entries in column ext[q], in
+ * entry order); a -1 position is an identity row and column.  P keeps the block's own rows of the exact inverse,
+ *   z[B * block + i] = sum_q W_B[i][q] * v[ext_B[q]],  W_B the first cnt rows of A_B^-1,  q ascending with fma, 0.0 for v at a -1:
+ * every row of z is written by one block (no scatter, no atomics), which is what "restricted" means.  The solves stay right-preconditioned.
+ * The plane: wlsqm_hip_krylov_schwarz_bytes(nrows, block, rows) bytes of device memory, 8-byte aligned,
+ *   W[(slice * rows + q) * 64 + lane]   float64   entry (lane % block, q) of W_B for the block that holds row slice * 64 + lane,
+ * nslices * rows * 64 doubles, so that a wave reads column q of its slice as one contiguous run of 512 bytes; zeros in the rows beyond
+ * nrows.  Behind them nslices * (64 / block) doubles, one per block position: 1.0 where the last build could not invert the block.
+ *
+ * wlsqm_hip_krylov_schwarz_build_device ("krylov-schwarz-build", one launch): one wave per block, lane p gathering row ext[p] from whatever
+ *   slice holds it, then Gauss-Jordan elimination in LDS by the pivoting rule of wlsqm_hip_krylov_block_factor_device (the largest entry of
+ *   the column among the rows not yet used, the lowest row at a tie).  planes_t (nullable): a second plane that receives the first cnt rows
+ *   of (A_B^T)^-1 from the same elimination: the same preconditioner of M^T on the same sets (not P^T, whose application would scatter).
+ *   A zero or non-finite pivot or a non-finite inverse counts the block as unusable: never a fault, and the next start answers status 4
+ *   with x as given.  No scratch memory.
+ * wlsqm_hip_krylov_schwarz_apply_device ("krylov-schwarz-apply", one launch): out = P v; a wave serves a slice, gathers v[ext[q]] of its
+ *   64 / block blocks once into LDS and reads the plane column by column.  v and out must not overlap.
+ * wlsqm_hip_krylov_schwarz_start_device / _iterate_device: wlsqm_hip_krylov_spai_start_device / _iterate_device with this P: l2 == 0,
+ *   `niter` iterations of 10 launches ("krylov-schwarz-update"); l2 != 0, `niter` cycles of 19 launches ("krylov-schwarz-l2-update").  P is
+ *   applied by launches of its own because a block reads rows that other workgroups of an update launch would still be writing.  For M^T
+ *   pass the transposed matrix with the transposed plane and the same table.
+ * WLSQM_EVALUE as above, and for another block or rows. */
+int64_t wlsqm_hip_krylov_schwarz_bytes(int64_t nrows, int block, int rows);
+int wlsqm_hip_krylov_schwarz_build_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                          const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                          int block, int rows, const int32_t* table, void* planes, void* planes_t, int device,
+                                          void* stream);
+int wlsqm_hip_krylov_schwarz_apply_device(int64_t nrows, int block, int rows, const int32_t* table, const void* planes, const double* v,
+                                          double* out, int device, void* stream);
+int wlsqm_hip_krylov_schwarz_start_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                          const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                          int l2, int block, int rows, const int32_t* table, const void* planes, const double* b,
+                                          const double* x, double rtol, double atol, int64_t maxiter, void* workspace, int device,
+                                          void* stream);
+int wlsqm_hip_krylov_schwarz_iterate_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                            const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                            int l2, int block, int rows, const int32_t* table, const void* planes, double* x,
+                                            int64_t niter, void* workspace, int device, void* stream);
+
 /* ---- coupled fields: implicit solves with m unknowns per point (extension; csrc/krylov.hip) ----
  * BiCGSTAB on M x = b with block (a, b) of M = D_ab + sum_o coupling[a][b][o] * A_o, 1 <= m <= 4 unknowns per point, A_o the nop <= 8
  * value planes of a SQUARE matrix in the SELL-64 layout above (`val` points at plane 0, plane o at val + o * total).  coupling: HOST

@@ -1569,19 +1569,21 @@ static void krylov_spai_apply(const KrylovSys& q, long long nwg, const double* i
     hipLaunchKernelGGL(krylov_spai_apply_kernel, dim3((unsigned)nwg), dim3(256), 0, s, q, in, out, acc, sc, always);
 }
 
-// An iteration of BiCGSTAB with P = Q: krylov_update_kernel without a diagonal, and phat = Q p, shat = Q s by launches of their own.
-static void krylov_spai_iterations(const KrylovSys& m, const KrylovSys& q, const KrylovWork& w, double* x, int64_t niter, hipStream_t s) {
+// An iteration of BiCGSTAB with a P that launches of its own apply (Q here, the overlapping blocks of section 28): krylov_update_kernel
+// without a diagonal, then phat = P p and shat = P s by apply(in, out, acc): out = P in, or acc += P in.
+template <class Apply>
+static void krylov_applied_iterations(const KrylovSys& m, const Apply& apply, const KrylovWork& w, double* x, int64_t niter, hipStream_t s) {
     const dim3 grid((unsigned)w.nwg), block(256);
     const KrylovScalars* sc = w.sc;
     const long long nrows = m.nrows;
     double* const none = nullptr;
     for (int64_t it = 0; it < niter; ++it) {
         hipLaunchKernelGGL((krylov_update_kernel<UPDATE_P>), grid, block, 0, s, nrows, w, x, sc);
-        krylov_spai_apply(q, w.nwg, w.p, w.phat, none, sc, 0, s);
+        apply((const double*)w.p, w.phat, none);
         hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_V>), grid, block, 0, s, m, (const double*)w.phat, (const double*)w.r0, w.v, none, w.partial, sc, 0);
         krylov_reduce(REDUCE_ALPHA, w, w.nwg, 1, 0.0, 0.0, 0, s);
         hipLaunchKernelGGL((krylov_update_kernel<UPDATE_S>), grid, block, 0, s, nrows, w, x, sc);
-        krylov_spai_apply(q, w.nwg, w.s, w.shat, none, sc, 0, s);
+        apply((const double*)w.s, w.shat, none);
         hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_T>), grid, block, 0, s, m, (const double*)w.shat, (const double*)w.s, w.t, none, w.partial, sc, 0);
         krylov_reduce(REDUCE_OMEGA, w, w.nwg, 2, 0.0, 0.0, 0, s);
         hipLaunchKernelGGL((krylov_update_kernel<UPDATE_X>), grid, block, 0, s, nrows, w, x, sc);
@@ -1589,11 +1591,12 @@ static void krylov_spai_iterations(const KrylovSys& m, const KrylovSys& q, const
     }
 }
 
-// A cycle of BiCGSTAB(2) with P = Q, 19 launches: every update leaves what P is applied to in `pre` (the workspace's tenth vector), an
-// apply forms hat = Q pre for the product behind it, and the last one adds Q pre to x: between U4, which every check of the cycle's
+// A cycle of BiCGSTAB(2) with such a P, 19 launches: every update leaves what P is applied to in `pre` (the workspace's tenth vector), an
+// apply forms hat = P pre for the product behind it, and the last one adds P pre to x: between U4, which every check of the cycle's
 // scalars precedes, and the reduce that takes the stop.
-static void krylov_spai_l2_cycles(const KrylovSys& m, const KrylovSys& q, const KrylovL2Work& w, double* pre, double* x, int64_t ncycles,
-                                  hipStream_t s) {
+template <class Apply>
+static void krylov_applied_l2_cycles(const KrylovSys& m, const Apply& applied, const KrylovL2Work& w, double* pre, double* x, int64_t ncycles,
+                                     hipStream_t s) {
     const dim3 grid((unsigned)w.nwg), block(256);
     const KrylovScalars* sc = w.sc;
     const long long nrows = m.nrows;
@@ -1604,7 +1607,7 @@ static void krylov_spai_l2_cycles(const KrylovSys& m, const KrylovSys& q, const 
     auto reduce = [&](int mode) {
         hipLaunchKernelGGL(krylov_l2_reduce_kernel, dim3(1), block, 0, s, mode, (const double*)w.partial, w.nwg, w.sc, 0.0, 0.0);
     };
-    auto apply = [&](double* acc) { krylov_spai_apply(q, w.nwg, pre, w.hat, acc, sc, 0, s); };
+    auto apply = [&](double* acc) { applied((const double*)pre, w.hat, acc); };
     for (int64_t it = 0; it < ncycles; ++it) {
         hipLaunchKernelGGL((krylov_l2_update_kernel<0, L2_U0>), grid, block, 0, s, nrows, u, W, none);
         apply(none);
@@ -1628,6 +1631,44 @@ static void krylov_spai_l2_cycles(const KrylovSys& m, const KrylovSys& q, const 
     }
 }
 
+// The iterations (l2: the cycles) of a solve whose P is applied by launches of its own, on the method's own workspace.
+template <class Apply>
+static void krylov_applied_run(const KrylovSys& m, const Apply& apply, int l2, double* x, int64_t niter, void* workspace, hipStream_t s) {
+    if (l2) {
+        KrylovL2Work w = krylov_l2_work(workspace, m.nrows, 1);
+        krylov_applied_l2_cycles(m, apply, w, w.dinv, x, niter, s);
+    } else {
+        KrylovWork w = krylov_work(workspace, m.nrows, true);
+        w.dinv = nullptr;                                        // the update kernels form p and s only
+        krylov_applied_iterations(m, apply, w, x, niter, s);
+    }
+}
+
+// The start of such a solve: the `ncounts` counts of what the last build could not use into status 4, then the residual and its stop.
+static int krylov_applied_start(const KrylovSys& m, const double* counts, long long ncounts, int l2, const double* b, const double* x,
+                                double rtol, double atol, int64_t maxiter, void* workspace, hipStream_t s) {
+    const long long nrows = m.nrows, nwg = (nrows + 255) / 256;
+    const dim3 grid((unsigned)nwg);
+    KrylovScalars* sc = static_cast<KrylovScalars*>(workspace);
+    hipLaunchKernelGGL(krylov_reduce_kernel, dim3(1), dim3(256), 0, s, (int)REDUCE_DIAG, counts, ncounts, 1, sc, rtol, atol, (int)maxiter);
+    if (l2) {
+        const KrylovL2Work w = krylov_l2_work(workspace, nrows, 1);
+        hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_RESIDUAL>), grid, dim3(256), 0, s, m, x, b, w.r, w.rt, w.partial, (const KrylovScalars*)sc, 0);
+        note_kernel("krylov-spmv-dot");
+        hipLaunchKernelGGL(krylov_l2_reduce_kernel, dim3(1), dim3(256), 0, s, (int)L2_START, (const double*)w.partial, w.nwg, sc, rtol, atol);
+        WLSQM_HIP_CHECK(hipGetLastError());
+        note_kernel("krylov-l2-reduce");
+        return WLSQM_OK;
+    }
+    const KrylovWork w = krylov_work(workspace, nrows, true);
+    hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_RESIDUAL>), grid, dim3(256), 0, s, m, x, b, w.r, w.r0, w.partial, (const KrylovScalars*)sc, 0);
+    note_kernel("krylov-spmv-dot");
+    krylov_reduce(REDUCE_RESIDUAL, w, w.nwg, 2, rtol, atol, (int)maxiter, s);
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-reduce");
+    return WLSQM_OK;
+}
+
 static int krylov_spai_arguments(const char* who, int64_t nrows, int64_t nslices, const void* planes) {
     if (!planes) { set_error(std::string(who) + ": null array"); return WLSQM_EVALUE; }
     if (nslices != (nrows + 63) / 64) { set_error(std::string(who) + ": nslices must be ceil(nrows / 64)"); return WLSQM_EVALUE; }
@@ -1641,6 +1682,195 @@ static int krylov_tolerances(const char* who, const void* b, const void* x, doub
         return WLSQM_EVALUE;
     }
     if (maxiter < 0 || maxiter > INT32_MAX) { set_error(std::string(who) + ": maxiter must be 0 .. 2^31 - 1"); return WLSQM_EVALUE; }
+    return WLSQM_OK;
+}
+
+// ---- overlapping blocks: a restricted additive Schwarz preconditioner ------------------------------------------
+// Block B is the rows B NB .. B NB + NB - 1, cut at nrows (cnt of them).  Its set ext_B is those rows followed by up to ROWS - cnt others,
+// ascending, which the caller's table names (int32, (nblocks, ROWS), -1 where there are none; the block's own positions are taken from
+// B, not from the table, and an entry that is no row, or one of the block's own, counts as -1; ascending order is the caller's to keep:
+// a column is found by a binary search, and one that the search misses in an unsorted list is left out of A_B).  A_B = M[ext_B, ext_B], a -1 position an
+// identity row and column, is inverted exactly and the first cnt rows of the inverse are kept: z[B NB + i] = sum_q W_B[i][q] v[ext_B[q]].
+// The plane: W[(slice * ROWS + q) * 64 + lane] = entry (lane % NB, q) of W_B for the block that holds row slice * 64 + lane, so that a
+// wave reads column q of its slice as one contiguous run of 512 bytes; zeros in the rows beyond nrows.  Behind the nslices * ROWS * 64
+// doubles sit nslices * (64 / NB) more: per block position 1.0 where the last build could not invert, which every start reduces into
+// status 4.  The transposed plane holds the first cnt rows of (A_B^T)^-1, the same preconditioner of M^T, from the same elimination.
+
+struct KrylovSchwarz {
+    int nb, rows;
+    long long nblocks, nslots;          // the blocks of the matrix; the block positions of the plane, nslices * (64 / nb)
+    double *W, *counts;
+};
+
+static KrylovSchwarz krylov_schwarz_planes(const void* planes, long long nrows, long long nslices, int nb, int rows) {
+    double* base = static_cast<double*>(const_cast<void*>(planes));
+    return KrylovSchwarz{nb, rows, (nrows + nb - 1) / nb, nslices * (64 / nb), base, base ? base + nslices * rows * 64 : nullptr};
+}
+
+// Position p of ext_B, or -1: `first` the block's first row, cnt its rows.
+__device__ __forceinline__ long long krylov_schwarz_ext(const int32_t* table, long long B, int rows, int p, long long first, int cnt,
+                                                        long long nrows) {
+    if (p < cnt) return first + p;
+    const long long r = table[B * rows + p];
+    return r < 0 || r >= nrows || (r >= first && r < first + cnt) ? -1 : r;
+}
+
+// One wave per block, lane p the owner of row ext[p]: it looks its slice up by itself (the rows of a set lie in any slice), zeroes row p
+// of the LDS image (ROWS x ROWS at the pitch ROWS + 1: a column is read without a bank conflict), and adds every stored entry whose
+// column the set names onto (p, position), in entry order: the block's own columns by their range, the others by a binary search of the
+// ascending rest of the list in LDS.  Then entry (p, q) = d delta_pq + c sum, as krylov_blocks_kernel forms it.
+// The elimination is that kernel's, in place: Gauss-Jordan with partial pivoting, at step k the largest |entry k| among the rows that
+// have not been a pivot, the lowest row at a tie, a NaN the largest; the pivot row times 1 / pivot goes through `prow` (with 1 / pivot
+// in place k: column k of the image is a unit vector from here on, so it holds the column of the inverse that starts at this step), and
+// every other lane eliminates its own row with fma.  Rows are not moved: entry (i, c) of the inverse ends at (who[i], step[c]), who[k]
+// the pivot row of step k and step[r] the step of row r.  A zero or non-finite pivot or a non-finite entry counts the block as unusable.
+template <int ROWS>
+__global__ void __launch_bounds__(64) krylov_schwarz_build_kernel(const KrylovSys m, const KrylovSchwarz p, const int32_t* table, double* WT,
+                                                                  double* counts_t) {
+    constexpr int PITCH = ROWS + 1;
+    __shared__ double a[ROWS * PITCH];
+    __shared__ double prow[ROWS];
+    __shared__ int32_t ext[ROWS], who_of[ROWS], step_of[ROWS];
+    const int lane = threadIdx.x, nb = p.nb, bps = 64 / nb;
+    const long long B = blockIdx.x, first = B * nb;
+    const long long left = m.nrows - first;
+    const int cnt = B >= p.nblocks || left <= 0 ? 0 : left < nb ? (int)left : nb;
+    const int i_out = lane % nb, q_out = lane / nb;
+    double* w = p.W + ((B / bps) * ROWS) * 64 + (B % bps) * nb + i_out;
+    double* wt = WT ? WT + ((B / bps) * ROWS) * 64 + (B % bps) * nb + i_out : nullptr;
+    if (cnt == 0) {                                              // uniform: a block position beyond the matrix
+        for (int q = q_out; q < ROWS; q += bps) { w[64LL * q] = 0.0; if (wt) wt[64LL * q] = 0.0; }
+        if (lane == 0) { p.counts[B] = 0.0; if (counts_t) counts_t[B] = 0.0; }
+        return;
+    }
+    const bool owner = lane < ROWS;
+    const long long r = owner ? krylov_schwarz_ext(table, B, ROWS, lane, first, cnt, m.nrows) : -1;
+    if (owner) {
+        ext[lane] = r < 0 ? INT32_MAX : (int32_t)r;              // a -1 sorts behind every row
+        for (int q = 0; q < ROWS; ++q) a[lane * PITCH + q] = 0.0;
+    }
+    __syncthreads();
+    if (r >= 0) {
+        const long long sr = r >> 6, at = m.soff[sr] + (r & 63);
+        const int wid = m.width[sr];
+        int n = m.len[r];
+        n = n < wid ? n : wid;
+        for (int e = 0; e < n; ++e) {
+            const long long c = m.col[at + 64LL * e];
+            int q = -1;
+            if (c >= first && c < first + cnt) {
+                q = (int)(c - first);
+            } else {
+                int lo = cnt, hi = ROWS;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (ext[mid] < c) lo = mid + 1; else hi = mid;
+                }
+                if (lo < ROWS && ext[lo] == c) q = lo;
+            }
+            if (q >= 0) a[lane * PITCH + q] += m.val[at + 64LL * e];
+        }
+    }
+    if (owner) {
+        const double d = r >= 0 ? (m.dvec ? m.dvec[r] : m.dconst) : 1.0;
+        for (int q = 0; q < ROWS; ++q) {
+            const double dq = q == lane ? d : 0.0;
+            a[lane * PITCH + q] = r >= 0 ? dq + m.c * a[lane * PITCH + q] : dq;
+        }
+    }
+    __syncthreads();
+    bool used = false, unusable = false;
+    for (int k = 0; k < ROWS; ++k) {                             // uniform
+        const double f = owner ? a[lane * PITCH + k] : 0.0;
+        const double mag = __builtin_fabs(f);
+        double key = !owner ? -2.0 : used ? -1.0 : (mag != mag ? __builtin_inf() : mag);
+        int who = lane;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const double okey = __shfl_xor(key, off, 64);
+            const int owho = __shfl_xor(who, off, 64);
+            if (okey > key || (okey == key && owho < who)) { key = okey; who = owho; }
+        }
+        const double pv = __shfl(f, who, 64);
+        if (!(pv != 0.0 && __builtin_isfinite(pv))) unusable = true;
+        const double pinv = 1.0 / pv;
+        const bool mine = lane == who;
+        if (mine) { used = true; who_of[k] = lane; step_of[lane] = k; }
+        if (owner) prow[lane] = lane == k ? pinv : a[who * PITCH + lane] * pinv;
+        __syncthreads();
+        if (owner) {
+            for (int j = 0; j < ROWS; ++j) {
+                const double old = j == k ? 0.0 : a[lane * PITCH + j];
+                a[lane * PITCH + j] = mine ? prow[j] : __builtin_fma(-f, prow[j], old);
+            }
+        }
+        __syncthreads();
+    }
+    if (owner)
+        for (int j = 0; j < ROWS; ++j)
+            if (!__builtin_isfinite(a[lane * PITCH + j])) unusable = true;
+    const bool bad = __any(unusable);
+    if (lane == 0) { p.counts[B] = bad ? 1.0 : 0.0; if (counts_t) counts_t[B] = bad ? 1.0 : 0.0; }
+    const bool kept = i_out < cnt;
+    const int wi = kept ? who_of[i_out] : 0, si = kept ? step_of[i_out] : 0;
+    for (int q = q_out; q < ROWS; q += bps) {
+        w[64LL * q] = kept ? a[wi * PITCH + step_of[q]] : 0.0;
+        if (wt) wt[64LL * q] = kept ? a[who_of[q] * PITCH + si] : 0.0;
+    }
+}
+
+// out = P in, or (acc) acc += P in.  A wave serves the 64 rows of a slice, 64 / NB blocks: it gathers in[ext[q]] of each block once into
+// LDS (0.0 at a -1), then z_lane = sum_q W[.., q, lane] * gathered[block of the lane][q], q ascending with fma.
+template <int ROWS>
+__global__ void __launch_bounds__(256) krylov_schwarz_apply_kernel(long long nrows, const KrylovSchwarz p, const int32_t* table,
+                                                                   const double* in, double* out, double* acc, const KrylovScalars* sc,
+                                                                   int always) {
+    if (!always && sc->done) return;                             // uniform: the whole grid
+    constexpr int PITCH = ROWS + 1;                              // the blocks of a wave read different banks
+    __shared__ double gathered[4][8 * PITCH];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nb = p.nb, bps = 64 / nb;
+    const long long s = (long long)blockIdx.x * 4 + wave;
+    const bool active = s * 64 < nrows;                          // wave-uniform
+    if (active) {
+        for (int t = lane; t < bps * ROWS; t += 64) {
+            const int b = t / ROWS, q = t - b * ROWS;
+            const long long B = s * bps + b, first = B * nb, left = nrows - first;
+            const int cnt = left <= 0 ? 0 : left < nb ? (int)left : nb;
+            const long long r = cnt ? krylov_schwarz_ext(table, B, ROWS, q, first, cnt, nrows) : -1;
+            gathered[wave][b * PITCH + q] = r >= 0 ? in[r] : 0.0;
+        }
+    }
+    __syncthreads();
+    if (!active) return;
+    const long long row = s * 64 + lane;
+    const double* w = p.W + (s * ROWS) * 64 + lane;
+    const double* g = gathered[wave] + (lane / nb) * PITCH;
+    double z = 0.0;
+#pragma unroll 8
+    for (int q = 0; q < ROWS; ++q) z = __builtin_fma(w[64LL * q], g[q], z);
+    if (row < nrows) {
+        if (acc) acc[row] = acc[row] + z;
+        else out[row] = z;
+    }
+}
+
+static void krylov_schwarz_apply(const KrylovSchwarz& p, const int32_t* table, long long nrows, const double* in, double* out, double* acc,
+                                 const KrylovScalars* sc, int always, hipStream_t s) {
+    const dim3 grid((unsigned)((nrows + 255) / 256));
+    if (p.rows == 32) hipLaunchKernelGGL(krylov_schwarz_apply_kernel<32>, grid, dim3(256), 0, s, nrows, p, table, in, out, acc, sc, always);
+    else hipLaunchKernelGGL(krylov_schwarz_apply_kernel<64>, grid, dim3(256), 0, s, nrows, p, table, in, out, acc, sc, always);
+}
+
+static int krylov_schwarz_arguments(const char* who, int64_t nrows, int64_t nslices, int block, int rows, const void* table,
+                                    const void* planes) {
+    if (block != 8 && block != 16 && block != 32) { set_error(std::string(who) + ": block must be 8, 16 or 32"); return WLSQM_EVALUE; }
+    if ((rows != 32 && rows != 64) || rows <= block) {
+        set_error(std::string(who) + ": rows must be 32 or 64, and more than block");
+        return WLSQM_EVALUE;
+    }
+    if (!table || !planes) { set_error(std::string(who) + ": null array"); return WLSQM_EVALUE; }
+    if (nrows < 1 || nslices != (nrows + 63) / 64) { set_error(std::string(who) + ": nslices must be ceil(nrows / 64)"); return WLSQM_EVALUE; }
+    if (nslices * (64 / block) > 0x7fffffffLL) { set_error(std::string(who) + ": too many blocks for one launch"); return WLSQM_EVALUE; }
     return WLSQM_OK;
 }
 
@@ -3174,29 +3404,8 @@ int wlsqm_hip_krylov_spai_start_device(int64_t nrows, int64_t nslices, const int
     DeviceScope scope;
     rc = scope.enter(device);
     if (rc != WLSQM_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
     const KrylovSpai p = krylov_spai_planes(planes, nrows);
-    const long long nwg = (nrows + 255) / 256;
-    const dim3 grid((unsigned)nwg);
-    KrylovScalars* sc = static_cast<KrylovScalars*>(workspace);
-    hipLaunchKernelGGL(krylov_reduce_kernel, dim3(1), dim3(256), 0, s, (int)REDUCE_DIAG, (const double*)p.counts, (long long)nslices, 1, sc, rtol,
-                       atol, (int)maxiter);
-    if (l2) {
-        const KrylovL2Work w = krylov_l2_work(workspace, nrows, 1);
-        hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_RESIDUAL>), grid, dim3(256), 0, s, m, x, b, w.r, w.rt, w.partial, (const KrylovScalars*)sc, 0);
-        note_kernel("krylov-spmv-dot");
-        hipLaunchKernelGGL(krylov_l2_reduce_kernel, dim3(1), dim3(256), 0, s, (int)L2_START, (const double*)w.partial, w.nwg, sc, rtol, atol);
-        WLSQM_HIP_CHECK(hipGetLastError());
-        note_kernel("krylov-l2-reduce");
-        return WLSQM_OK;
-    }
-    const KrylovWork w = krylov_work(workspace, nrows, true);
-    hipLaunchKernelGGL((krylov_spmv_kernel<SPMV_RESIDUAL>), grid, dim3(256), 0, s, m, x, b, w.r, w.r0, w.partial, (const KrylovScalars*)sc, 0);
-    note_kernel("krylov-spmv-dot");
-    krylov_reduce(REDUCE_RESIDUAL, w, w.nwg, 2, rtol, atol, (int)maxiter, s);
-    WLSQM_HIP_CHECK(hipGetLastError());
-    note_kernel("krylov-reduce");
-    return WLSQM_OK;
+    return krylov_applied_start(m, p.counts, nslices, l2, b, x, rtol, atol, maxiter, workspace, (hipStream_t)stream);
 }
 
 int wlsqm_hip_krylov_spai_iterate_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
@@ -3214,16 +3423,99 @@ int wlsqm_hip_krylov_spai_iterate_device(int64_t nrows, int64_t nslices, const i
     if (rc != WLSQM_OK || niter == 0) return rc;
     hipStream_t s = (hipStream_t)stream;
     const KrylovSys q = krylov_spai_system(m, krylov_spai_planes(planes, nrows));
-    if (l2) {
-        KrylovL2Work w = krylov_l2_work(workspace, nrows, 1);
-        krylov_spai_l2_cycles(m, q, w, w.dinv, x, niter, s);
-    } else {
-        KrylovWork w = krylov_work(workspace, nrows, true);
-        w.dinv = nullptr;                                        // the update kernels form p and s only
-        krylov_spai_iterations(m, q, w, x, niter, s);
-    }
+    const long long nwg = (nrows + 255) / 256;
+    const KrylovScalars* sc = static_cast<const KrylovScalars*>(workspace);
+    krylov_applied_run(m, [&](const double* in, double* out, double* acc) { krylov_spai_apply(q, nwg, in, out, acc, sc, 0, s); }, l2, x,
+                       niter, workspace, s);
     WLSQM_HIP_CHECK(hipGetLastError());
     note_kernel(l2 ? "krylov-spai-l2-update" : "krylov-spai-update");
+    return WLSQM_OK;
+}
+
+int64_t wlsqm_hip_krylov_schwarz_bytes(int64_t nrows, int block, int rows) {
+    if (nrows < 0 || (block != 8 && block != 16 && block != 32) || (rows != 32 && rows != 64) || rows <= block) return -1;
+    const int64_t nslices = (nrows + 63) / 64;
+    return (int64_t)sizeof(double) * (nslices * rows * 64 + nslices * (64 / block));
+}
+
+int wlsqm_hip_krylov_schwarz_build_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                          const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                          int block, int rows, const int32_t* table, void* planes, void* planes_t, int device,
+                                          void* stream) {
+    KrylovSys m;
+    int rc = krylov_schwarz_arguments("krylov_schwarz_build", nrows, nslices, block, rows, table, planes);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_system("krylov_schwarz_build", m, nrows, nslices, len, width, soff, col, val, diag, diag_const, scale, planes);
+    if (rc != WLSQM_OK) return rc;
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const KrylovSchwarz p = krylov_schwarz_planes(planes, nrows, nslices, block, rows);
+    const KrylovSchwarz t = krylov_schwarz_planes(planes_t, nrows, nslices, block, rows);
+    const dim3 grid((unsigned)p.nslots);
+    if (rows == 32) hipLaunchKernelGGL(krylov_schwarz_build_kernel<32>, grid, dim3(64), 0, s, m, p, table, t.W, t.counts);
+    else hipLaunchKernelGGL(krylov_schwarz_build_kernel<64>, grid, dim3(64), 0, s, m, p, table, t.W, t.counts);
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-schwarz-build");
+    return WLSQM_OK;
+}
+
+int wlsqm_hip_krylov_schwarz_apply_device(int64_t nrows, int block, int rows, const int32_t* table, const void* planes, const double* v,
+                                          double* out, int device, void* stream) {
+    int rc = krylov_schwarz_arguments("krylov_schwarz_apply", nrows, (nrows + 63) / 64, block, rows, table, planes);
+    if (rc != WLSQM_OK) return rc;
+    if (!v || !out) { set_error("krylov_schwarz_apply: null array"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    krylov_schwarz_apply(krylov_schwarz_planes(planes, nrows, (nrows + 63) / 64, block, rows), table, nrows, v, out, nullptr, nullptr, 1,
+                         (hipStream_t)stream);
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel("krylov-schwarz-apply");
+    return WLSQM_OK;
+}
+
+int wlsqm_hip_krylov_schwarz_start_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                          const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                          int l2, int block, int rows, const int32_t* table, const void* planes, const double* b,
+                                          const double* x, double rtol, double atol, int64_t maxiter, void* workspace, int device,
+                                          void* stream) {
+    KrylovSys m;
+    int rc = krylov_schwarz_arguments("krylov_schwarz_start", nrows, nslices, block, rows, table, planes);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_system("krylov_schwarz_start", m, nrows, nslices, len, width, soff, col, val, diag, diag_const, scale, workspace);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_tolerances("krylov_schwarz_start", b, x, rtol, atol, maxiter);
+    if (rc != WLSQM_OK) return rc;
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK) return rc;
+    const KrylovSchwarz p = krylov_schwarz_planes(planes, nrows, nslices, block, rows);
+    return krylov_applied_start(m, p.counts, p.nslots, l2, b, x, rtol, atol, maxiter, workspace, (hipStream_t)stream);
+}
+
+int wlsqm_hip_krylov_schwarz_iterate_device(int64_t nrows, int64_t nslices, const int32_t* len, const int32_t* width, const int64_t* soff,
+                                            const int32_t* col, const double* val, const double* diag, double diag_const, double scale,
+                                            int l2, int block, int rows, const int32_t* table, const void* planes, double* x,
+                                            int64_t niter, void* workspace, int device, void* stream) {
+    KrylovSys m;
+    int rc = krylov_schwarz_arguments("krylov_schwarz_iterate", nrows, nslices, block, rows, table, planes);
+    if (rc != WLSQM_OK) return rc;
+    rc = krylov_system("krylov_schwarz_iterate", m, nrows, nslices, len, width, soff, col, val, diag, diag_const, scale, workspace);
+    if (rc != WLSQM_OK) return rc;
+    if (!x) { set_error("krylov_schwarz_iterate: null array"); return WLSQM_EVALUE; }
+    if (niter < 0) { set_error("krylov_schwarz_iterate: niter must be >= 0"); return WLSQM_EVALUE; }
+    DeviceScope scope;
+    rc = scope.enter(device);
+    if (rc != WLSQM_OK || niter == 0) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const KrylovSchwarz p = krylov_schwarz_planes(planes, nrows, nslices, block, rows);
+    const KrylovScalars* sc = static_cast<const KrylovScalars*>(workspace);
+    krylov_applied_run(m, [&](const double* in, double* out, double* acc) { krylov_schwarz_apply(p, table, nrows, in, out, acc, sc, 0, s); },
+                       l2, x, niter, workspace, s);
+    WLSQM_HIP_CHECK(hipGetLastError());
+    note_kernel(l2 ? "krylov-schwarz-l2-update" : "krylov-schwarz-update");
     return WLSQM_OK;
 }
 

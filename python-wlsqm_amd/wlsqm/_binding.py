@@ -263,6 +263,19 @@ def lib():
         L.wlsqm_hip_krylov_spai_iterate_device.argtypes = system + [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
         for name in ("build", "apply", "start", "iterate"):
             getattr(L, "wlsqm_hip_krylov_spai_%s_device" % name).restype = C.c_int
+    # the overlapping blocks of those solves (wlsqm.hip.OverlappingBlocks)
+    if hasattr(L, "wlsqm_hip_krylov_schwarz_build_device"):
+        system = [C.c_int64, C.c_int64] + [C.c_void_p] * 6 + [C.c_double, C.c_double]
+        sets = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]       # block, rows, table, planes
+        L.wlsqm_hip_krylov_schwarz_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
+        L.wlsqm_hip_krylov_schwarz_bytes.restype = C.c_int64
+        L.wlsqm_hip_krylov_schwarz_build_device.argtypes = system + sets + [C.c_void_p, C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_schwarz_apply_device.argtypes = [C.c_int64] + sets + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_schwarz_start_device.argtypes = system + [C.c_int] + sets + [C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                                                                      C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+        L.wlsqm_hip_krylov_schwarz_iterate_device.argtypes = system + [C.c_int] + sets + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+        for name in ("build", "apply", "start", "iterate"):
+            getattr(L, "wlsqm_hip_krylov_schwarz_%s_device" % name).restype = C.c_int
     # coupled fields on one cloud (wlsqm.hip.StencilSystemSolver)
     if hasattr(L, "wlsqm_hip_krylov_system_start_device"):
         # the SELL-64 arrays, total, nop, m, coupling (host), diag (device), diag_const (host)
